@@ -13,7 +13,15 @@ default), or split into C pieces that travel while the next piece is encoded (--
 ends only when every gather has landed. `value` is whole-job input GB/s = bytes all ranks compressed /
 max-over-ranks time. Scaling is weak (fixed work per GPU).
 
-Rank 0 prints ONE JSON line. Besides the contract fields it carries
+Exactly --steps steps are timed (one region between two barriers, unless --min-seconds asks for repeats). A plain run sets
+up, warms up, times the steps, writes the last step's outputs when --dump-outputs DIR is given, and prints the line.
+
+    --dump-outputs DIR   after the timed steps, what the last step handed its caller -- the compressed stream (rank 0's
+                         assembled stream for N > 1) -- as float32/float64 .npy files in DIR: its length, its first 1 MiB,
+                         its last 64 KiB and a fixed, seeded sample of 8 Mi byte positions (about 38 MB in all)
+    --full               everything else below: validation, side measurements, CPU baseline, roofline, exchange costs
+
+Rank 0 prints ONE JSON line. With --full it also carries
   "roofline":     the encode kernel's algorithmic bytes (input read once + compressed bytes written once,
                   SURVEY.md 8d) over its mean launch duration measured with HIP events on the launch stream,
                   against the 8 TB/s HBM peak; "traffic" comes from profiles/traffic.json when present
@@ -21,6 +29,8 @@ Rank 0 prints ONE JSON line. Besides the contract fields it carries
                   oracle restatement (kind "port"), timed on this box's host cores on a bounded sample.
   "check":        untimed validation of the last step: every packet inflated on the device and compared with its
                   input (zz_verify_last_device, all ranks), plus a 64 MiB prefix through zlib on rank 0.
+  "exchange":     N > 1: the encode-only rate and the serial cost of the gather, measured apart from the timed steps;
+and, at level 1 on one GPU, the side measurements "level2", "level6" and "sequential".
 The oracle is only the checker / baseline here, never the thing measured.
 """
 import argparse
@@ -143,6 +153,41 @@ def want_another_region(times, min_total=1.0, max_repeats=64):
     return not times or (len(times) < max_repeats and sum(times) < min_total)
 
 
+DUMP_HEAD = 1 << 20          # --dump-outputs: the stream's first bytes,
+DUMP_TAIL = 1 << 16          # its last bytes (the final block and the container's trailer),
+DUMP_SAMPLE = 8 << 20        # and this many byte positions drawn over the whole stream
+DUMP_SEED = 0x5EED0D0D
+
+
+def sample_positions(nbytes, k=DUMP_SAMPLE, seed=DUMP_SEED):
+    """--dump-outputs: the sorted byte positions sampled from a stream of `nbytes` bytes, a function of (nbytes, k, seed)
+    alone; every position when the stream is no longer than k. Pure host code (tests/test_bench_host.py)."""
+    import numpy as np
+    if nbytes <= k:
+        return np.arange(nbytes, dtype=np.int64)
+    return np.sort(np.random.default_rng(seed).integers(0, nbytes, size=k, dtype=np.int64))
+
+
+def dump_stream(out_dir, stream, nbytes):
+    """--dump-outputs: the first `nbytes` bytes of the uint8 tensor `stream` (what the timed path handed its caller) as
+    compressed_bytes.npy (float64, the length), stream_head.npy, stream_tail.npy and stream_sample.npy (float32 byte values
+    at sample_positions(nbytes)). Returns the names written."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    s = stream[:nbytes]
+    idx = torch.from_numpy(sample_positions(nbytes)).to(s.device)
+    arrays = {
+        "compressed_bytes": np.array([nbytes], dtype=np.float64),
+        "stream_head": s[:DUMP_HEAD].float().cpu().numpy(),
+        "stream_tail": s[max(0, nbytes - DUMP_TAIL):].float().cpu().numpy(),
+        "stream_sample": s[idx].float().cpu().numpy(),
+    }
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return sorted(arrays)
+
+
 def scalar_bound(scalar_insts, kernel_ms, cus=256, clock_ghz=2.4):
     """roofline.scalar: a CU has ONE scalar unit, one instruction per cycle, for all its wavefronts (tools/ubench_scalar.hip:
     0.92 per cycle measured with 32 waves on it). (SALU + branch instructions of a launch) / (CUs x clock x kernel time) = the
@@ -202,7 +247,7 @@ def launch_ranks(n):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=60)      # (a timed region; regions are repeated until they add up to a second)
+    ap.add_argument("--steps", type=int, default=60)      # (the timed region: exactly this many steps)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--level", type=int, default=1)
     ap.add_argument("--mib", type=int, default=1024, help="input MiB per GPU")
@@ -224,11 +269,15 @@ def main():
     ap.add_argument("--gather-root", default="0", choices=["0", "rotate"], help="N > 1: '0' (default) = every step's stream is gathered "
                     "onto rank 0; 'rotate' = step i's onto rank i mod N (still ONE grouped send/recv per stream), so that a run of "
                     "streams is not capped by ONE GPU's seven inbound xGMI links")
-    ap.add_argument("--min-seconds", type=float, default=1.0, help="the timed region (exactly --steps steps) is repeated until the regions "
-                    "add up to this many seconds; 0 = one region (profiler passes)")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg")
-    ap.add_argument("--no-extra", action="store_true", help="skip the level-2 side measurement")
-    ap.add_argument("--no-sequential", action="store_true", help="skip the threaded=false side measurement (64 MiB on one wavefront: seconds)")
+    ap.add_argument("--min-seconds", type=float, default=0.0, help="0 (default) = one timed region of exactly --steps steps; > 0 = the "
+                    "region is repeated until the regions add up to this many seconds, and the line reports the median region")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write the last step's compressed stream "
+                    "(length, head, tail and a seeded sample of positions) to DIR/<name>.npy, so that two builds can be compared")
+    ap.add_argument("--full", action="store_true", help="also validate the last step and run the side measurements, the CPU baseline, "
+                    "the roofline and (N > 1) the exchange costs; a plain run measures the headline only")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the CPU baseline leg")
+    ap.add_argument("--no-extra", action="store_true", help="--full: skip the level-2 side measurement")
+    ap.add_argument("--no-sequential", action="store_true", help="--full: skip the threaded=false side measurement (64 MiB on one wavefront: seconds)")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -448,6 +497,28 @@ def main():
     regions = summarize_regions(region_times, args.steps)
     dt = regions["region_seconds_median"]
 
+    # ---- --dump-outputs: the last step's stream as its caller received it (untimed) ------------------------------------
+    if args.dump_outputs:
+        if not multi:
+            dump = (lanes[state.get("last_lane", 0)]["dst"], state["out_bytes"])
+        elif args.gather == "none":                         # nothing was assembled: rank 0's own shard, raw DEFLATE
+            dump = (shard_b[state.get("last_buf", 0)], state["comp_bytes"])
+        elif pipe is not None:
+            dump = (gathered, state.get("out_bytes"))
+        else:
+            b = state["last_buf"]
+            if root_b[b] != 0:                              # --gather-root rotate left the last stream on another rank: onto rank 0 again
+                from zzflate_amd import sharded
+                w, cks = state["comp_bytes"], state["last_cks"]
+                xshard = shard_b[b] if backend == "nccl" else shard_b[b][:w].cpu()
+                tot = sharded.gather_stream(dist, fmt, xshard, w, cks, n, gathered_b[b] if rank == 0 else None, wait=True)
+                if rank == 0:
+                    state["out_bytes"] = tot
+            dump = (gathered_b[b], state.get("out_bytes"))
+        if rank == 0:
+            dump_stream(args.dump_outputs, dump[0], dump[1])
+        torch.cuda.synchronize()
+
     # ---- validation of what was just measured (untimed) ----------------------------------------------------------
     # every packet this rank produced in the last step is inflated on the device and compared with its input
     # (zz_verify_last_device: a plain RFC 1951 decoder, one lane per packet); rank 0 also inflates a prefix with zlib
@@ -459,7 +530,7 @@ def main():
     # start to landed, nothing else running; bytes_into_rank0: what rank 0's inbound links carry per step. With these a
     # scaling run can tell "the encoders do not scale" from "rank 0's links are full" (DESIGN.md 6).
     exchange = None
-    if multi and pipe is None and args.gather == "rccl":
+    if args.full and multi and pipe is None and args.gather == "rccl":
         from zzflate_amd import sharded
         k2 = max(2, min(args.steps, 5))
         args.gather = "none"
@@ -508,36 +579,37 @@ def main():
                         "gather_ms_serial_onto_last_rank": round(float(g2.item()), 3) if g2 is not None else None,
                         "bytes_into_rank0_per_step": inbound,
                         "inbound_GBps_serial": round(inbound / (float(g1.item()) * 1e-3) / 1e9, 2) if inbound else 0.0}
-    vctx = lanes[state.get("last_lane", 0)]["ctx"] if (not multi) else (mctx[state.get("last_buf", 0)] if pipe is None else ctx)   # the context of the last step
-    bad, first_bad = vctx.verify_last()
-    tv = time.perf_counter() - tv
-    if multi:
-        tb = torch.tensor([bad], dtype=torch.int64, device="cuda")
-        dist.all_reduce(tb)
-        bad = int(tb.item())
-    check["device_inflate"] = {"packets": ((n + P - 1) // P) * world, "bad": bad, "seconds_rank0": round(tv, 3)}
-    if rank == 0:
-        import zlib
-        if multi and args.gather == "none":                 # nothing was assembled: rank 0's own shard, raw DEFLATE
-            out_t = shard_b[state.get("last_buf", 0)]
-            k = min(state["comp_bytes"], 96 << 20)
-            wb = -15
-        else:
-            out_t = lanes[state.get("last_lane", 0)]["dst"] if (not multi) else gathered_b[state.get("last_buf", 0)]
-            k = min(state["out_bytes"], 96 << 20)
-            wb = {0: 15, 1: 31, 2: -15}[fmt]
-        head = out_t[:k].cpu().numpy().tobytes()
-        o = zlib.decompressobj(wb)
-        try:
-            dec = o.decompress(head, 64 << 20)
-        except zlib.error:            # an invalid stream is reported in the line (inflate_prefix_ok false), not as a crash
-            dec = b""
-        ref = src[:len(dec)].cpu().numpy().tobytes() if len(dec) <= n else None
-        check["inflate_prefix_ok"] = bool(ref is not None and dec == ref)
-        check["inflate_prefix_bytes"] = len(dec)
+    if args.full:
+        vctx = lanes[state.get("last_lane", 0)]["ctx"] if (not multi) else (mctx[state.get("last_buf", 0)] if pipe is None else ctx)   # the context of the last step
+        bad, first_bad = vctx.verify_last()
+        tv = time.perf_counter() - tv
+        if multi:
+            tb = torch.tensor([bad], dtype=torch.int64, device="cuda")
+            dist.all_reduce(tb)
+            bad = int(tb.item())
+        check["device_inflate"] = {"packets": ((n + P - 1) // P) * world, "bad": bad, "seconds_rank0": round(tv, 3)}
+        if rank == 0:
+            import zlib
+            if multi and args.gather == "none":                 # nothing was assembled: rank 0's own shard, raw DEFLATE
+                out_t = shard_b[state.get("last_buf", 0)]
+                k = min(state["comp_bytes"], 96 << 20)
+                wb = -15
+            else:
+                out_t = lanes[state.get("last_lane", 0)]["dst"] if (not multi) else gathered_b[state.get("last_buf", 0)]
+                k = min(state["out_bytes"], 96 << 20)
+                wb = {0: 15, 1: 31, 2: -15}[fmt]
+            head = out_t[:k].cpu().numpy().tobytes()
+            o = zlib.decompressobj(wb)
+            try:
+                dec = o.decompress(head, 64 << 20)
+            except zlib.error:            # an invalid stream is reported in the line (inflate_prefix_ok false), not as a crash
+                dec = b""
+            ref = src[:len(dec)].cpu().numpy().tobytes() if len(dec) <= n else None
+            check["inflate_prefix_ok"] = bool(ref is not None and dec == ref)
+            check["inflate_prefix_bytes"] = len(dec)
 
     extra = {}
-    if rank == 0 and (not multi) and not args.no_extra and args.level == 1:
+    if args.full and rank == 0 and (not multi) and not args.no_extra and args.level == 1:
         # the config's "dynamic Huffman" wording means reference level 2: side measurement
         try:
             cap2 = zz.bound(n, fmt, 2, P)
@@ -617,66 +689,13 @@ def main():
             extra["sequential"] = {"error": str(e)}
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu:        # (the CPU leg runs at N = 1 only: the other ranks would wait for it)
+    if args.full and rank == 0 and world == 1 and not args.no_cpu:        # (the CPU leg runs at N = 1 only: the other ranks would wait for it)
         sample_bytes = min(n, 1 << 30)
         # the reference has no level above 3 (zzflate.cpp:201,230): its level 3 is the baseline of the extended levels
         cpu = cpu_baseline(src[:sample_bytes].cpu().numpy().tobytes(), min(args.level, 3), fmt, P)
 
     if rank == 0:
         ms = dt / args.steps * 1e3
-        kms = sum(kernel_ms) / max(1, len(kernel_ms))
-        comp = state["comp_bytes"]
-        algo_bytes = n + comp                      # per launch on this rank: input once + compressed once
-        achieved = algo_bytes / (kms * 1e-3) / 1e9 if kms > 0 else None
-        if (not multi) and len(lanes) > 1:
-            achieved = None                        # event times of overlapping kernels include the sharing of the CUs
-        # HBM traffic of the dominant kernel comes from separate rocprofv3 --pmc passes (tools/collect_profiles.sh; counters
-        # cannot be read inside this run). profiles/traffic.json records which sources it was measured on: it is only
-        # reported while those are the sources this run was built from.
-        traffic, traffic_src, insts, tj_scalar = None, None, None, None
-        tpath = os.path.join(ROOT, "profiles", "traffic.json")
-        if os.path.exists(tpath):
-            try:
-                import hashlib
-                tj = json.load(open(tpath))
-                hsh = hashlib.sha256()
-                cdir = os.path.join(ROOT, "zzflate_amd", "csrc")
-                for f in sorted(os.listdir(cdir)):
-                    hsh.update(f.encode()); hsh.update(open(os.path.join(cdir, f), "rb").read())
-                if tj.get("source_sha256") == hsh.hexdigest():
-                    traffic = tj.get(f"level{args.level}_{args.gen}_{args.mib}MiB")
-                    insts = tj.get(f"instructions_level{args.level}_{args.gen}_{args.mib}MiB")
-                    tj_scalar = tj.get(f"scalar_instructions_level{args.level}_{args.gen}_{args.mib}MiB")
-                    traffic_src = f"profiles/traffic.json @ {tj.get('git_sha')}"
-                    # the counters were collected on the default (cold, two-parser) kernels: another kernel's line does not borrow them
-                    other = bool(args.warm) or os.environ.get("ZZFLATE_L1_KERNEL") == "classic" or os.environ.get("ZZFLATE_L2_KERNEL") == "classic" \
-                        or (args.level == 1 and hasattr(zz.lib, "zz_debug_l1_kernel") and zz.lib.zz_debug_l1_kernel(ctx._h) != 2)
-                    if other and traffic is not None:
-                        traffic, insts, tj_scalar = None, None, None
-                        traffic_src += " was measured on the default kernel of this level, not on the one this run launched: not reported"
-                else:
-                    traffic_src = f"profiles/traffic.json @ {tj.get('git_sha')} is stale (kernel sources changed since): not reported"
-            except Exception:
-                traffic = None
-        # The bound that applies to levels >= 1 is not HBM but instruction issue (SURVEY.md hard part 5): a
-        # wavefront issues at most one instruction per ~5 cycles (tools/ubench_valu.hip), and the LDS hash table admits 9
-        # workgroups of 2 wavefronts per CU. issue.bound_ms = the kernel's wave-level instructions (SQ_INSTS_*, from the same
-        # profile pass as `traffic`) x 5 cycles / (resident wavefronts x clock): what the kernel would take if every resident
-        # wavefront issued flat out; frac = bound_ms / kernel_ms.
-        issue = None
-        # which level-1 kernel ran: asked of the library (ZZFLATE_L1_KERNEL=classic and a negative LDS-order verdict both give k_encode_l1)
-        l1_two = args.level == 1 and not args.warm and (not hasattr(zz.lib, "zz_debug_l1_kernel") or zz.lib.zz_debug_l1_kernel(ctx._h) == 2)
-        classic = os.environ.get("ZZFLATE_L1_KERNEL") == "classic"
-        l1_kernel = ("k_encode_l1w" if classic else "k_encode_l1pw") if args.warm else ("k_encode_l1p" if l1_two else "k_encode_l1")
-        l1_two = l1_two or (args.level == 1 and bool(args.warm) and not classic)
-        scal = tj_scalar if (args.level == 1 and l1_two) or args.level in (2, 3) else None
-        if insts and kms > 0 and args.level >= 1:
-            l2_two = args.level in (2, 3) and not args.warm and os.environ.get("ZZFLATE_L2_KERNEL") != "classic"
-            resident = 256 * (8 if args.level >= 4 else 9) * (3 if (l1_two or l2_two) else 2)     # k_encode_l1p / k_encode_l2p: two parsers + the emitter / helper per packet
-            cpi, ghz = 5.0, 2.4
-            bound_ms = insts * cpi / (resident * ghz * 1e9) * 1e3
-            issue = {"bound": "issue", "instructions": insts, "cycles_per_instruction": cpi, "resident_wavefronts": resident,
-                     "clock_ghz": ghz, "bound_ms": round(bound_ms, 3), "frac": round(bound_ms / kms, 4)}
         line = {
             "metric": "input GB/s compressed (whole node) + ratio, level 1, 1/2/4/8 MI355X",
             "value": round(total_n * args.steps / dt / 1e9, 3),
@@ -702,21 +721,77 @@ def main():
                 "level": args.level, "packet_size": P, "bytes_per_gpu": n, "format": args.format, "warm_window": args.warm,
             },
             "calls_in_flight": len(lanes) if (not multi) else None,
-            "exchange": exchange if multi else None,
-            "roofline": {
-                "bound": "hbm", "kernel": ("k_l6_matches + k_encode_l2_t<32768, true>" if args.level >= 4 else
-                                           ("k_encode_l2_t<32768, false>" if args.warm else "k_encode_l2_t<0, false>" if os.environ.get("ZZFLATE_L2_KERNEL") == "classic"
-                                            else "k_encode_l2_t<0, false, true> (k_encode_l2p)") if args.level >= 2
-                                           else l1_kernel if args.level == 1 else "k_encode_l0"),
-                "achieved": round(achieved, 2) if achieved else None, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                "frac": round(achieved / HBM_PEAK_GBS, 5) if achieved else None,
-                "algorithmic_bytes_per_launch": algo_bytes, "kernel_ms": round(kms, 4), "traffic": traffic,
-                "traffic_source": traffic_src, "issue": issue, "scalar": scalar_bound(scal, kms),
-            },
-            "cpu_baseline": cpu,
-            "check": check,
         }
-        line.update(extra)
+        if args.full:
+            kms = sum(kernel_ms) / max(1, len(kernel_ms))
+            comp = state["comp_bytes"]
+            algo_bytes = n + comp                      # per launch on this rank: input once + compressed once
+            achieved = algo_bytes / (kms * 1e-3) / 1e9 if kms > 0 else None
+            if (not multi) and len(lanes) > 1:
+                achieved = None                        # event times of overlapping kernels include the sharing of the CUs
+            # HBM traffic of the dominant kernel comes from separate rocprofv3 --pmc passes (tools/collect_profiles.sh; counters
+            # cannot be read inside this run). profiles/traffic.json records which sources it was measured on: it is only
+            # reported while those are the sources this run was built from.
+            traffic, traffic_src, insts, tj_scalar = None, None, None, None
+            tpath = os.path.join(ROOT, "profiles", "traffic.json")
+            if os.path.exists(tpath):
+                try:
+                    import hashlib
+                    tj = json.load(open(tpath))
+                    hsh = hashlib.sha256()
+                    cdir = os.path.join(ROOT, "zzflate_amd", "csrc")
+                    for f in sorted(os.listdir(cdir)):
+                        hsh.update(f.encode()); hsh.update(open(os.path.join(cdir, f), "rb").read())
+                    if tj.get("source_sha256") == hsh.hexdigest():
+                        traffic = tj.get(f"level{args.level}_{args.gen}_{args.mib}MiB")
+                        insts = tj.get(f"instructions_level{args.level}_{args.gen}_{args.mib}MiB")
+                        tj_scalar = tj.get(f"scalar_instructions_level{args.level}_{args.gen}_{args.mib}MiB")
+                        traffic_src = f"profiles/traffic.json @ {tj.get('git_sha')}"
+                        # the counters were collected on the default (cold, two-parser) kernels: another kernel's line does not borrow them
+                        other = bool(args.warm) or os.environ.get("ZZFLATE_L1_KERNEL") == "classic" or os.environ.get("ZZFLATE_L2_KERNEL") == "classic" \
+                            or (args.level == 1 and hasattr(zz.lib, "zz_debug_l1_kernel") and zz.lib.zz_debug_l1_kernel(ctx._h) != 2)
+                        if other and traffic is not None:
+                            traffic, insts, tj_scalar = None, None, None
+                            traffic_src += " was measured on the default kernel of this level, not on the one this run launched: not reported"
+                    else:
+                        traffic_src = f"profiles/traffic.json @ {tj.get('git_sha')} is stale (kernel sources changed since): not reported"
+                except Exception:
+                    traffic = None
+            # The bound that applies to levels >= 1 is not HBM but instruction issue (SURVEY.md hard part 5): a
+            # wavefront issues at most one instruction per ~5 cycles (tools/ubench_valu.hip), and the LDS hash table admits 9
+            # workgroups of 2 wavefronts per CU. issue.bound_ms = the kernel's wave-level instructions (SQ_INSTS_*, from the same
+            # profile pass as `traffic`) x 5 cycles / (resident wavefronts x clock): what the kernel would take if every resident
+            # wavefront issued flat out; frac = bound_ms / kernel_ms.
+            issue = None
+            # which level-1 kernel ran: asked of the library (ZZFLATE_L1_KERNEL=classic and a negative LDS-order verdict both give k_encode_l1)
+            l1_two = args.level == 1 and not args.warm and (not hasattr(zz.lib, "zz_debug_l1_kernel") or zz.lib.zz_debug_l1_kernel(ctx._h) == 2)
+            classic = os.environ.get("ZZFLATE_L1_KERNEL") == "classic"
+            l1_kernel = ("k_encode_l1w" if classic else "k_encode_l1pw") if args.warm else ("k_encode_l1p" if l1_two else "k_encode_l1")
+            l1_two = l1_two or (args.level == 1 and bool(args.warm) and not classic)
+            scal = tj_scalar if (args.level == 1 and l1_two) or args.level in (2, 3) else None
+            if insts and kms > 0 and args.level >= 1:
+                l2_two = args.level in (2, 3) and not args.warm and os.environ.get("ZZFLATE_L2_KERNEL") != "classic"
+                resident = 256 * (8 if args.level >= 4 else 9) * (3 if (l1_two or l2_two) else 2)     # k_encode_l1p / k_encode_l2p: two parsers + the emitter / helper per packet
+                cpi, ghz = 5.0, 2.4
+                bound_ms = insts * cpi / (resident * ghz * 1e9) * 1e3
+                issue = {"bound": "issue", "instructions": insts, "cycles_per_instruction": cpi, "resident_wavefronts": resident,
+                         "clock_ghz": ghz, "bound_ms": round(bound_ms, 3), "frac": round(bound_ms / kms, 4)}
+            line.update({
+                "exchange": exchange if multi else None,
+                "roofline": {
+                    "bound": "hbm", "kernel": ("k_l6_matches + k_encode_l2_t<32768, true>" if args.level >= 4 else
+                                               ("k_encode_l2_t<32768, false>" if args.warm else "k_encode_l2_t<0, false>" if os.environ.get("ZZFLATE_L2_KERNEL") == "classic"
+                                                else "k_encode_l2_t<0, false, true> (k_encode_l2p)") if args.level >= 2
+                                               else l1_kernel if args.level == 1 else "k_encode_l0"),
+                    "achieved": round(achieved, 2) if achieved else None, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                    "frac": round(achieved / HBM_PEAK_GBS, 5) if achieved else None,
+                    "algorithmic_bytes_per_launch": algo_bytes, "kernel_ms": round(kms, 4), "traffic": traffic,
+                    "traffic_source": traffic_src, "issue": issue, "scalar": scalar_bound(scal, kms),
+                },
+                "cpu_baseline": cpu,
+                "check": check,
+            })
+            line.update(extra)
         print(json.dumps(line), flush=True)
     if multi:
         dist.destroy_process_group()

@@ -1,8 +1,11 @@
 """Host-side pieces of bench.py that need no GPU: the core count the CPU baseline may use, and the native timing drivers
-(oracle/ref_harness.cpp zzref_bench, oracle/zzoracle.c zzo_bench) on a small sample."""
+(oracle/ref_harness.cpp zzref_bench, oracle/zzoracle.c zzo_bench) on a small sample; and, on a GPU, one plain run of
+bench.py with --dump-outputs."""
 import ctypes
 import os
 import sys
+
+import pytest
 
 from conftest import ROOT
 
@@ -91,3 +94,53 @@ def test_scalar_unit_bound_arithmetic():
     b = bench.scalar_bound(2_660_000_000, 7.34)
     assert abs(b["per_cu_per_cycle"] - 2.66e9 / (256 * 2.4e9 * 7.34e-3)) < 1e-4 and 0.6 < b["frac"] < 0.7
     assert bench.scalar_bound(None, 7.0) is None and bench.scalar_bound(1, 0) is None
+
+
+def test_dump_sample_positions_are_fixed_and_bounded():
+    """--dump-outputs samples the same sorted positions for the same stream length, every position of a short stream, and
+    the four arrays of a dump stay far below 64 MB"""
+    import numpy as np
+    a, b = bench.sample_positions(700_000_000), bench.sample_positions(700_000_000)
+    assert a.dtype == np.int64 and len(a) == bench.DUMP_SAMPLE and np.array_equal(a, b)
+    assert a[0] >= 0 and a[-1] < 700_000_000 and np.all(a[1:] >= a[:-1])
+    assert np.array_equal(bench.sample_positions(1000), np.arange(1000)) and len(bench.sample_positions(0)) == 0
+    assert not np.array_equal(bench.sample_positions(10 ** 9, 1000), bench.sample_positions(10 ** 9, 1000, seed=1))
+    assert 8 + 4 * (bench.DUMP_HEAD + bench.DUMP_TAIL + bench.DUMP_SAMPLE) < 64 * 10 ** 6
+
+
+@pytest.mark.gpu
+def test_plain_run_times_its_steps_and_dumps_the_last_stream(tmp_path):
+    """A plain run times exactly --steps steps, carries only the headline fields, and --dump-outputs writes the last
+    step's stream: the same arrays from run to run, a head that inflates to the benchmark's input"""
+    import json
+    import subprocess
+    import zlib
+    import numpy as np
+    dumps = []
+    for k in range(2):
+        d = tmp_path / f"out{k}"
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                            "--mib", "64", "--dump-outputs", str(d)], capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stdout + r.stderr
+        line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+        assert line["steps"] == 3 and line["repeats"] == 1 and line["ms_per_step"] > 0 and line["value"] > 0
+        assert abs(line["timed_seconds_total"] - line["ms_per_step"] * 3e-3) < 2e-3
+        assert not {"check", "roofline", "cpu_baseline", "level2"} & set(line)
+        arrays = {f.stem: np.load(f) for f in sorted(d.glob("*.npy"))}
+        assert set(arrays) == {"compressed_bytes", "stream_head", "stream_tail", "stream_sample"}
+        assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+        nbytes = int(arrays["compressed_bytes"][0])
+        assert abs(nbytes / (64 << 20) - line["ratio"]) < 1e-3
+        dumps.append(arrays)
+    for name in dumps[0]:
+        assert np.array_equal(dumps[0][name], dumps[1][name]), name
+    a = dumps[0]
+    head = a["stream_head"].astype(np.uint8).tobytes()
+    dec = zlib.decompressobj(15).decompress(head)
+    assert len(dec) > 0 and dec == zz.generate_host(zz.GEN_TEXT, bench.SEEDS["text"], 0, len(dec))
+    pos = bench.sample_positions(nbytes)
+    inside = pos < len(head)
+    assert np.array_equal(a["stream_sample"][inside], a["stream_head"][pos[inside]])
+    tail0 = nbytes - len(a["stream_tail"])
+    at_end = pos >= tail0
+    assert np.array_equal(a["stream_sample"][at_end], a["stream_tail"][pos[at_end] - tail0])

@@ -125,7 +125,7 @@ def test_bench_launches_its_own_ranks(tmp_path):
     env = dict(os.environ, ZZ_BENCH_BACKEND="gloo")
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--mib", "64",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--mib", "64", "--full",
                         "--no-cpu", "--no-extra"], env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout + r.stderr
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
@@ -140,7 +140,7 @@ def test_bench_launches_its_own_ranks(tmp_path):
     assert 0 < ex["bytes_into_rank0_per_step"] < total - hl - tl          # rank 1's shard, and only that
     assert abs(ex["bytes_into_rank0_per_step"] - (total - hl - tl) / 2) < 0.2 * total
     # --gather none: the encoders alone
-    r2 = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--mib", "64",
+    r2 = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--mib", "64", "--full",
                          "--no-cpu", "--no-extra", "--gather", "none"], env=env, capture_output=True, text=True, timeout=900)
     assert r2.returncode == 0, r2.stdout + r2.stderr
     l2 = json.loads([l for l in r2.stdout.splitlines() if l.startswith("{")][-1])
@@ -148,7 +148,7 @@ def test_bench_launches_its_own_ranks(tmp_path):
     assert l2["check"]["device_inflate"]["bad"] == 0 and l2["check"]["inflate_prefix_ok"]
     # --gather-root rotate: step i's stream lands on rank i mod 2 (three steps: both ranks take a turn); the line, the
     # device inflate of every packet and the zlib check of the stream on rank 0 must come out the same
-    r3 = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--mib", "64",
+    r3 = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--mib", "64", "--full",
                          "--no-cpu", "--no-extra", "--gather-root", "rotate"], env=env, capture_output=True, text=True, timeout=900)
     assert r3.returncode == 0, r3.stdout + r3.stderr
     l3 = json.loads([l for l in r3.stdout.splitlines() if l.startswith("{")][-1])
@@ -167,7 +167,7 @@ def test_rccl_path_with_one_rank(tmp_path):
     env = dict(os.environ, ZZ_BENCH_FORCE_DIST="1", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(_free_port()))
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "ZZ_BENCH_BACKEND"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--mib", "64",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--mib", "64", "--full",
                         "--no-cpu", "--no-extra"], env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout + r.stderr
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])

@@ -6,6 +6,6 @@ A=$1; B=$2; shift 2
 for r in 1 2 3; do
   for L in $A $B; do
     echo -n "$L: "
-    ZZFLATE_AMD_LIB=$R/$L timeout -k 5 200 python $R/bench.py --steps 10 --no-cpu "$@" 2>&1 | tail -1 | python3 -c "import json,sys; d=json.loads(sys.stdin.read()); print(d['value'], d['roofline']['kernel_ms'], (d.get('level2') or {}).get('value'))"
+    ZZFLATE_AMD_LIB=$R/$L timeout -k 5 200 python $R/bench.py --full --min-seconds 1 --steps 10 --no-cpu "$@" 2>&1 | tail -1 | python3 -c "import json,sys; d=json.loads(sys.stdin.read()); print(d['value'], d['roofline']['kernel_ms'], (d.get('level2') or {}).get('value'))"
   done
 done

@@ -1,6 +1,6 @@
 #!/bin/bash
 # the bench.py lines behind the table in profiles/README.md (one GPU, 1 GiB per call unless said otherwise)
-run() { echo "## bench.py $*"; timeout -k 10 400 python bench.py "$@" 2>&1 | tail -1; }
+run() { echo "## bench.py $*"; timeout -k 10 400 python bench.py --full --min-seconds 1 "$@" 2>&1 | tail -1; }
 run --steps 10 --warmup 2
 run --steps 5 --level 2 --no-cpu --no-extra
 run --steps 5 --level 0 --gen random --no-cpu --no-extra

@@ -7,7 +7,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$R/gpurun_out/prof/${TAG}_busy
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
-B="python3 $R/bench.py --no-cpu --no-sequential --no-extra --min-seconds 0 --steps 2 --warmup 1"
+B="python3 $R/bench.py --full --no-cpu --no-sequential --no-extra --min-seconds 0 --steps 2 --warmup 1"
 run() { name=$1; shift; echo "[busy] $name"; timeout -k 10 200 rocprofv3 "$@" > "$OUT/$name.log" 2>&1 || echo "[busy] $name failed: $(tail -2 $OUT/$name.log)"; }
 run busy1_l1  --pmc SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_SCA SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_VMEM SQ_INST_CYCLES_SALU SQ_BUSY_CYCLES SQ_WAVES \
               --output-format csv -d "$OUT/busy1_l1" -- $B

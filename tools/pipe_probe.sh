@@ -11,7 +11,7 @@ mkdir -p $D
 line() { python3 -c 'import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(d["value"], "GB/s  kernel_ms", d["roofline"]["kernel_ms"])'; }
 for gen in ${@:-text mix logs}; do
   for r in 1 2; do
-    echo -n "$gen shipped: "; timeout -k 10 200 python3 $R/bench.py --steps 5 --no-cpu --no-extra --gen $gen 2>&1 | line
-    echo -n "$gen probe  : "; ZZFLATE_AMD_LIB=$D/lib.so timeout -k 10 200 python3 $R/bench.py --steps 5 --no-cpu --no-extra --gen $gen 2>&1 | line
+    echo -n "$gen shipped: "; timeout -k 10 200 python3 $R/bench.py --full --min-seconds 1 --steps 5 --no-cpu --no-extra --gen $gen 2>&1 | line
+    echo -n "$gen probe  : "; ZZFLATE_AMD_LIB=$D/lib.so timeout -k 10 200 python3 $R/bench.py --full --min-seconds 1 --steps 5 --no-cpu --no-extra --gen $gen 2>&1 | line
   done
 done

@@ -18,7 +18,7 @@ for r in 1 2; do
   for v in "${VARS[@]}"; do
     for g in $GENS; do
       echo -n "[$v] $g: "
-      ZZFLATE_AMD_LIB=/tmp/sweep/lib_$i.so timeout -k 5 200 python3 $R/bench.py --steps 5 --no-cpu --no-extra --gen $g 2>&1 | tail -1 | python3 -c 'import json,sys; d=json.loads(sys.stdin.read()); print(d["value"], "GB/s kernel_ms", d["roofline"]["kernel_ms"], "bad", d["check"]["device_inflate"]["bad"])'
+      ZZFLATE_AMD_LIB=/tmp/sweep/lib_$i.so timeout -k 5 200 python3 $R/bench.py --full --min-seconds 1 --steps 5 --no-cpu --no-extra --gen $g 2>&1 | tail -1 | python3 -c 'import json,sys; d=json.loads(sys.stdin.read()); print(d["value"], "GB/s kernel_ms", d["roofline"]["kernel_ms"], "bad", d["check"]["device_inflate"]["bad"])'
     done
     i=$((i+1))
   done

@@ -9,10 +9,10 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 cd /tmp && export TMPDIR=/tmp
 for pad in 0 2500 9000 22000 36000; do
   wg=$((163840 / (17932 + pad)))
-  out=$(ZZFLATE_L1_PAD_LDS=$pad timeout -k 10 200 python3 $R/bench.py --steps 5 --no-cpu --no-extra --no-sequential 2>&1 | tail -1)
+  out=$(ZZFLATE_L1_PAD_LDS=$pad timeout -k 10 200 python3 $R/bench.py --full --min-seconds 1 --steps 5 --no-cpu --no-extra --no-sequential 2>&1 | tail -1)
   val=$(echo "$out" | python3 -c "import sys,json; d=json.loads(sys.stdin.read()); print(d['value'], d['roofline']['kernel_ms'])")
   rm -rf /tmp/tvo_$pad
-  ZZFLATE_L1_PAD_LDS=$pad timeout -k 10 280 rocprofv3 --pmc FETCH_SIZE --output-format csv -d /tmp/tvo_$pad -- python3 $R/bench.py --steps 2 --warmup 1 --no-cpu --no-extra --no-sequential > /tmp/tvo_$pad.log 2>&1
+  ZZFLATE_L1_PAD_LDS=$pad timeout -k 10 280 rocprofv3 --pmc FETCH_SIZE --output-format csv -d /tmp/tvo_$pad -- python3 $R/bench.py --full --min-seconds 1 --steps 2 --warmup 1 --no-cpu --no-extra --no-sequential > /tmp/tvo_$pad.log 2>&1
   f=$(python3 - <<PY
 import csv, glob, collections
 per = collections.defaultdict(float)

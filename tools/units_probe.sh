@@ -14,7 +14,7 @@ if [ ! -f $D/lib.so ]; then
   sed -i "s/#define ZZ_HASH_BITS 13/#define ZZ_HASH_BITS 10/" $D/zzflate_amd/csrc/zz_common.h
   /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -shared -o $D/lib.so $D/zzflate_amd/csrc/zz_api.hip $D/zzflate_amd/csrc/zz_cxx_shim.cpp || exit 1
 fi
-B="python3 $R/bench.py --no-cpu --no-extra --steps 2 --warmup 1 --gen $GEN"
+B="python3 $R/bench.py --full --min-seconds 1 --no-cpu --no-extra --steps 2 --warmup 1 --gen $GEN"
 pass() {  # name lib counters...
   name=$1; lib=$2; shift 2
   echo "[units] $name"
