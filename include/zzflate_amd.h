@@ -50,7 +50,10 @@ enum {
     ZZ_E_NOSPACE = -2,      /* destination too small */
     ZZ_E_HIP = -3,          /* HIP runtime error / no device */
     ZZ_E_ARG = -4,          /* bad argument (packet size, null pointer) */
-    ZZ_E_UNSUPPORTED = -5   /* the device lacks a property the requested mode needs (zz_ctx_set_warm_window, zz_ctx_set_extended_levels) */
+    ZZ_E_UNSUPPORTED = -5,  /* the device lacks a property the requested mode needs (zz_ctx_set_warm_window, zz_ctx_set_extended_levels);
+                               zz_decode_device: a preset dictionary (FDICT) */
+    ZZ_E_DATA = -6          /* not a valid stream of the requested format: header, block structure, distance too far back,
+                               checksum or ISIZE mismatch, bytes behind the trailer */
 };
 
 #define ZZ_DEFAULT_PACKET 32768u
@@ -186,9 +189,47 @@ int zz_verify_last_device(zz_ctx* ctx, uint64_t* bad_packets, uint64_t* first_ba
 
 /* Random access: where packet k (input bytes [k*packet_size, (k+1)*packet_size)) of the stream produced by the LAST
  * zz_encode_device / zz_encode_shard_device call on this context lies. *offset counts from the first byte of the
- * DEFLATE stream (behind the container header), *bytes is the packet's length. Packets are independent byte-aligned
- * runs of complete blocks (zzflate.cpp:101-125), so each can be inflated on its own. */
+ * DEFLATE stream (behind the container header), *bytes is the packet's length. Packets are byte-aligned runs of complete
+ * blocks (zzflate.cpp:101-125) that start with an empty bit buffer and fresh codes. At levels 0 and 1 with cold packets
+ * each can be inflated on its own. At levels >= 2 a match may reach in front of the packet's start (the backward
+ * extension, encoder.cpp:404; warm windows and levels 4..6 up to 32 KiB back), so a packet needs the bytes in front of
+ * it -- zz_decode_device resolves such references across packets. */
 int zz_packet_extent_device(zz_ctx* ctx, uint64_t packet, uint64_t* offset, uint64_t* bytes, void* hip_stream);
+
+/* ---- decode (beyond the reference, whose decoder.h is an empty stub) ------------------------------------------------
+ * The packet index of the LAST zz_encode_device / zz_encode_shard_device call on this context: entries = npk + 1
+ * offsets counted from the first DEFLATE byte, index[npk] = stream bytes (level 0 included; its offsets are arithmetic;
+ * an empty input's one empty block counts as a packet). *entries is set even when max_entries is too small
+ * (ZZ_E_NOSPACE). Small (8 bytes per packet); callers that store a stream can store it beside it. */
+int zz_packet_index_device(zz_ctx* ctx, uint64_t* d_index, uint64_t max_entries, uint64_t* entries, void* hip_stream);
+
+/* d_src[0, src_len) = a zlib / gzip / raw stream -> d_dst; *out_len = decompressed bytes.
+ *   packet_size 1..32768 and d_index != NULL : packets at the given offsets, decoded in parallel
+ *   packet_size 1..32768 and d_index == NULL : packet starts found on the device (after every 01 00 FE FF), then as above
+ *   packet_size 0                            : any single-member RFC 1950/1951/1952 stream, serial
+ * Every valid stream decodes to its bytes whatever packet_size and d_index say: they decide speed, not the result (an
+ * index or a packet size that does not fit the stream sends the call to the serial path). The trailer (Adler-32, or
+ * CRC-32 and ISIZE) is checked on the device; ZZ_E_DATA for an invalid stream, ZZ_E_NOSPACE when the output does not
+ * fit `cap` (nothing is written past it), ZZ_E_UNSUPPORTED for a preset dictionary. A shard that is not the first
+ * refers to bytes in front of it: ZZ_E_DATA. d_index holds `entries` int64 offsets in device memory.
+ * Cost of errors: a packet-mode stream whose packets all decode but whose output exceeds `cap` gives ZZ_E_NOSPACE at
+ * the parallel rate. Any other failure of the parallel paths -- a corrupt byte, a truncated stream, bytes behind the
+ * trailer, an index that does not describe the stream -- is decided by the serial path, which runs at a few MB/s: a
+ * damaged multi-GiB stream takes minutes to be refused.
+ * Workspace: at most ~270 MiB (4 bytes per output byte of a 64 MiB batch, 20 bytes per packet of a batch); discovery adds
+ * 20 bytes per candidate, at most 4 Mi candidates. Synchronous, like zz_encode_device. */
+int zz_decode_device(zz_ctx* ctx, const void* d_src, uint64_t src_len, void* d_dst, uint64_t cap, uint64_t* out_len,
+                     int format, uint32_t packet_size, const uint64_t* d_index, uint64_t entries, void* hip_stream);
+
+enum { ZZ_DECODE_INDEXED = 1, ZZ_DECODE_DISCOVERED = 2, ZZ_DECODE_SERIAL = 3 };
+/* which path the last zz_decode_device finished on (0: none) */
+int zz_ctx_last_decode_path(const zz_ctx* ctx);
+/* the packet index the last zz_decode_device recovered by discovery (path ZZ_DECODE_DISCOVERED; ZZ_E_ARG otherwise), in
+ * the form of zz_packet_index_device: *entries = packets + 1 (set even when max_entries is too small: ZZ_E_NOSPACE) */
+int zz_ctx_last_decode_index_device(zz_ctx* ctx, uint64_t* d_index, uint64_t max_entries, uint64_t* entries, void* hip_stream);
+/* what the last zz_decode_device's parallel path saw: bytes phase 1 left pending (their match source lay in front of
+ * their packet) and the pointer-jumping rounds that resolved them (0 and 0 on the serial path) */
+int zz_ctx_last_decode_stats(const zz_ctx* ctx, uint64_t* pending_bytes, uint32_t* rounds);
 
 /* container pieces for assembling shards on the host */
 int zz_header(int format, uint8_t out[10]);                                   /* returns 0/2/10 */

@@ -84,6 +84,11 @@ def _load():
         "zz_encode_multi_device": (i32, [ctypes.POINTER(vp), i32, ctypes.POINTER(vp), pu64, pu64, vp, u64, pu64, i32, i32, u32]),
         "zz_verify_last_device": (i32, [vp, pu64, pu64, vp]),
         "zz_packet_extent_device": (i32, [vp, u64, pu64, pu64, vp]),
+        "zz_packet_index_device": (i32, [vp, vp, u64, pu64, vp]),
+        "zz_decode_device": (i32, [vp, vp, u64, vp, u64, pu64, i32, u32, vp, u64, vp]),
+        "zz_ctx_last_decode_path": (i32, [vp]),
+        "zz_ctx_last_decode_stats": (i32, [vp, pu64, ctypes.POINTER(u32)]),
+        "zz_ctx_last_decode_index_device": (i32, [vp, vp, u64, pu64, vp]),
         "zz_header": (i32, [i32, vp]),
         "zz_trailer": (i32, [i32, u32, u64, vp]),
         "zz_adler32": (u32, [u32, vp, u64]),
@@ -208,6 +213,9 @@ def generate_host(kind, seed, first_byte, n):
 
 
 GEN_TEXT, GEN_RANDOM, GEN_LOG, GEN_MIX = 0, 1, 2, 3
+# which path a decode finished on (Context.last_decode_path)
+DECODE_INDEXED, DECODE_DISCOVERED, DECODE_SERIAL = 1, 2, 3
+E_NOSPACE, E_UNSUPPORTED, E_DATA = -2, -5, -6
 
 
 class Context:
@@ -347,6 +355,62 @@ class Context:
         st = self._stream() if stream is None else stream
         _check(lib.zz_packet_extent_device(self._h, k, ctypes.byref(off), ctypes.byref(nb), st))
         return off.value, nb.value
+
+    def packet_index(self, stream=None):
+        """The packet index of the last encode / encode_shard call: an int64 tensor of npk + 1 offsets on this context's
+        device, counted from the first DEFLATE byte; the last one is the stream's length. Store it beside the stream to
+        decode it in parallel later."""
+        import torch
+        entries = ctypes.c_uint64(0)
+        st = self._stream() if stream is None else stream
+        rc = lib.zz_packet_index_device(self._h, None, 0, ctypes.byref(entries), st)
+        if rc not in (0, E_NOSPACE) or entries.value == 0:
+            _check(rc)
+        idx = torch.empty(entries.value, dtype=torch.int64, device=f"cuda:{self.device}")
+        _check(lib.zz_packet_index_device(self._h, idx.data_ptr(), entries.value, ctypes.byref(entries), st))
+        return idx
+
+    def decode(self, src, src_len, dst, cap, format=Format.Zlib, packet_size=DEFAULT_PACKET, index=None, stream=None):
+        """Decode the zlib / gzip / raw stream ``src[:src_len]`` into ``dst`` (``cap`` bytes); returns the decoded length.
+        ``packet_size`` 1..32768 with ``index`` (an int64 tensor from ``packet_index``): packets decoded in parallel;
+        without ``index``: packet starts found on the device first; ``packet_size`` 0: any stream, serially. Any valid
+        stream decodes whatever they say. Raises ZzFlateError (code E_DATA, E_NOSPACE, E_UNSUPPORTED) otherwise."""
+        out = ctypes.c_uint64(0)
+        st = self._stream() if stream is None else stream
+        ip, ne = None, 0
+        if index is not None:
+            import torch
+            if not isinstance(index, torch.Tensor) or index.dtype != torch.int64 or index.dim() != 1 or not index.is_contiguous():
+                raise TypeError("index must be a contiguous one-dimensional int64 tensor (as packet_index() returns)")
+            if index.device.type != "cuda" or index.device.index != self.device:
+                raise ValueError(f"index must live on this context's device (cuda:{self.device}), not {index.device}")
+            ip, ne = index.data_ptr(), index.numel()
+        _check(lib.zz_decode_device(self._h, self._ptr(src), src_len, self._ptr(dst), cap, ctypes.byref(out), int(format),
+                                    packet_size, ip, ne, st))
+        return out.value
+
+    def last_decode_path(self):
+        """DECODE_INDEXED, DECODE_DISCOVERED or DECODE_SERIAL: the path the last decode finished on (0: none)."""
+        return lib.zz_ctx_last_decode_path(self._h)
+
+    def last_decode_index(self, stream=None):
+        """The packet index the last decode recovered by discovery (an int64 tensor like packet_index()), or None when
+        the last decode took another path."""
+        import torch
+        if self.last_decode_path() != DECODE_DISCOVERED:
+            return None
+        entries = ctypes.c_uint64(0)
+        st = self._stream() if stream is None else stream
+        lib.zz_ctx_last_decode_index_device(self._h, None, 0, ctypes.byref(entries), st)
+        idx = torch.empty(entries.value, dtype=torch.int64, device=f"cuda:{self.device}")
+        _check(lib.zz_ctx_last_decode_index_device(self._h, idx.data_ptr(), entries.value, ctypes.byref(entries), st))
+        return idx
+
+    def last_decode_stats(self):
+        """(pending bytes, pointer-jumping rounds) of the last decode's parallel path."""
+        pend, rounds = ctypes.c_uint64(0), ctypes.c_uint32(0)
+        _check(lib.zz_ctx_last_decode_stats(self._h, ctypes.byref(pend), ctypes.byref(rounds)))
+        return pend.value, rounds.value
 
     def generate(self, kind, seed, first_byte, buf, n, stream=None):
         st = self._stream() if stream is None else stream

@@ -11,6 +11,7 @@
 #include <string>
 #include <thread>
 #include <vector>
+#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -28,6 +29,7 @@
 #include "zz_compact.h"
 #include "zz_datagen.h"
 #include "zz_verify.h"
+#include "zz_inflate.h"
 
 using namespace zz;
 
@@ -105,6 +107,7 @@ struct zz_ctx {
     hipEvent_t ev_in[2] = { nullptr, nullptr }, ev_out[2] = { nullptr, nullptr };
     // what the last packet-mode call did, for zz_verify_last_device
     zz_verify_params last = {};  bool have_last = false;
+    bool idx_empty = false; uint64_t idx_empty_bytes = 0;   // the last packet-mode call had an empty input (zz_packet_index_device)
     unsigned long long* d_verify = nullptr;
     uint32_t* d_work = nullptr;          // level 2: packet counter of the persistent workgroups
     uint64_t* d_log = nullptr; uint64_t log_cap_bytes = 0;   // sequential stream, callback form: EnsureOutputLength log
@@ -122,6 +125,19 @@ struct zz_ctx {
     bool timing = false;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     bool have_time = false;
+    // decode (zz_decode_device): one batch of phase-1 / phase-2 workspace, per-packet results of the call, discovery's candidates
+    struct {
+        uint32_t* st = nullptr; uint64_t st_cap = 0;          // pointers, 4 bytes per output byte of a batch
+        uint32_t* pend = nullptr; uint64_t pend_cap = 0;      // bitmap words
+        uint32_t* pcnt = nullptr; uint64_t pcnt_cap = 0; uint32_t* prem = nullptr; uint64_t prem_cap = 0;
+        uint64_t* ends = nullptr; uint64_t ends_cap = 0; uint32_t* stat = nullptr; uint64_t stat_cap = 0;
+        uint64_t* cand = nullptr; uint64_t cand_cap = 0;      // candidates, then a recovered index
+        zz_cks* cks = nullptr; uint64_t cks_cap = 0;
+        unsigned long long* tot = nullptr;                    // 64 counters (zz_inf_params::tot)
+        zz_inf_serial_out* sres = nullptr; uint32_t* ok = nullptr;
+        int last_path = 0; uint64_t last_pending = 0; uint32_t last_rounds = 0;
+        std::vector<uint64_t> last_index;                     // the index discovery recovered (zz_ctx_last_decode_index_device)
+    } dec;
 };
 
 // Small host values (an empty input's block, a result record whose size is known up front) reach the device as kernel
@@ -219,6 +235,9 @@ extern "C" void zz_ctx_destroy(zz_ctx* c)
     if (c->s_enc) (void)hipStreamDestroy(c->s_enc);
     if (c->s_out) (void)hipStreamDestroy(c->s_out);
     (void)hipHostFree(c->h_res); (void)hipHostFree(c->h_err);
+    (void)hipFree(c->dec.st); (void)hipFree(c->dec.pend); (void)hipFree(c->dec.pcnt); (void)hipFree(c->dec.prem);
+    (void)hipFree(c->dec.ends); (void)hipFree(c->dec.stat); (void)hipFree(c->dec.cand); (void)hipFree(c->dec.cks);
+    (void)hipFree(c->dec.tot); (void)hipFree(c->dec.sres); (void)hipFree(c->dec.ok);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
     delete c;
@@ -542,6 +561,7 @@ static int encode_common(zz_ctx* c, const uint8_t* d_src, uint64_t n, uint64_t h
     const uint32_t stride = slot_stride_for(level, P);
     c->have_time = false;
     c->have_last = false;            // whatever zz_verify_last_device could look at is about to change
+    c->idx_empty = false;
 
     HIPCHK(hipMemsetAsync(c->d_res, 0, sizeof(zz_result), st));
     HIPCHK(hipMemsetAsync(c->d_cks_total, 0, sizeof(zz_cks_total), st));
@@ -664,6 +684,7 @@ static int encode_finish(zz_ctx* c, zz_result* host_res)
     if (c->h_err[0]) { set_err("internal: packet slot overflow"); return ZZ_E_NOSPACE; }
     if (host_res->err) { set_err("destination too small for the compressed stream"); return ZZ_E_NOSPACE; }
     if (c->pend.npk) { c->last.stream_bytes = host_res->stream_bytes; c->have_last = true; }
+    else if (c->pend.whole || c->pend.last_is_final) { c->idx_empty = true; c->idx_empty_bytes = host_res->stream_bytes; }
     return ZZ_OK;
 }
 
@@ -716,6 +737,323 @@ extern "C" int zz_packet_extent_device(zz_ctx* c, uint64_t packet, uint64_t* off
 }
 
 static int cks_kind_for(int format) { return format == ZZ_ZLIB ? ZZ_CKS_ADLER : format == ZZ_GZIP ? ZZ_CKS_CRC : ZZ_CKS_NONE; }
+
+// ---- decode (zz_inflate.h) --------------------------------------------------------------------------------------------
+
+// The packet index of the last packet-mode call: where every packet starts behind the container header, and the stream's
+// end. An empty input's one empty block counts as a packet of 0 bytes.
+extern "C" int zz_packet_index_device(zz_ctx* c, uint64_t* d_index, uint64_t max_entries, uint64_t* entries, void* hip_stream)
+{
+    if (!c || !entries) { set_err("null argument"); return ZZ_E_ARG; }
+    if (!c->have_last && !c->idx_empty) { set_err("no packet-mode call on this context"); return ZZ_E_ARG; }
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t st = (hipStream_t)hip_stream;
+    const uint64_t npk = c->have_last ? c->last.npk : 1;
+    *entries = npk + 1;
+    if (max_entries < npk + 1 || !d_index) { set_err("index buffer too small"); return ZZ_E_NOSPACE; }
+    if (!c->have_last) {
+        const uint64_t h[2] = { 0, c->idx_empty_bytes };
+        HIPCHK(hipMemcpyAsync(d_index, h, sizeof h, hipMemcpyHostToDevice, st));
+        HIPCHK(hipStreamSynchronize(st));
+        return ZZ_OK;
+    }
+    const zz_verify_params& v = c->last;
+    if (!v.offsets) {                                         // level 0: every packet has its known place
+        std::vector<uint64_t> h(npk + 1);
+        for (uint64_t k = 0; k < npk; ++k) h[k] = k * v.l0_stride;
+        h[npk] = v.stream_bytes;
+        HIPCHK(hipMemcpyAsync(d_index, h.data(), h.size() * 8, hipMemcpyHostToDevice, st));
+    } else {
+        HIPCHK(hipMemcpyAsync(d_index, v.offsets, npk * 8, hipMemcpyDeviceToDevice, st));
+        HIPCHK(hipMemcpyAsync(d_index + npk, &v.stream_bytes, 8, hipMemcpyHostToDevice, st));
+    }
+    HIPCHK(hipStreamSynchronize(st));
+    return ZZ_OK;
+}
+
+extern "C" int zz_ctx_last_decode_path(const zz_ctx* c) { return c ? c->dec.last_path : 0; }
+extern "C" int zz_ctx_last_decode_stats(const zz_ctx* c, uint64_t* pending_bytes, uint32_t* rounds)
+{
+    if (!c) { set_err("null context"); return ZZ_E_ARG; }
+    if (pending_bytes) *pending_bytes = c->dec.last_pending;
+    if (rounds) *rounds = c->dec.last_rounds;
+    return ZZ_OK;
+}
+
+template <class T> static int dec_grow(T** p, uint64_t* cap, uint64_t count)
+{
+    if (count <= *cap) return ZZ_OK;
+    (void)hipFree(*p); *p = nullptr; *cap = 0;
+    HIPCHK(hipMalloc((void**)p, count * sizeof(T)));
+    *cap = count;
+    return ZZ_OK;
+}
+// the parallel paths' workspace: when it cannot be had, the call goes to the serial path, which needs none
+template <class T> static bool dec_try_grow(T** p, uint64_t* cap, uint64_t count)
+{
+    if (dec_grow(p, cap, count) == ZZ_OK) return true;
+    (void)hipGetLastError();
+    return false;
+}
+static uint32_t dec_ceil_log2(uint64_t x) { uint32_t r = 0; while ((1ull << r) < x) ++r; return r; }
+
+// what the parallel paths return (negative: a HIP error)
+enum { DEC_SERIAL = 0,      // not taken: the index, the packet size or discovery does not fit this stream
+       DEC_DONE = 1,        // decoded; *out = bytes
+       DEC_NOSPACE = 2 };   // decoded -- so this is the stream's true output -- but it does not fit the destination
+
+// phase 1 and phase 2 over packets [0, npk) starting at starts[0, nstarts) (device). Indexed: per-packet results per batch,
+// the last packet's kept in *last_stat; discovery: per candidate in dec.ends / dec.stat. Counters in dec.tot.
+static int dec_packets(zz_ctx* c, const uint8_t* s, uint64_t sn, const uint64_t* starts, uint64_t nstarts, uint64_t npk, int mode,
+                       uint32_t P, uint8_t* dst, uint64_t cap, hipStream_t st, uint32_t* rounds_launched, uint32_t* last_stat)
+{
+    auto& D = c->dec;
+    const uint32_t words = ((P + 31) / 32 + 3) & ~3u;
+    uint64_t B = ZZ_INF_BATCH_BYTES / P;
+    if (B > ZZ_INF_BATCH_PACKETS) B = ZZ_INF_BATCH_PACKETS;
+    if (B > npk) B = npk;
+    if (B == 0) B = 1;
+    const uint64_t per = mode == ZZ_INF_INDEXED ? B : npk;      // results kept per batch, or per candidate (bounded)
+    if (!dec_try_grow(&D.st, &D.st_cap, B * P) || !dec_try_grow(&D.pend, &D.pend_cap, B * words) ||
+        !dec_try_grow(&D.pcnt, &D.pcnt_cap, B) || !dec_try_grow(&D.prem, &D.prem_cap, B) ||
+        !dec_try_grow(&D.ends, &D.ends_cap, per) || !dec_try_grow(&D.stat, &D.stat_cap, per))
+        return DEC_SERIAL;
+    HIPCHK(hipMemsetAsync(D.tot, 0, 64 * sizeof(unsigned long long), st));
+    const uint32_t rounds = dec_ceil_log2(B) + 2;               // a chain has at most one link per packet of a batch
+    *rounds_launched = rounds;
+    const size_t lds = (size_t)words * 4 + ZZ_INF_IBUF + ((P + 15) & ~15u);
+    uint64_t last_base = 0;
+    for (uint64_t k0 = 0; k0 < npk; k0 += B) {
+        const uint32_t nb = (uint32_t)(npk - k0 < B ? npk - k0 : B);
+        zz_inf_params Q;
+        Q.s = s; Q.sn = sn; Q.starts = starts; Q.nstarts = nstarts; Q.k0 = k0; Q.npk = nb; Q.npk_total = npk;
+        Q.P = P; Q.mode = mode; Q.dst = dst; Q.cap = cap;
+        Q.st = D.st; Q.pend = D.pend; Q.words = words; Q.pcnt = D.pcnt; Q.prem = D.prem; Q.ends = D.ends; Q.stat = D.stat; Q.tot = D.tot;
+        Q.ebase = mode == ZZ_INF_INDEXED ? k0 : 0;
+        last_base = Q.ebase;
+        hipLaunchKernelGGL(k_inflate_packets, dim3(nb), dim3(ZZ_INF_THREADS), lds, st, Q);
+        zz_res_params R{ dst, k0 * P, P, nb, words, D.st, D.pend, D.pcnt, D.prem, D.tot };
+        for (uint32_t r = 1; r <= rounds; ++r) hipLaunchKernelGGL(k_inflate_resolve, dim3(nb), dim3(ZZ_INF_RES_THREADS), 0, st, R, r);
+    }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(last_stat, D.stat + (npk - 1 - last_base), 4, hipMemcpyDeviceToHost, st));
+    return DEC_DONE;
+}
+
+// what dec_packets left for the packets [0, npk) it ran on (their chain already checked by the kernel or the host walk)
+static int dec_collect(zz_ctx* c, uint64_t npk, uint32_t P, uint32_t rounds, uint32_t last, hipStream_t st, uint64_t* out)
+{
+    auto& D = c->dec;
+    unsigned long long tot[64];
+    HIPCHK(hipMemcpyAsync(tot, D.tot, sizeof tot, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (tot[63] != 0 || !(last & 1u) || !(last & 2u)) return DEC_SERIAL;
+    *out = (npk - 1) * (uint64_t)P + (last >> 3);
+    if (tot[62] != 0) return DEC_NOSPACE;
+    if (tot[1 + rounds] != 0) return DEC_SERIAL;            // (cannot happen: the rounds suffice for any chain)
+    D.last_pending = tot[0];
+    D.last_rounds = 0;
+    if (tot[0]) { uint32_t r = 1; while (r < rounds && tot[1 + r] != 0) ++r; D.last_rounds = r; }
+    return DEC_DONE;
+}
+
+static int dec_indexed(zz_ctx* c, const uint8_t* s, uint64_t sn, const uint64_t* d_index, uint64_t entries, uint32_t P,
+                       uint8_t* dst, uint64_t cap, hipStream_t st, uint64_t* out)
+{
+    if (entries < 2) return DEC_SERIAL;
+    const uint64_t npk = entries - 1;
+    if (npk > (1ull << 40)) return DEC_SERIAL;
+    uint64_t ends[2];
+    HIPCHK(hipMemcpyAsync(&ends[0], d_index, 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(&ends[1], d_index + npk, 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (ends[0] != 0 || ends[1] != sn) return DEC_SERIAL;
+    uint32_t rounds = 0, last = 0;
+    int rc = dec_packets(c, s, sn, d_index, entries, npk, ZZ_INF_INDEXED, P, dst, cap, st, &rounds, &last);
+    if (rc != DEC_DONE) return rc;
+    return dec_collect(c, npk, P, rounds, last, st, out);
+}
+
+// discovery: candidates from the scan, phase 1 from every one of them (at its place if all are true starts), the chain
+// of true starts walked on the host; if some candidates are not starts, phase 1 again on the index the walk recovered
+static int dec_discover(zz_ctx* c, const uint8_t* s, uint64_t sn, uint32_t P, uint8_t* dst, uint64_t cap, hipStream_t st,
+                        uint64_t* out)
+{
+    auto& D = c->dec;
+    // a packet of P bytes takes at least P / 1032 + 6 bytes of stream (the longest match per two bits, the closing stored
+    // block): twice the packets that can fit bounds the speculative work on adversarial input
+    uint64_t cap_c = 2 * (sn / ((uint64_t)P / 1032 + 6)) + 64;
+    if (cap_c > ZZ_INF_MAX_CANDIDATES) cap_c = ZZ_INF_MAX_CANDIDATES;
+    if (!dec_try_grow(&D.cand, &D.cand_cap, cap_c + 1)) return DEC_SERIAL;
+    HIPCHK(hipMemsetAsync(D.tot, 0, 64 * sizeof(unsigned long long), st));
+    {
+        uint64_t g = (sn + 255) / 256;
+        if (g > 8192) g = 8192;
+        if (g == 0) g = 1;
+        hipLaunchKernelGGL(k_inflate_scan, dim3((uint32_t)g), dim3(256), 0, st, s, sn, D.cand + 1, D.tot, cap_c);
+    }
+    HIPCHK(hipGetLastError());
+    unsigned long long count = 0;
+    HIPCHK(hipMemcpyAsync(&count, D.tot, 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (count > cap_c) return DEC_SERIAL;
+    std::vector<uint64_t> cand(count + 1);
+    cand[0] = 0;                                             // the position behind the container header
+    if (count) HIPCHK(hipMemcpyAsync(cand.data() + 1, D.cand + 1, count * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    std::sort(cand.begin(), cand.end());
+    cand.erase(std::unique(cand.begin(), cand.end()), cand.end());
+    const uint64_t nc = cand.size();
+    HIPCHK(hipMemcpyAsync(D.cand, cand.data(), nc * 8, hipMemcpyHostToDevice, st));
+    uint32_t rounds = 0, last = 0;
+    int rc = dec_packets(c, s, sn, D.cand, nc, nc, ZZ_INF_DISCOVER, P, dst, cap, st, &rounds, &last);
+    if (rc != DEC_DONE) return rc;
+    std::vector<uint64_t> ends(nc);
+    std::vector<uint32_t> stat(nc);
+    HIPCHK(hipMemcpyAsync(ends.data(), D.ends, nc * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(stat.data(), D.stat, nc * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    // walk from the first start: a true start ends exactly where the next true start begins. A candidate decoded at the
+    // wrong place (behind false ones) may not have fit the destination; its end is known all the same.
+    std::vector<uint64_t>& index = D.last_index;
+    index.assign(1, 0);
+    uint64_t i = 0;
+    for (;;) {
+        if (!(stat[i] & 1u)) return DEC_SERIAL;
+        if (stat[i] & 2u) { if (ends[i] != sn) return DEC_SERIAL; break; }
+        const auto it = std::lower_bound(cand.begin() + i + 1, cand.end(), ends[i]);
+        if (it == cand.end() || *it != ends[i]) return DEC_SERIAL;
+        i = (uint64_t)(it - cand.begin());
+        index.push_back(cand[i]);
+    }
+    const uint64_t npk = index.size();
+    index.push_back(sn);
+    if (npk == nc) return dec_collect(c, npk, P, rounds, last, st, out);   // every candidate was a true start, decoded in place
+    HIPCHK(hipMemcpyAsync(D.cand, index.data(), index.size() * 8, hipMemcpyHostToDevice, st));
+    return dec_indexed(c, s, sn, D.cand, index.size(), P, dst, cap, st, out);
+}
+
+// The packet index the last zz_decode_device recovered by discovery (entries = packets + 1, as zz_packet_index_device)
+extern "C" int zz_ctx_last_decode_index_device(zz_ctx* c, uint64_t* d_index, uint64_t max_entries, uint64_t* entries,
+                                               void* hip_stream)
+{
+    if (!c || !entries) { set_err("null argument"); return ZZ_E_ARG; }
+    if (c->dec.last_path != ZZ_DECODE_DISCOVERED) { set_err("the last decode on this context did not discover an index"); return ZZ_E_ARG; }
+    const auto& v = c->dec.last_index;
+    *entries = v.size();
+    if (!d_index || max_entries < v.size()) { set_err("index buffer too small"); return ZZ_E_NOSPACE; }
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t st = (hipStream_t)hip_stream;
+    HIPCHK(hipMemcpyAsync(d_index, v.data(), v.size() * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return ZZ_OK;
+}
+
+// the decoded bytes against the trailer, on the device (zz_checksum.h's per-packet partials and their fold)
+static int dec_check_trailer(zz_ctx* c, const uint8_t* trailer, int format, const uint8_t* dst, uint64_t n, hipStream_t st, bool* good)
+{
+    auto& D = c->dec;
+    *good = true;
+    if (format == ZZ_DEFLATE) return ZZ_OK;
+    const int kind = cks_kind_for(format);
+    const uint32_t CP = 32768;
+    const uint64_t npk = (n + CP - 1) / CP;
+    HIPCHK(hipMemsetAsync(c->d_cks_total, 0, sizeof(zz_cks_total), st));
+    if (npk) {
+        int rc = dec_grow(&D.cks, &D.cks_cap, npk);
+        if (rc) return rc;
+        zz_packet_params pp = {};
+        pp.src = dst; pp.n = n; pp.packet_size = CP; pp.npk = (uint32_t)npk; pp.cks_kind = kind; pp.cks = D.cks;
+        if (kind == ZZ_CKS_ADLER) hipLaunchKernelGGL(k_adler_packets, dim3(npk < 16384 ? (uint32_t)npk : 16384), dim3(ZZ_WAVE), 0, st, pp);
+        else hipLaunchKernelGGL(k_crc32_packets, dim3(npk < 2048 ? (uint32_t)npk : 2048), dim3(ZZ_CRC_THREADS), 0, st, pp);
+        hipLaunchKernelGGL(k_cks_reduce, dim3(1), dim3(ZZ_RED_THREADS), 0, st, D.cks, (uint32_t)npk, CP, n, kind, c->d_cks_total);
+    }
+    hipLaunchKernelGGL(k_inflate_trailer, dim3(1), dim3(1), 0, st, trailer, format, c->d_cks_total, n, D.ok);
+    HIPCHK(hipGetLastError());
+    uint32_t ok = 0;
+    HIPCHK(hipMemcpyAsync(&ok, D.ok, 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    *good = ok == 1;
+    return ZZ_OK;
+}
+
+extern "C" int zz_decode_device(zz_ctx* c, const void* d_src_v, uint64_t src_len, void* d_dst_v, uint64_t cap, uint64_t* out_len,
+                                int format, uint32_t P, const uint64_t* d_index, uint64_t entries, void* hip_stream)
+{
+    if (!c || !out_len) { set_err("null argument"); return ZZ_E_ARG; }
+    *out_len = 0;
+    if (format < ZZ_ZLIB || format > ZZ_DEFLATE) { set_err("format must be ZZ_ZLIB, ZZ_GZIP or ZZ_DEFLATE"); return ZZ_E_ARG; }
+    if (P > ZZ_MAX_PACKET_SIZE) { set_err("packet size must be 0..32768"); return ZZ_E_ARG; }
+    if ((!d_src_v && src_len) || (!d_dst_v && cap)) { set_err("null buffer"); return ZZ_E_ARG; }
+    if (c->pend.active) { set_err("a call enqueued with zz_encode_device_async has not been finished on this context"); return ZZ_E_ARG; }
+    const uint8_t* d_src = (const uint8_t*)d_src_v;
+    uint8_t* d_dst = (uint8_t*)d_dst_v;
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t st = (hipStream_t)hip_stream;
+    auto& D = c->dec;
+    D.last_path = 0; D.last_pending = 0; D.last_rounds = 0; D.last_index.clear();
+    if (!D.tot) {
+        HIPCHK(hipMalloc(&D.tot, 64 * sizeof(unsigned long long)));
+        HIPCHK(hipMalloc(&D.sres, sizeof(zz_inf_serial_out)));
+        HIPCHK(hipMalloc(&D.ok, 4));
+    }
+    // the container header, read on the host (it may hold a file name of any length)
+    int64_t hl = 0;
+    if (format != ZZ_DEFLATE) {
+        uint64_t have = src_len < 4096 ? src_len : 4096;
+        std::vector<uint8_t> h;
+        for (;;) {
+            h.resize(have);
+            if (have) HIPCHK(hipMemcpyAsync(h.data(), d_src, have, hipMemcpyDeviceToHost, st));
+            HIPCHK(hipStreamSynchronize(st));
+            hl = zi_header(format, h.data(), have);
+            if (hl != -1 || have == src_len) break;
+            have = src_len - have < 3 * have ? src_len : 4 * have;
+        }
+        if (hl == -2) { set_err("the stream needs a preset dictionary (FDICT): not supported"); return ZZ_E_UNSUPPORTED; }
+        if (hl < 0) { set_err("not a valid stream of the requested format: bad container header"); return ZZ_E_DATA; }
+    }
+    const uint64_t tl = (uint64_t)trailer_len(format);
+    if (src_len < (uint64_t)hl + tl) { set_err("not a valid stream of the requested format: truncated"); return ZZ_E_DATA; }
+    const uint8_t* s = d_src + hl;
+    const uint64_t sn = src_len - hl - tl;
+    uint64_t out = 0;
+    int got = DEC_SERIAL;
+    if (P != 0 && sn > 0) {
+        got = d_index ? dec_indexed(c, s, sn, d_index, entries, P, d_dst, cap, st, &out) : dec_discover(c, s, sn, P, d_dst, cap, st, &out);
+        if (got < 0) return got;
+        if (got == DEC_NOSPACE) {
+            set_err("destination too small for the decoded stream (" + std::to_string(out) + " bytes)");
+            return ZZ_E_NOSPACE;
+        }
+        if (got == DEC_DONE) D.last_path = d_index ? ZZ_DECODE_INDEXED : ZZ_DECODE_DISCOVERED;
+    }
+    if (got != DEC_DONE) {
+        D.last_pending = 0; D.last_rounds = 0;
+        hipLaunchKernelGGL(k_inflate_serial, dim3(1), dim3(ZZ_INF_THREADS), 0, st, s, src_len - hl, d_dst, cap, D.sres);
+        HIPCHK(hipGetLastError());
+        zz_inf_serial_out r;
+        HIPCHK(hipMemcpyAsync(&r, D.sres, sizeof r, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        if (r.err == ZI_E_SPACE) { set_err("destination too small for the decoded stream"); return ZZ_E_NOSPACE; }
+        if (r.err == ZI_E_FAR) { set_err("not a valid stream of the requested format: distance too far back"); return ZZ_E_DATA; }
+        if (r.err) { set_err("not a valid stream of the requested format: invalid block structure"); return ZZ_E_DATA; }
+        const uint64_t rest = src_len - hl >= r.end ? src_len - hl - r.end : 0;
+        if (rest != tl) {
+            set_err(rest < tl ? "not a valid stream of the requested format: truncated trailer"
+                                                : "not a valid stream of the requested format: bytes behind the trailer");
+            return ZZ_E_DATA;
+        }
+        out = r.out;
+        D.last_path = ZZ_DECODE_SERIAL;
+    }
+    bool good = true;
+    int rc = dec_check_trailer(c, d_src + src_len - tl, format, d_dst, out, st, &good);
+    if (rc) return rc;
+    if (!good) { set_err("not a valid stream of the requested format: checksum or ISIZE mismatch"); return ZZ_E_DATA; }
+    *out_len = out;
+    return ZZ_OK;
+}
 
 // The reference's sequential whole-buffer stream (threaded=false, zzflate.cpp:84-95) on the device. Level 0 is
 // parallel (stored blocks of 65535 bytes have known places); level 1 is a chain of fixed-Huffman blocks whose lengths

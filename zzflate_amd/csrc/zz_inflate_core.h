@@ -1,0 +1,433 @@
+// zz_inflate_core.h -- the RFC 1951 inflate core shared by the device decoder (zz_inflate.h) and its CPU harness
+// (tests/cxx/inflate_harness.cpp): bit reader, block headers, code-length parsing, canonical table construction,
+// symbol decode and every bounds check live here, once.
+//
+// The core is written for a group of `nl` lanes that run the same control flow (one wavefront on the device, one
+// thread on the host): every lane decodes every symbol (the bit reader, the tables and the block state are uniform),
+// and only the writes are divided -- table fills, stored bytes and match copies are lane-strided. Compiles with g++
+// without HIP (ZZ_HD is empty there); with -DZZ_INFLATE_CHECKED every buffer access goes through ZI_CHECK, which aborts
+// on an index out of range, so that a CPU build proves the bounds the device relies on.
+//
+// Tables: a 10-bit first level plus second-level tables for longer codes, 16-bit entries:
+//   bit 15 = 0 : bits 0..8 symbol (0x1FF: no code), bits 9..12 bits to consume (0: no code)
+//   bit 15 = 1 : link; bits 0..10 = index of the second-level table, bits 11..14 = its index bits
+// zlib's `enough` bounds a 286-symbol, root-10, 15-bit code at 1332 entries and a 30-symbol one well below that;
+// ZI_TAB leaves room, and the builder still refuses (as invalid) a code that would not fit.
+#pragma once
+#include <stdint.h>
+
+#if defined(__HIPCC__) || defined(__HIP__)
+#define ZZ_HD __host__ __device__
+#else
+#define ZZ_HD
+#endif
+
+#ifdef ZZ_INFLATE_CHECKED
+#include <cstdio>
+#include <cstdlib>
+#define ZI_CHECK(c) do { if (!(c)) { fprintf(stderr, "zz_inflate_core: access out of range at line %d\n", __LINE__); abort(); } } while (0)
+#else
+#define ZI_CHECK(c) ((void)0)
+#endif
+
+namespace zz {
+
+// results of the core (the C ABI maps them: DATA / FAR -> ZZ_E_DATA, SPACE -> ZZ_E_NOSPACE)
+enum { ZI_OK = 0, ZI_E_DATA = 1, ZI_E_SPACE = 2, ZI_E_FAR = 3, ZI_E_SHAPE = 4 };
+
+#define ZI_ROOT 10
+#define ZI_TAB 1536
+#define ZI_NOCODE 0x01FFu
+
+// a bounds-checked window onto a buffer (checked only in ZZ_INFLATE_CHECKED builds)
+template <class T> struct zi_view {
+    T* p; uint64_t n;
+    ZZ_HD T& operator[](uint64_t i) const { ZI_CHECK(i < n); return p[i]; }
+};
+
+// table memory of one decoder (LDS on the device): 2 * 3 KiB + scratch
+struct zi_tables {
+    uint16_t lit[ZI_TAB];
+    uint16_t dst[ZI_TAB];
+    uint16_t sorted[320];       // symbols in canonical order
+    uint8_t lens[320];          // code lengths of the block being read (litlen followed by distance)
+    uint16_t cnt[16], offs[16];
+    int kind;                   // what `lit`/`dst` hold now: 0 nothing, 1 the fixed code, 2 a dynamic code
+};
+
+ZZ_HD inline uint32_t zi_rev(uint32_t v, int n)
+{
+    uint32_t r = 0;
+    for (int i = 0; i < n; ++i) { r = (r << 1) | (v & 1); v >>= 1; }
+    return r;
+}
+
+// Canonical code (RFC 1951 3.2.2) from lens[0, n) into tab. Validity as zlib: over-subscribed codes are refused;
+// incomplete codes only in the form of a single one-bit code (literal/length and distance codes; the unused half of
+// the table stays "no code") -- `allow_empty` additionally accepts no code at all (a block without distances). Lanes split the fills; the serial parts are done by every lane alike.
+ZZ_HD inline bool zi_build(zi_view<uint16_t> tab, zi_tables& S, int n, bool allow_empty, bool allow_incomplete,
+                           uint32_t lane, uint32_t nl)
+{
+    zi_view<uint8_t> lens{ S.lens, 320 };
+    zi_view<uint16_t> cnt{ S.cnt, 16 }, offs{ S.offs, 16 }, sorted{ S.sorted, 320 };
+    for (int l = 0; l < 16; ++l) cnt[l] = 0;
+    for (int i = 0; i < n; ++i) cnt[lens[i]] = (uint16_t)(cnt[lens[i]] + 1);
+    int maxl = 0;
+    for (int l = 1; l < 16; ++l) if (cnt[l]) maxl = l;
+    for (uint32_t i = lane; i < ZI_TAB; i += nl) tab[i] = (uint16_t)ZI_NOCODE;
+    if (maxl == 0) return allow_empty;
+    int left = 1;
+    for (int l = 1; l < 16; ++l) { left = (left << 1) - cnt[l]; if (left < 0) return false; }
+    if (left > 0 && !(allow_incomplete && maxl == 1)) return false;
+    offs[1] = 0;
+    for (int l = 1; l < 15; ++l) offs[l + 1] = (uint16_t)(offs[l] + cnt[l]);
+    for (int i = 0; i < n; ++i) if (lens[i]) { sorted[offs[lens[i]]] = (uint16_t)i; offs[lens[i]] = (uint16_t)(offs[lens[i]] + 1); }
+    // walk the codes in canonical order; codes longer than the root share second-level tables per root prefix. The
+    // codes under one prefix are consecutive and the last of them is the longest, so one pass sizes and places them.
+    uint32_t code = 0, next_sub = 1u << ZI_ROOT;
+    int idx = 0;
+    int cur_prefix = -1; uint32_t cur_off = 0, cur_bits = 0;
+    for (int l = 1; l <= maxl; ++l) {
+        for (int c = 0; c < cnt[l]; ++c, ++idx, ++code) {
+            const uint32_t sym = sorted[(uint64_t)idx];
+            const uint32_t r = zi_rev(code, l);
+            if (l <= ZI_ROOT) {
+                const uint16_t e = (uint16_t)((l << 9) | sym);
+                for (uint32_t i = r + ((uint32_t)lane << l); i < (1u << ZI_ROOT); i += nl << l) tab[i] = e;
+                continue;
+            }
+            const int prefix = (int)(r & ((1u << ZI_ROOT) - 1));
+            if (prefix != cur_prefix) {
+                // the longest code under this prefix: the last one that shares it (canonical order)
+                uint32_t c2 = code; int l2 = l, j = idx, cc = c;
+                uint32_t maxbits = (uint32_t)(l - ZI_ROOT);
+                while (true) {
+                    // advance one code in canonical order
+                    ++j; ++cc; ++c2;
+                    while (l2 <= maxl && cc >= cnt[l2]) { cc = 0; ++l2; c2 <<= 1; }
+                    if (l2 > maxl) break;
+                    if ((int)(zi_rev(c2, l2) & ((1u << ZI_ROOT) - 1)) != prefix) break;
+                    maxbits = (uint32_t)(l2 - ZI_ROOT);
+                }
+                if (next_sub + (1u << maxbits) > ZI_TAB) return false;
+                cur_prefix = prefix; cur_off = next_sub; cur_bits = maxbits;
+                next_sub += 1u << maxbits;
+                if (lane == 0) tab[(uint64_t)prefix] = (uint16_t)(0x8000u | (cur_bits << 11) | cur_off);
+            }
+            const uint32_t sl = (uint32_t)(l - ZI_ROOT);
+            const uint16_t e = (uint16_t)((sl << 9) | sym);
+            for (uint32_t i = (r >> ZI_ROOT) + ((uint32_t)lane << sl); i < (1u << cur_bits); i += nl << sl) tab[cur_off + i] = e;
+        }
+        code <<= 1;
+    }
+    return true;
+}
+
+// ---- input: the bit reader over a byte source ------------------------------------------------------------------
+// In is a policy with `uint64_t peek8(uint64_t pos)`: the 8 bytes from pos on, little-endian, zero at or past `end`.
+// A refill takes as many whole bytes as fit the 64-bit buffer from one such read (the bits above `bn` are those same
+// bytes again, so OR-ing the next read over them changes nothing); consumed() > end * 8 means the decoder has used bits
+// that are not there.
+template <class In> struct zi_bits {
+    In& in;
+    uint64_t pos;        // next byte to load
+    uint64_t end;        // bytes of the view
+    uint64_t bb; uint32_t bn;
+    ZZ_HD zi_bits(In& i, uint64_t start, uint64_t e) : in(i), pos(start), end(e), bb(0), bn(0) {}
+    ZZ_HD void refill()
+    {
+        if (bn > 56) return;
+        bb |= in.peek8(pos) << bn;
+        const uint32_t k = (63 - bn) >> 3;
+        pos += k; bn += 8 * k;
+    }
+    ZZ_HD uint64_t consumed() const { return pos * 8 - bn; }
+    ZZ_HD bool overrun() const { return pos > end && consumed() > end * 8; }
+    ZZ_HD uint32_t get(uint32_t n) { if (bn < n) refill(); const uint32_t v = (uint32_t)(bb & ((1ull << n) - 1)); bb >>= n; bn -= n; return v; }
+    ZZ_HD void align() { const uint32_t k = bn & 7; bb >>= k; bn -= k; }
+    // restart at byte `p` (behind a stored block)
+    ZZ_HD void seek(uint64_t p) { pos = p; bb = 0; bn = 0; }
+};
+
+// one symbol from a table; -1 when the bits do not form a code
+ZZ_HD inline int zi_decode(const zi_view<uint16_t>& tab, uint64_t& bb, uint32_t& bn)
+{
+    uint32_t e = tab[bb & ((1u << ZI_ROOT) - 1)];
+    if (e & 0x8000u) {
+        const uint32_t sb = (e >> 11) & 15u;
+        bb >>= ZI_ROOT; bn -= ZI_ROOT;
+        e = tab[(e & 0x7FFu) + (uint32_t)(bb & ((1u << sb) - 1))];
+    }
+    const uint32_t l = (e >> 9) & 15u;
+    if (l == 0 || l > bn) return -1;
+    bb >>= l; bn -= l;
+    return (int)(e & 0x1FFu);
+}
+
+// ---- what ends a run of blocks ---------------------------------------------------------------------------------
+enum { ZI_RUN_STREAM = 0,     // until the final block (serial path)
+       ZI_RUN_INDEXED = 1,    // a packet with a known end: non-final blocks until bit `end * 8`, or the final block
+       ZI_RUN_DISCOVER = 2 }; // a packet from a candidate start: until `want` bytes at a byte-aligned block end, or the final block
+struct zi_result {
+    int err;
+    int final;               // the run ended with the final block
+    uint64_t end;            // byte (relative to the view) behind the run; the final block's last byte included
+    uint64_t out;            // bytes produced
+};
+
+// Out is a policy: lit(v), copy(dist, len), stored(in view, pos, len) return ZI_*; `pos` = bytes produced so far.
+// `view` is the input [0, n) of the run (the packet or the whole stream) in global memory; `in` the byte source over it.
+template <class In, class Out>
+ZZ_HD zi_result zi_run(In& in, zi_view<const uint8_t> view, uint64_t start, Out& o, zi_tables& S, int mode, uint64_t want,
+                       uint32_t lane, uint32_t nl)
+{
+    zi_result R{ ZI_OK, 0, 0, 0 };
+    zi_bits<In> b(in, start, view.n);
+    zi_view<uint16_t> lit{ S.lit, ZI_TAB }, dst{ S.dst, ZI_TAB };
+    zi_view<uint8_t> lens{ S.lens, 320 };
+    bool any_block = false;
+    for (;;) {
+        if (any_block) {
+            if (mode == ZI_RUN_INDEXED && b.consumed() == view.n * 8) break;
+            if (mode == ZI_RUN_DISCOVER && o.pos == want && (b.consumed() & 7) == 0) break;
+        }
+        if (b.consumed() >= view.n * 8) { R.err = ZI_E_DATA; break; }          // the run needs another block that is not there
+        b.refill();
+        const uint32_t bfinal = b.get(1), type = b.get(2);
+        any_block = true;
+        if (type == 3) { R.err = ZI_E_DATA; break; }
+        if (type == 0) {
+            b.align();
+            b.refill();
+            const uint32_t ln = b.get(16), nln = b.get(16);
+            if ((ln ^ nln) != 0xFFFFu || b.overrun()) { R.err = ZI_E_DATA; break; }
+            const uint64_t at = b.consumed() >> 3;
+            if (at + ln > view.n) { R.err = ZI_E_DATA; break; }
+            R.err = o.stored(view, at, ln);
+            if (R.err) break;
+            b.seek(at + ln);
+        } else {
+            if (type == 1) {
+                if (S.kind != 1) {
+                    for (int i = 0; i < 288; ++i) lens[i] = (uint8_t)(i < 144 ? 8 : i < 256 ? 9 : i < 280 ? 7 : 8);
+                    zi_build(lit, S, 288, false, false, lane, nl);
+                    for (int i = 0; i < 32; ++i) lens[i] = 5;
+                    zi_build(dst, S, 32, false, false, lane, nl);
+                    S.kind = 1;
+                }
+            } else {
+                S.kind = 0;
+                b.refill();
+                const uint32_t hlit = b.get(5) + 257, hdist = b.get(5) + 1, hclen = b.get(4) + 4;
+                if (hlit > 286 || hdist > 30) { R.err = ZI_E_DATA; break; }
+                const uint8_t order[19] = { 16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15 };
+                for (int i = 0; i < 19; ++i) lens[i] = 0;
+                b.refill();
+                for (uint32_t i = 0; i < hclen; ++i) { if (b.bn < 3) b.refill(); lens[order[i]] = (uint8_t)b.get(3); }
+                if (!zi_build(lit, S, 19, false, false, lane, nl)) { R.err = ZI_E_DATA; break; }   // `lit` holds the code-length code
+                // the code lengths go to lens[] (the code-length code is in `lit` already)
+                uint32_t idx = 0;
+                bool bad = false;
+                while (idx < hlit + hdist) {
+                    b.refill();
+                    const int sym = zi_decode(lit, b.bb, b.bn);
+                    if (sym < 0 || sym > 18) { bad = true; break; }
+                    if (sym < 16) { lens[idx++] = (uint8_t)sym; continue; }
+                    uint32_t rep, val = 0;
+                    if (sym == 16) { if (idx == 0) { bad = true; break; } val = lens[idx - 1]; rep = 3 + b.get(2); }
+                    else if (sym == 17) rep = 3 + b.get(3);
+                    else rep = 11 + b.get(7);
+                    if (idx + rep > hlit + hdist) { bad = true; break; }
+                    while (rep--) lens[idx++] = (uint8_t)val;
+                }
+                if (bad || b.overrun()) { R.err = ZI_E_DATA; break; }
+                if (lens[256] == 0) { R.err = ZI_E_DATA; break; }                        // no end-of-block code
+                if (!zi_build(lit, S, (int)hlit, false, true, lane, nl)) { R.err = ZI_E_DATA; break; }
+                for (uint32_t i = 0; i < hdist; ++i) lens[i] = lens[hlit + i];
+                if (!zi_build(dst, S, (int)hdist, true, true, lane, nl)) { R.err = ZI_E_DATA; break; }
+                S.kind = 2;
+            }
+            // the symbols of the block; one refill covers a whole length / distance pair (<= 48 bits)
+            for (;;) {
+                if (b.bn < 48) b.refill();
+                const int sym = zi_decode(lit, b.bb, b.bn);
+                if (sym < 256) {
+                    if (sym < 0) { R.err = ZI_E_DATA; break; }
+                    R.err = o.lit((uint32_t)sym);
+                    if (R.err) break;
+                    if (b.overrun()) { R.err = ZI_E_DATA; break; }
+                    continue;
+                }
+                if (sym == 256) break;
+                if (sym > 285) { R.err = ZI_E_DATA; break; }
+                uint32_t len;                                                            // RFC 1951 3.2.5
+                if (sym < 265) len = (uint32_t)sym - 254;
+                else if (sym == 285) len = 258;
+                else { const uint32_t eb = ((uint32_t)sym - 261) >> 2; len = 3 + ((4u | (((uint32_t)sym - 265) & 3)) << eb) + (uint32_t)(b.bb & ((1u << eb) - 1)); b.bb >>= eb; b.bn -= eb; }
+                const int ds = zi_decode(dst, b.bb, b.bn);
+                if (ds < 0 || ds > 29) { R.err = ZI_E_DATA; break; }
+                uint32_t dist;
+                if (ds < 4) dist = (uint32_t)ds + 1;
+                else { const uint32_t eb = ((uint32_t)ds >> 1) - 1; dist = 1 + ((2u | ((uint32_t)ds & 1)) << eb) + (uint32_t)(b.bb & ((1u << eb) - 1)); b.bb >>= eb; b.bn -= eb; }
+                if (b.overrun()) { R.err = ZI_E_DATA; break; }
+                R.err = o.copy(dist, len);
+                if (R.err) break;
+            }
+            if (R.err) break;
+            if (b.overrun()) { R.err = ZI_E_DATA; break; }
+        }
+        if (bfinal) { R.final = 1; break; }
+        if (mode == ZI_RUN_INDEXED && b.consumed() > view.n * 8) { R.err = ZI_E_DATA; break; }
+    }
+    R.end = (b.consumed() + 7) >> 3;
+    R.out = o.pos;
+    if (R.err) return R;
+    if (mode == ZI_RUN_STREAM) { if (!R.final) R.err = ZI_E_DATA; return R; }
+    // a packet: a non-final one is exactly `want` bytes and ends on a byte; the final one holds at most `want`
+    if (R.final) { if (o.pos > want) R.err = ZI_E_SHAPE; }
+    else if (o.pos != want || (b.consumed() & 7) != 0) R.err = ZI_E_SHAPE;
+    return R;
+}
+
+// ---- the whole output as the window (serial path; the CPU reference) -----------------------------------------------
+// out[0, cap): bytes land at their final place and matches read the bytes in front of them there.
+struct zi_fence_none { ZZ_HD void operator()() const {} };
+template <class Fence = zi_fence_none> struct zi_out_linear {
+    zi_view<uint8_t> out;
+    uint64_t pos;
+    uint32_t lane, nl;
+    Fence fence;
+    ZZ_HD int lit(uint32_t v)
+    {
+        if (pos >= out.n) return ZI_E_SPACE;
+        if (lane == 0) out[pos] = (uint8_t)v;
+        ++pos;
+        return ZI_OK;
+    }
+    ZZ_HD int copy(uint32_t dist, uint32_t len)
+    {
+        if (dist > pos) return ZI_E_FAR;
+        if (out.n - pos < len) return ZI_E_SPACE;
+        fence();                                            // the bytes other lanes wrote are visible
+        for (uint32_t i = lane; i < len; i += nl) out[pos + i] = out[pos - dist + (i < dist ? i : i % dist)];
+        pos += len;
+        return ZI_OK;
+    }
+    ZZ_HD int stored(const zi_view<const uint8_t>& in, uint64_t at, uint32_t len)
+    {
+        if (out.n - pos < len) return ZI_E_SPACE;
+        for (uint32_t i = lane; i < len; i += nl) out[pos + i] = in[at + i];
+        pos += len;
+        return ZI_OK;
+    }
+};
+
+// ---- one packet with its window (phase 1 of the parallel paths) -----------------------------------------------------
+// The packet's bytes go to win[0, cap) (LDS on the device). A byte whose match source lies in front of the packet's
+// start is PENDING: its bit in `pend` is set and st[pos] holds the absolute position (relative to `base`, plus
+// ZI_BIAS) of the byte it copies; a copy from a pending byte copies that pointer. Nothing waits for another packet.
+#define ZI_BIAS 32768u
+#define ZI_PTR_MASK ((1u << 27) - 1)
+struct zi_fence_or {};
+template <class Fence, class Or> struct zi_out_packet {
+    zi_view<uint8_t> win;          // cap = packet size
+    zi_view<uint32_t> pend;        // (cap + 31) / 32 words, zero on entry
+    zi_view<uint32_t> st;          // cap pointers (global on the device)
+    uint64_t abs;                  // absolute output position of the packet's first byte
+    int64_t rel;                   // the same, relative to the batch base the pointers count from
+    uint64_t pos;
+    uint32_t npend;                // pending bytes this lane wrote
+    bool any_pend;                 // uniform: the packet has pending bytes
+    uint32_t lane, nl;
+    Fence fence; Or bit_or;
+    ZZ_HD int lit(uint32_t v)
+    {
+        if (pos >= win.n) return ZI_E_SHAPE;
+        if (lane == 0) win[pos] = (uint8_t)v;
+        ++pos;
+        return ZI_OK;
+    }
+    ZZ_HD int copy(uint32_t dist, uint32_t len)
+    {
+        if (dist > abs + pos) return ZI_E_FAR;                    // in front of the stream
+        if (win.n - pos < len) return ZI_E_SHAPE;
+        const bool direct = dist > pos;                           // the copy starts in front of the packet
+        if (any_pend) fence();                                    // pointers other lanes stored are visible
+        if (direct || any_pend) {
+            for (uint32_t i = lane; i < len; i += nl) {
+                const int64_t s = (int64_t)pos - (int64_t)dist + (int64_t)(i < dist ? i : i % dist);
+                const uint64_t q = pos + i;
+                if (s < 0) {
+                    st[q] = (uint32_t)(rel + s + (int64_t)ZI_BIAS);
+                    bit_or(pend, q); ++npend;
+                } else if ((pend[(uint64_t)s >> 5] >> (s & 31)) & 1u) {
+                    st[q] = st[(uint64_t)s];
+                    bit_or(pend, q); ++npend;
+                } else {
+                    win[q] = win[(uint64_t)s];
+                }
+            }
+            any_pend = true;
+        } else {
+            for (uint32_t i = lane; i < len; i += nl) win[pos + i] = win[pos - dist + (i < dist ? i : i % dist)];
+        }
+        pos += len;
+        return ZI_OK;
+    }
+    ZZ_HD int stored(const zi_view<const uint8_t>& in, uint64_t at, uint32_t len)
+    {
+        if (win.n - pos < len) return ZI_E_SHAPE;
+        for (uint32_t i = lane; i < len; i += nl) win[pos + i] = in[at + i];
+        pos += len;
+        return ZI_OK;
+    }
+};
+struct zi_or_plain {
+    ZZ_HD void operator()(zi_view<uint32_t>& m, uint64_t q) const { m[q >> 5] |= 1u << (q & 31); }
+};
+
+// ---- the container --------------------------------------------------------------------------------------------
+// Header length of a zlib / gzip / raw stream held in h[0, n); <0: -1 not a valid header (or truncated), -2 preset dictionary.
+ZZ_HD inline int64_t zi_header(int format, const uint8_t* hp, uint64_t n)
+{
+    zi_view<const uint8_t> h{ hp, n };
+    if (format == 2) return 0;
+    if (format == 0) {
+        if (n < 2) return -1;
+        const uint32_t cmf = h[0], flg = h[1];
+        if ((cmf & 15) != 8 || (cmf >> 4) > 7 || ((cmf << 8) | flg) % 31 != 0) return -1;
+        if (flg & 0x20) return -2;
+        return 2;
+    }
+    if (format != 1) return -1;
+    if (n < 10 || h[0] != 0x1f || h[1] != 0x8b || h[2] != 8) return -1;
+    const uint32_t flg = h[3];
+    if (flg & 0xE0) return -1;
+    uint64_t p = 10;
+    if (flg & 4) {                                                 // FEXTRA
+        if (p + 2 > n) return -1;
+        const uint64_t xlen = h[p] | ((uint64_t)h[p + 1] << 8);
+        p += 2 + xlen;
+        if (p > n) return -1;
+    }
+    for (uint32_t f = 8; f <= 16; f <<= 1) {                       // FNAME, FCOMMENT: zero-terminated
+        if (!(flg & f)) continue;
+        while (p < n && h[p] != 0) ++p;
+        if (p >= n) return -1;
+        ++p;
+    }
+    if (flg & 2) {                                                 // FHCRC: the low 16 bits of the header's CRC-32
+        if (p + 2 > n) return -1;
+        uint32_t c = ~0u;
+        for (uint64_t i = 0; i < p; ++i) {
+            c ^= h[i];
+            for (int k = 0; k < 8; ++k) c = (c >> 1) ^ ((c & 1u) * 0xEDB88320u);
+        }
+        c = ~c;
+        if ((c & 0xFFFFu) != (h[p] | ((uint32_t)h[p + 1] << 8))) return -1;
+        p += 2;
+    }
+    return (int64_t)p;
+}
+
+}  // namespace zz
