@@ -117,6 +117,22 @@ uint32_t zz_get_packet_size(void);
 int zz_encode_device(zz_ctx* ctx, const void* d_src, uint64_t n, void* d_dst, uint64_t cap, uint64_t* out_len,
                      int format, int level, uint32_t packet_size, void* hip_stream);
 
+/* Many independent buffers, one call. Item i = d_srcs[i][0, d_ns[i]) becomes its own complete stream (container header,
+ * packets, trailer) in d_dsts[i][0, d_caps[i]); d_out_lens[i] = its length, or ~0 when it does not fit (nothing is
+ * written past d_caps[i]; the other items are still complete). Every item's bytes are exactly what
+ * zz_encode_device(ctx, d_srcs[i], d_ns[i], d_dsts[i], d_caps[i], .., format, level, packet_size, ..) writes for it alone:
+ * an empty item gets one empty final block, an item of at most one packet the reference's single-encoder stream, and no
+ * match reaches in front of an item. All five arrays live in device memory. Returns ZZ_OK, ZZ_E_NOSPACE if at least one
+ * item did not fit, or the usual errors; nitems == 0 returns ZZ_OK at once, null arrays give ZZ_E_ARG. Levels 0..3, cold
+ * packets: ZZ_E_UNSUPPORTED when the context has a warm window or the extended levels switched on. At most 2^31 - 1
+ * items and 2^31 - 1 packets in all. Synchronous; the host reads back two totals of the plan, whatever nitems is.
+ * zz_ctx_last_kernel_ms reports the batch's encode kernels. A batch is not a "last call" for zz_verify_last_device,
+ * zz_packet_extent_device and zz_packet_index_device: they return ZZ_E_ARG after it. Workspace: about what a single call
+ * over the batch's bytes takes, plus 140 bytes per item and 16 bytes per packet. */
+int zz_encode_batch_device(zz_ctx* ctx, uint64_t nitems, const void* const* d_srcs, const uint64_t* d_ns,
+                           void* const* d_dsts, const uint64_t* d_caps, uint64_t* d_out_lens,
+                           int format, int level, uint32_t packet_size, void* hip_stream);
+
 /* The same call in two halves: zz_encode_device_async enqueues the whole pipeline on `hip_stream` and returns without
  * waiting; zz_encode_finish waits for it and returns the length (or the error, as zz_encode_device). With two contexts
  * on two streams, call i+1 can be enqueued before call i is finished: its encode kernel fills the CUs call i's last

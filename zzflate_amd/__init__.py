@@ -74,6 +74,7 @@ def _load():
         "zz_get_packet_size": (u32, []),
         "zz_encode_device": (i32, [vp, vp, u64, vp, u64, pu64, i32, i32, u32, vp]),
         "zz_encode_device_async": (i32, [vp, vp, u64, vp, u64, i32, i32, u32, vp]),
+        "zz_encode_batch_device": (i32, [vp, u64, vp, vp, vp, vp, vp, i32, i32, u32, vp]),
         "zz_encode_finish": (i32, [vp, pu64]),
         "zz_encode_stream_device": (i32, [vp, vp, u64, vp, u64, pu64, i32, i32, vp]),
         "zz_encode_ranges_device": (i32, [vp, vp, u64, vp, u64, pu64, i32, i32, u32, vp]),
@@ -277,6 +278,44 @@ class Context:
         _check(lib.zz_encode_device(self._h, self._ptr(src), n, self._ptr(dst), cap, ctypes.byref(out), int(format),
                                     int(level), packet_size, st))
         return out.value
+
+    def encode_batch(self, srcs, dsts, format=Format.Zlib, level=1, packet_size=DEFAULT_PACKET, caps=None, stream=None):
+        """Many independent streams in one call: item i = ``srcs[i]`` becomes its own complete stream in ``dsts[i]``, the bytes
+        ``encode`` would write for it alone. Items are uint8 tensors on this context's device (their whole length) or
+        ``(data_ptr, nbytes)`` pairs; ``caps`` defaults to each destination's size. Returns the list of lengths, ``None``
+        for an item that did not fit its destination (the others are complete). Levels 0..3, cold packets."""
+        import torch
+        if len(srcs) != len(dsts):
+            raise ValueError(f"{len(srcs)} sources but {len(dsts)} destinations")
+        if caps is not None and len(caps) != len(dsts):
+            raise ValueError(f"{len(caps)} capacities for {len(dsts)} destinations")
+        k = len(srcs)
+        if k == 0:
+            return []
+
+        def split(t):
+            if isinstance(t, torch.Tensor):
+                if t.dtype != torch.uint8 or not t.is_contiguous():
+                    raise TypeError("items must be contiguous uint8 tensors or (data_ptr, nbytes) pairs")
+                if t.device.type != "cuda" or t.device.index != self.device:
+                    raise ValueError(f"items must live on this context's device (cuda:{self.device}), not {t.device}")
+                return t.data_ptr(), t.numel()
+            p, nb = t
+            return int(p), int(nb)
+
+        s = [split(t) for t in srcs]
+        d = [split(t) for t in dsts]
+        cp = [nb for _, nb in d] if caps is None else [int(c) for c in caps]
+        dev = f"cuda:{self.device}"
+        # the five device arrays (pointers and sizes as int64: the C side reads them as pointers and uint64)
+        table = torch.tensor([[p for p, _ in s], [nb for _, nb in s], [p for p, _ in d], cp], dtype=torch.int64).to(dev)
+        out = torch.empty(k, dtype=torch.int64, device=dev)
+        st = self._stream() if stream is None else stream
+        rc = lib.zz_encode_batch_device(self._h, k, table[0].data_ptr(), table[1].data_ptr(), table[2].data_ptr(),
+                                        table[3].data_ptr(), out.data_ptr(), int(format), int(level), packet_size, st)
+        if rc not in (0, E_NOSPACE):
+            _check(rc)
+        return [None if v == -1 else v for v in out.cpu().tolist()]
 
     def encode_async(self, src, n, dst, cap, format=Format.Zlib, level=1, packet_size=DEFAULT_PACKET, stream=None):
         """Enqueue ``encode`` on ``stream`` without waiting; ``finish()`` returns the byte count. One call per context at a

@@ -30,6 +30,7 @@
 #include "zz_datagen.h"
 #include "zz_verify.h"
 #include "zz_inflate.h"
+#include "zz_batch.h"
 
 using namespace zz;
 
@@ -109,6 +110,12 @@ struct zz_ctx {
     zz_verify_params last = {};  bool have_last = false;
     bool idx_empty = false; uint64_t idx_empty_bytes = 0;   // the last packet-mode call had an empty input (zz_packet_index_device)
     unsigned long long* d_verify = nullptr;
+    // zz_encode_batch_device: per item (first packet, slot base, tail), per packet (descriptor), the plan's totals
+    struct {
+        uint32_t* first = nullptr; uint64_t* slotbase = nullptr; uint8_t* tails = nullptr; uint64_t items_cap = 0;
+        zz_batch_desc* desc = nullptr; uint64_t desc_cap = 0;
+        zz_batch_totals* d_tot = nullptr; zz_batch_totals* h_tot = nullptr;     // (h_tot pinned)
+    } bat;
     uint32_t* d_work = nullptr;          // level 2: packet counter of the persistent workgroups
     uint64_t* d_log = nullptr; uint64_t log_cap_bytes = 0;   // sequential stream, callback form: EnsureOutputLength log
     // a call that has been enqueued but not waited for (zz_encode_device_async .. zz_encode_finish)
@@ -160,15 +167,7 @@ static int header_len(int format) { return format == ZZ_ZLIB ? 2 : format == ZZ_
 static int trailer_len(int format) { return format == ZZ_ZLIB ? 4 : format == ZZ_GZIP ? 8 : 0; }
 
 // worst-case bytes one packet can occupy in its slot, per level (multiple of 16)
-static uint32_t slot_stride_for(int level, uint32_t P)
-{
-    uint64_t b;
-    if (level == 0) b = (uint64_t)P + 10;
-    else if (level == 1) b = ((uint64_t)9 * P + 10 + 7) / 8 + 6;   // 3 + 9 bits/byte + EOB, + 1-byte stored block
-    else b = (uint64_t)P + 11;                                      // stored fallback is the worst case
-    b += 8;                                                         // the ring stores whole words
-    return (uint32_t)((b + 15) & ~15ull);
-}
+static uint32_t slot_stride_for(int level, uint32_t P) { return zz_slot_stride(level, P); }
 
 extern "C" uint64_t zz_bound(uint64_t n, int format, int level, uint32_t P)
 {
@@ -238,6 +237,8 @@ extern "C" void zz_ctx_destroy(zz_ctx* c)
     (void)hipFree(c->dec.st); (void)hipFree(c->dec.pend); (void)hipFree(c->dec.pcnt); (void)hipFree(c->dec.prem);
     (void)hipFree(c->dec.ends); (void)hipFree(c->dec.stat); (void)hipFree(c->dec.cand); (void)hipFree(c->dec.cks);
     (void)hipFree(c->dec.tot); (void)hipFree(c->dec.sres); (void)hipFree(c->dec.ok);
+    (void)hipFree(c->bat.first); (void)hipFree(c->bat.slotbase); (void)hipFree(c->bat.tails); (void)hipFree(c->bat.desc);
+    (void)hipFree(c->bat.d_tot); (void)hipHostFree(c->bat.h_tot);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
     delete c;
@@ -246,7 +247,8 @@ extern "C" void zz_ctx_destroy(zz_ctx* c)
 extern "C" uint64_t zz_ctx_workspace_bytes(const zz_ctx* c)
 {
     if (!c) return 0;
-    return c->slots_cap + c->npk_cap * (4 + 8 + sizeof(zz_cks)) + c->l2_scratch_cap + c->stage_in_cap + c->stage_out_cap;
+    return c->slots_cap + c->npk_cap * (4 + 8 + sizeof(zz_cks)) + c->l2_scratch_cap + c->stage_in_cap + c->stage_out_cap +
+           c->bat.items_cap * (4 + 8 + 128) + c->bat.desc_cap * sizeof(zz_batch_desc);
 }
 // diagnostic (not part of the public header): workgroups of the level's encode kernel the runtime places on one CU
 extern "C" int zz_debug_occupancy(int level)
@@ -1419,6 +1421,154 @@ extern "C" int zz_encode_shard_finish(zz_ctx* c, uint64_t* out_len, uint32_t* ck
     *out_len = r.stream_bytes;
     if (cks) *cks = checksum == ZZ_ZLIB ? ((r.cks_b << 16) | r.cks_a) : r.cks_a;
     return ZZ_OK;
+}
+
+// ---- many independent streams in one call (zz_batch.h) --------------------------------------------------------------------
+template <class T> static int bat_grow(T** p, uint64_t* cap, uint64_t count)
+{
+    if (count <= *cap) return ZZ_OK;
+    (void)hipFree(*p); *p = nullptr; *cap = 0;
+    HIPCHK(hipMalloc(p, count * sizeof(T)));
+    *cap = count;
+    return ZZ_OK;
+}
+static int encode_batch(zz_ctx* c, uint32_t nitems, const uint8_t* const* d_srcs, const uint64_t* d_ns, uint8_t* const* d_dsts,
+                        const uint64_t* d_caps, uint64_t* d_out_lens, int format, int level, uint32_t P, hipStream_t st, bool one_parser)
+{
+    const int cks_kind = cks_kind_for(format);
+    c->have_time = false;
+    c->have_last = false;            // verify / extent / index describe single calls only
+    c->idx_empty = false;
+    // per-item workspace: first packet (+1 entry), slot base, tail
+    if ((uint64_t)nitems + 1 > c->bat.items_cap) {
+        (void)hipFree(c->bat.first); (void)hipFree(c->bat.slotbase); (void)hipFree(c->bat.tails);
+        c->bat.first = nullptr; c->bat.slotbase = nullptr; c->bat.tails = nullptr; c->bat.items_cap = 0;
+        const uint64_t m = (uint64_t)nitems + 1;
+        HIPCHK(hipMalloc(&c->bat.first, m * sizeof(uint32_t)));
+        HIPCHK(hipMalloc(&c->bat.slotbase, m * sizeof(uint64_t)));
+        HIPCHK(hipMalloc(&c->bat.tails, m * 128));
+        c->bat.items_cap = m;
+    }
+    if (!c->bat.d_tot) {
+        HIPCHK(hipMalloc(&c->bat.d_tot, sizeof(zz_batch_totals)));
+        HIPCHK(hipHostMalloc((void**)&c->bat.h_tot, sizeof(zz_batch_totals), hipHostMallocDefault));
+    }
+    HIPCHK(hipMemsetAsync(c->d_err, 0, sizeof(uint32_t), st));
+    // the plan; its two totals are the one thing the host reads before the launches (grid and workspace sizes)
+    hipLaunchKernelGGL(k_batch_plan, dim3(1), dim3(ZZ_SCAN_THREADS), 0, st, d_ns, nitems, P, level, c->bat.first, c->bat.slotbase, c->bat.d_tot);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(c->bat.h_tot, c->bat.d_tot, sizeof(zz_batch_totals), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    const uint64_t npk64 = c->bat.h_tot->npk, slot_bytes = c->bat.h_tot->slot_bytes + 256;   // (+ room behind the last slot)
+    if (npk64 > 0x7FFFFFFFull) { set_err("too many packets for one call"); return ZZ_E_ARG; }
+    const uint32_t npk = (uint32_t)npk64;
+    bool order_checked = false;
+    if (npk) {
+        int rc = ensure_workspace(c, 0, npk, 0);                                  // sizes, offsets, checksum partials
+        if (rc) return rc;
+        if (slot_bytes > c->slots_cap) {
+            (void)hipFree(c->slots); c->slots = nullptr; c->slots_cap = 0;
+            HIPCHK(hipMalloc(&c->slots, slot_bytes));
+            c->slots_cap = slot_bytes;
+        }
+        if (level >= 2) {
+            const uint64_t need = l2_scratch_bytes(npk, 0, P);
+            if (need > c->l2_scratch_cap) {
+                (void)hipFree(c->l2_scratch); c->l2_scratch = nullptr; c->l2_scratch_cap = 0;
+                HIPCHK(hipMalloc(&c->l2_scratch, need));
+                c->l2_scratch_cap = need;
+            }
+        }
+        rc = bat_grow(&c->bat.desc, &c->bat.desc_cap, npk);
+        if (rc) return rc;
+    }
+    zz_batch_map M;
+    M.desc = c->bat.desc; M.srcs = d_srcs; M.ns = d_ns; M.first = c->bat.first; M.tails = c->bat.tails; M.npk = npk; M.level = level;
+    if (npk) {
+        hipLaunchKernelGGL(k_batch_desc, dim3((npk + 255) / 256), dim3(256), 0, st, c->bat.first, nitems, npk, P, level, c->bat.slotbase, c->bat.desc);
+        if (level >= 1)
+            hipLaunchKernelGGL(k_batch_tails, dim3(nitems < 65536 ? nitems : 65536), dim3(128), 0, st, d_srcs, d_ns, nitems, c->bat.tails);
+        zz_packet_params pp = {};
+        pp.packet_size = P; pp.cks_kind = cks_kind; pp.slots = c->slots; pp.sizes = c->sizes; pp.cks = c->cks; pp.err = c->d_err;
+        pp.prof = c->d_prof; pp.warm = 0; pp.last_is_final = 1; pp.dbg_viol = 0;
+        // the same kernel choice as a single call (encode_common), and the same run-time check behind the LDS-order verdict
+        const bool l1p = level == 1 && !one_parser && !l1_classic() && lds_order_cached(c->device);
+        const bool l2p = level >= 2 && !one_parser && !l2_classic() && (!ZZ_L2P_XCHG || lds_order_cached(c->device));
+        order_checked = l1p || (l2p && ZZ_L2P_XCHG);
+        if (order_checked) {
+            int left = g_force_violation.load();
+            while (left > 0 && !g_force_violation.compare_exchange_weak(left, left - 1)) {}
+            if (left > 0) pp.dbg_viol = 1;
+        }
+        if (c->timing) HIPCHK(hipEventRecord(c->ev0, st));
+        if (cks_kind == ZZ_CKS_CRC) {
+            hipLaunchKernelGGL(k_crc32_packets_batch, dim3(npk < 2048 ? npk : 2048), dim3(ZZ_CRC_THREADS), 0, st, pp, M);
+            pp.cks_kind = ZZ_CKS_NONE;
+        }
+        if (level == 0) {
+            zz_l0_batch_params q; q.pk = pp; q.dsts = d_dsts; q.caps = d_caps; q.format = format;
+            hipLaunchKernelGGL(k_encode_l0_batch, dim3(npk < 16384 ? npk : 16384), dim3(256), 0, st, q, M);
+        } else if (level == 1) {
+            if (l1p) hipLaunchKernelGGL(k_encode_l1p_batch, dim3(npk), dim3(ZZ_L1P_THREADS), 0, st, pp, M);
+            else hipLaunchKernelGGL(k_encode_l1_batch, dim3(npk), dim3(ZZ_L1_THREADS), 0, st, pp, M);
+        } else {
+            zz_l2_params q; q.pk = pp; q.scratch = c->l2_scratch; q.work = c->d_work; q.m = nullptr; q.k0 = 0; q.k1 = npk;
+            HIPCHK(hipMemsetAsync(c->d_work, 0, sizeof(uint32_t), st));
+            if (l2p) hipLaunchKernelGGL(k_encode_l2_batch_t<true>, dim3(l2_grid(npk, false, ZZ_L2P_WPE >= 7 ? 9 : 8)), dim3(ZZ_L2P_THREADS), 0, st, q, M);
+            else hipLaunchKernelGGL(k_encode_l2_batch_t<false>, dim3(l2_grid(npk)), dim3(ZZ_L2_THREADS), 0, st, q, M);
+        }
+        if (c->timing) { HIPCHK(hipEventRecord(c->ev1, st)); c->have_time = true; }
+        if (level != 0) hipLaunchKernelGGL(k_scan_sizes, dim3(1), dim3(ZZ_SCAN_THREADS), 0, st, c->sizes, npk, c->offsets, c->d_res);
+    }
+    zz_batch_join J;
+    J.map = M; J.sizes = c->sizes; J.offsets = c->offsets; J.cks = c->cks; J.slots = c->slots; J.dsts = d_dsts; J.caps = d_caps;
+    J.out_lens = d_out_lens; J.totals = c->bat.d_tot; J.nitems = nitems; J.packet_size = P; J.format = format; J.cks_kind = cks_kind;
+    J.level = level;
+    const uint32_t per_fin = ZZ_BATCH_FIN_THREADS / ZZ_WAVE, gf = (nitems + per_fin - 1) / per_fin;
+    hipLaunchKernelGGL(k_batch_finalize, dim3(gf < 65536 ? gf : 65536), dim3(ZZ_BATCH_FIN_THREADS), 0, st, J);
+    if (npk && level != 0) {
+        const uint32_t per_cp = ZZ_BATCH_COMPACT_THREADS / ZZ_WAVE, gc = (npk + per_cp - 1) / per_cp;
+        hipLaunchKernelGGL(k_batch_compact, dim3(gc < 65536 ? gc : 65536), dim3(ZZ_BATCH_COMPACT_THREADS), 0, st, J);
+    }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(c->bat.h_tot, c->bat.d_tot, sizeof(zz_batch_totals), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(c->h_err, c->d_err, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (c->h_err[0] & 4u) {
+        // as encode_finish: the device loses its LDS-order verdict and the whole batch runs again on the one-parser kernels
+        lds_order_revoke(c->device);
+        if (!order_checked) { set_err("internal: LDS-order violation reported by a kernel that does not check it"); return ZZ_E_HIP; }
+        return encode_batch(c, nitems, d_srcs, d_ns, d_dsts, d_caps, d_out_lens, format, level, P, st, true);
+    }
+    if (c->h_err[0] & 8u) { set_err("internal: a wavefront of the level-2 kernel waited for its neighbour longer than a packet can take (zz_level2p.h, l2p_wait_ge)"); return ZZ_E_HIP; }
+    if (c->h_err[0]) { set_err("internal: packet slot overflow"); return ZZ_E_NOSPACE; }
+    if (c->bat.h_tot->nospace) {
+        set_err(std::to_string(c->bat.h_tot->nospace) + " of " + std::to_string(nitems) + " items did not fit their destination");
+        return ZZ_E_NOSPACE;
+    }
+    return ZZ_OK;
+}
+
+extern "C" int zz_encode_batch_device(zz_ctx* c, uint64_t nitems, const void* const* d_srcs, const uint64_t* d_ns,
+                                      void* const* d_dsts, const uint64_t* d_caps, uint64_t* d_out_lens,
+                                      int format, int level, uint32_t P, void* hip_stream)
+{
+    if (!c) { set_err("null ctx"); return ZZ_E_ARG; }
+    if (nitems == 0) return ZZ_OK;
+    if (!d_srcs || !d_ns || !d_dsts || !d_caps || !d_out_lens) { set_err("null array"); return ZZ_E_ARG; }
+    if (nitems > 0x7FFFFFFFull) { set_err("too many items for one call"); return ZZ_E_ARG; }
+    if (c->pend.active) { set_err("a call enqueued with zz_encode_device_async has not been finished on this context"); return ZZ_E_ARG; }
+    if (c->warm || c->extended) {
+        set_err("batches take cold packets of levels 0..3: switch the warm window and the extended levels off on this context");
+        return ZZ_E_UNSUPPORTED;
+    }
+    if (level < 0 || level > 3) { set_err("level must be 0..3 (zzflate.cpp:201,230)"); return ZZ_E_LEVEL; }
+    if (format < 0 || format > 2) format = ZZ_DEFLATE;   // zzflate.cpp:39-48 default branch
+    if (P == 0) P = ZZ_DEFAULT_PACKET;
+    if (P > ZZ_MAX_PACKET_SIZE) { set_err("packet size must be 1..32768"); return ZZ_E_ARG; }
+    HIPCHK(hipSetDevice(c->device));
+    return encode_batch(c, (uint32_t)nitems, (const uint8_t* const*)d_srcs, d_ns, (uint8_t* const*)d_dsts, d_caps, d_out_lens, format,
+                        level, P, (hipStream_t)hip_stream, false);
 }
 
 static int ensure_stage(zz_ctx* c, uint64_t in_bytes, uint64_t out_bytes);

@@ -160,8 +160,10 @@ __global__ __launch_bounds__(ZZ_WAVE) void k_adler_packets(zz_packet_params P)
 // everything behind it (rest of the row, the later quarters) go into one GF(2) multiplication per lane; the
 // packet CRC is the XOR over lanes. CRC's initial value is folded into the packet's first word.
 // Packets that are not full (the last one) or not a multiple of 1024 bytes take the plain slicing-by-4 path.
+// MAP: zz_no_batch (one shard: P0's packets) or zz_batch_map (a batch: every packet sees its item through zz_packet_view).
 #define ZZ_CRC_THREADS 256
-__global__ __launch_bounds__(ZZ_CRC_THREADS) void k_crc32_packets(zz_packet_params P)
+template <class MAP>
+__device__ __forceinline__ void crc32_packets_run(const zz_packet_params& P0, const MAP& M)
 {
     __shared__ uint32_t tab[4][256];      // slicing-by-4: (byte at register position k) * x^32
     __shared__ uint32_t tabB[4][256];     // the same * x^(8*252): one step of 256 bytes
@@ -182,21 +184,23 @@ __global__ __launch_bounds__(ZZ_CRC_THREADS) void k_crc32_packets(zz_packet_para
         const uint32_t x252 = gf2_xpow8(252);
         for (int t = 0; t < 4; ++t) tabB[t][tid] = gf2_mulmod(tab[t][tid], x252);
     }
-    const bool fast = P.packet_size % 1024 == 0 && P.packet_size >= 1024;
-    const uint32_t quarter = P.packet_size / 4, rows = quarter / 256;
+    const bool fast = P0.packet_size % 1024 == 0 && P0.packet_size >= 1024;
+    const uint32_t quarter = P0.packet_size / 4, rows = quarter / 256;
     // fast path: x^(8 * bytes from my last word (inclusive of its own x^32) to the end of the packet)
     const uint32_t ktail = gf2_xpow8(256 - 4 * lane + quarter * (3 - wv));
     // slow path: x^(8 * bytes after my slice) for a full packet
     uint32_t shift_full;
     {
-        const uint32_t len = P.packet_size;
+        const uint32_t len = P0.packet_size;
         const uint32_t slice = ((len + ZZ_CRC_THREADS - 1) / ZZ_CRC_THREADS + 3) & ~3u;
         uint32_t b1 = tid * slice + slice;
         if (b1 > len) b1 = len;
         shift_full = gf2_xpow8(len - b1);
     }
     __syncthreads();
-    for (uint32_t k = blockIdx.x; k < P.npk; k += gridDim.x) {
+    for (uint32_t g = blockIdx.x; g < zz_batch_npk(P0, M); g += gridDim.x) {
+        uint32_t k;
+        decltype(auto) P = zz_packet_view(P0, M, g, k);
         const uint64_t off = (uint64_t)k * P.packet_size;
         const uint32_t len = (uint32_t)((P.n - off) < P.packet_size ? (P.n - off) : P.packet_size);
         const uint8_t* p = P.src + off;
@@ -250,6 +254,7 @@ __global__ __launch_bounds__(ZZ_CRC_THREADS) void k_crc32_packets(zz_packet_para
         __syncthreads();
     }
 }
+__global__ __launch_bounds__(ZZ_CRC_THREADS) void k_crc32_packets(zz_packet_params P) { crc32_packets_run(P, zz_no_batch()); }
 
 // ---- fold the per-packet partials of a shard into one (in packet order) --------------------------------
 // One workgroup; thread t folds a contiguous run of packets, then thread 0 folds the 1024 runs.

@@ -43,6 +43,67 @@ struct zz_packet_params {
 #define ZZ_ERR_SLOT_OVERFLOW 1u
 #define ZZ_ERR_LDS_ORDER 4u   // a kernel saw a slot keep a LOWER lane's store of an instruction a higher lane took part in
 
+// worst-case bytes one packet of `len` input bytes can occupy in its slot, per level (multiple of 16)
+__host__ __device__ inline uint32_t zz_slot_stride(int level, uint32_t len)
+{
+    uint64_t b;
+    if (level == 0) b = (uint64_t)len + 10;
+    else if (level == 1) b = ((uint64_t)9 * len + 10 + 7) / 8 + 6;   // 3 + 9 bits/byte + EOB, + 1-byte stored block
+    else b = (uint64_t)len + 11;                                      // stored fallback is the worst case
+    b += 8;                                                           // the ring stores whole words
+    return (uint32_t)((b + 15) & ~15ull);
+}
+
+// ---- batches (zz_encode_batch_device, zz_batch.h) ----------------------------------------------------------------
+// Many independent items in one launch. Packets are numbered across the batch (item 0's first, then item 1's, ...); a
+// packet's descriptor says whose it is. Each item is a stream of its own: cold packets, its own end, its own tail.
+struct zz_batch_desc {
+    uint32_t item;            // the item the packet belongs to
+    uint32_t k;               // its index within the item
+    uint64_t slot;            // byte offset of its slot in the batch's slots (slots are sized by the packet's own length)
+};
+struct zz_batch_map {
+    const zz_batch_desc* desc;      // one per packet of the batch
+    const uint8_t* const* srcs;     // per item: first input byte
+    const uint64_t* ns;             // per item: input bytes
+    const uint32_t* first;          // per item + 1: the item's first packet (exclusive scan of the packet counts)
+    const uint8_t* tails;           // per item: 128 bytes, its last min(n, 64) bytes followed by zeros (k_fill_tail)
+    uint32_t npk;                   // packets of the batch
+    int level;                      // slot strides: zz_slot_stride(level, len)
+};
+struct zz_no_batch {};              // the single-stream forms: the packet index is the shard's own
+
+// The packet-kernel bodies see a packet through zz_packet_params P and its index k in P's shard. A single stream's is the
+// launch's own P with k = g. A batch packet g gets a P of its own, built from its descriptor: the item as the shard (its
+// src, n and tail, no halo, the last packet final), and sizes / cks / slots based so that index k lands on packet g's
+// entries and slot. The slot stride is the packet's own (zz_slot_stride of its length), so the overflow check is exact.
+__device__ __forceinline__ uint32_t zz_batch_npk(const zz_packet_params& P, const zz_no_batch&) { return P.npk; }
+__device__ __forceinline__ uint32_t zz_batch_npk(const zz_packet_params&, const zz_batch_map& M) { return M.npk; }
+__device__ __forceinline__ const zz_packet_params& zz_packet_view(const zz_packet_params& P, const zz_no_batch&, uint32_t g, uint32_t& k)
+{
+    k = g;
+    return P;
+}
+__device__ __forceinline__ zz_packet_params zz_packet_view(const zz_packet_params& B, const zz_batch_map& M, uint32_t g, uint32_t& k)
+{
+    const zz_batch_desc d = M.desc[g];
+    zz_packet_params P = B;
+    const uint32_t f = g - d.k;                       // the item's first packet
+    k = d.k;
+    P.src = M.srcs[d.item];
+    P.n = M.ns[d.item];
+    P.halo = 0;                                       // nothing in front of an item belongs to its stream
+    P.npk = M.first[d.item + 1] - f;
+    P.last_is_final = 1;
+    P.tail = M.tails + (uint64_t)d.item * 128;
+    const uint32_t len = k + 1 < P.npk ? P.packet_size : (uint32_t)(P.n - (uint64_t)k * P.packet_size);
+    P.slot_stride = zz_slot_stride(M.level, len);
+    P.slots = B.slots + d.slot - (uint64_t)k * P.slot_stride;    // P.slots + k * P.slot_stride = this packet's slot
+    P.sizes = B.sizes + f;
+    P.cks = B.cks + f;
+    return P;
+}
+
 // ---- the sequential stream's output buffers (outputbitstream.h:171-201) ------------------------------------------
 // A single Encoder asks EnsureOutputLength(length) at every block start. With a caller-owned buffer the answer is the
 // room left in it; through the callback API the library owns chunks of 1,000,000 bytes and opens a new one when the

@@ -81,51 +81,57 @@ __device__ __forceinline__ void coop_copy_adler(uint8_t* dst, const uint8_t* src
     }
 }
 
+// one packet: its stored block(s) at d, its Adler-32 partial to P.cks[k] (when P.cks_kind asks for it); the whole workgroup
+__device__ __forceinline__ void l0_encode_packet(const zz_packet_params& P, uint32_t k, uint8_t* d, int stream_mode, uint64_t* red_a, uint64_t* red_c)
+{
+    const uint32_t tid = threadIdx.x;
+    const bool want = P.cks_kind == ZZ_CKS_ADLER;
+    const uint64_t off = (uint64_t)k * P.packet_size;
+    const uint32_t len = (uint32_t)((P.n - off) < P.packet_size ? (P.n - off) : P.packet_size);
+    const bool is_final = P.last_is_final && k == P.npk - 1;
+    const uint8_t* src = P.src + off;
+    uint32_t A = 0;
+    uint64_t C = 0;      // Adler-32 partial sums of this thread's bytes (the copy and the checksum share one read)
+    if (is_final || stream_mode) {
+        if (tid == 0) put_stored_header(d, is_final ? 1 : 0, len);
+        coop_copy_adler(d + 5, src, len, tid, blockDim.x, 0, want, A, C);
+    } else {
+        uint8_t* tail = d;
+        if (len > 1) {
+            if (tid == 0) put_stored_header(d, 0, len - 1);
+            coop_copy_adler(d + 5, src, len - 1, tid, blockDim.x, 0, want, A, C);
+            tail = d + 5 + (len - 1);
+        }
+        if (tid == 0) {
+            put_stored_header(tail, 0, 1);
+            const uint32_t last = src[len - 1];
+            tail[5] = (uint8_t)last;
+            A += last; C += (uint64_t)(len - 1) * last;
+        }
+    }
+    if (want) {
+        const uint64_t At = wave_sum64(A), Ct = wave_sum64(C);
+        if ((tid & 63) == 0) { red_a[tid >> 6] = At; red_c[tid >> 6] = Ct; }
+        __syncthreads();
+        if (tid == 0) {
+            const uint64_t Aa = red_a[0] + red_a[1] + red_a[2] + red_a[3];
+            const uint64_t Cc = red_c[0] + red_c[1] + red_c[2] + red_c[3];
+            zz_cks c;
+            c.a = (uint32_t)(Aa % ZZ_ADLER_MOD);
+            c.b = (uint32_t)(((uint64_t)len * Aa - Cc) % ZZ_ADLER_MOD);   // b = sum (len - i) d_i
+            P.cks[k] = c;
+        }
+        __syncthreads();
+    }
+}
+
 __global__ __launch_bounds__(256) void k_encode_l0(zz_l0_params Q)
 {
     __shared__ uint64_t red_a[4], red_c[4];
     const zz_packet_params& P = Q.pk;
-    const uint32_t tid = threadIdx.x;
-    const bool want = P.cks_kind == ZZ_CKS_ADLER;
     for (uint32_t k = blockIdx.x; k < P.npk; k += gridDim.x) {
-        const uint64_t off = (uint64_t)k * P.packet_size;
-        const uint32_t len = (uint32_t)((P.n - off) < P.packet_size ? (P.n - off) : P.packet_size);
-        const bool is_final = P.last_is_final && k == P.npk - 1;
-        const uint8_t* src = P.src + off;
         uint8_t* d = Q.dst + (uint64_t)k * (Q.stream_mode ? (uint64_t)P.packet_size + 5 : l0_packet_bytes(P.packet_size, false));
-        uint32_t A = 0;
-        uint64_t C = 0;      // Adler-32 partial sums of this thread's bytes (the copy and the checksum share one read)
-        if (is_final || Q.stream_mode) {
-            if (tid == 0) put_stored_header(d, is_final ? 1 : 0, len);
-            coop_copy_adler(d + 5, src, len, tid, blockDim.x, 0, want, A, C);
-        } else {
-            uint8_t* tail = d;
-            if (len > 1) {
-                if (tid == 0) put_stored_header(d, 0, len - 1);
-                coop_copy_adler(d + 5, src, len - 1, tid, blockDim.x, 0, want, A, C);
-                tail = d + 5 + (len - 1);
-            }
-            if (tid == 0) {
-                put_stored_header(tail, 0, 1);
-                const uint32_t last = src[len - 1];
-                tail[5] = (uint8_t)last;
-                A += last; C += (uint64_t)(len - 1) * last;
-            }
-        }
-        if (want) {
-            const uint64_t At = wave_sum64(A), Ct = wave_sum64(C);
-            if ((tid & 63) == 0) { red_a[tid >> 6] = At; red_c[tid >> 6] = Ct; }
-            __syncthreads();
-            if (tid == 0) {
-                const uint64_t Aa = red_a[0] + red_a[1] + red_a[2] + red_a[3];
-                const uint64_t Cc = red_c[0] + red_c[1] + red_c[2] + red_c[3];
-                zz_cks c;
-                c.a = (uint32_t)(Aa % ZZ_ADLER_MOD);
-                c.b = (uint32_t)(((uint64_t)len * Aa - Cc) % ZZ_ADLER_MOD);   // b = sum (len - i) d_i
-                P.cks[k] = c;
-            }
-            __syncthreads();
-        }
+        l0_encode_packet(P, k, d, Q.stream_mode, red_a, red_c);
     }
 }
 

@@ -1106,8 +1106,10 @@ struct zz_l2_params {
 // PP (levels 2,3 with cold packets: "k_encode_l2p"): THREE wavefronts -- the token pass on two parsers that take alternate
 // blocks (zz_level2p.h), wavefront 1 stays the helper, wavefront 2 is the second parser and sits out the rest of the packet at
 // the barriers. 27 wavefronts per CU: seven on one SIMD => at most 72 VGPRs.
-template <uint32_t BIAS, bool XD = false, bool PP = false>
-__global__ __launch_bounds__(PP ? ZZ_L2P_THREADS : ZZ_L2_THREADS, PP ? ZZ_L2P_WPE : (XD ? 6 : 5)) void k_encode_l2_t(zz_l2_params Q)
+// MAP: zz_no_batch (one shard: the packets of Q.pk) or zz_batch_map (a batch, k_encode_l2_batch_t: Q.k0 .. Q.k1 number the batch's
+// packets, and every packet sees its own item through zz_packet_view).
+template <uint32_t BIAS, bool XD, bool PP, class MAP>
+__device__ __forceinline__ void l2_encode_run(const zz_l2_params Q, const MAP M)
 {
     static_assert(!PP || (BIAS == 0 && !XD), "the two-parser token pass exists for cold packets of levels 2,3");
     const zz_packet_params& P = Q.pk;
@@ -1173,7 +1175,9 @@ __global__ __launch_bounds__(PP ? ZZ_L2P_THREADS : ZZ_L2_THREADS, PP ? ZZ_L2P_WP
     // (helper). Each wavefront runs its OWN packet loop over this body (below): with one loop around both roles,
     // values that are invariant across packets are hoisted for both roles at once and live through each other's code,
     // and the kernel does not fit its 96 registers.
-    auto packet = [&](const uint32_t k, auto roletag) {
+    auto packet = [&](const uint32_t g, auto roletag) {
+        uint32_t k;
+        decltype(auto) P = zz_packet_view(Q.pk, M, g, k);    // (this packet's view of its shard; the single stream's is Q.pk itself)
         constexpr int ROLE = decltype(roletag)::value;       // 0: parser (+ codes, first part of the emission), 1: helper, 2 (PP): second parser
         constexpr bool W0 = ROLE == 0, PB = ROLE == 2;
         // Behind the token pass: CODER builds the codes and emits the first part of the body, MID the second (PP: PB the third).
@@ -1552,6 +1556,11 @@ __global__ __launch_bounds__(PP ? ZZ_L2P_THREADS : ZZ_L2_THREADS, PP ? ZZ_L2P_WP
 #ifdef ZZ_PROF
     if (threadIdx.x == ((PP && ZZ_L2P_HELPER_CODES) ? 64u : 0u) && P.prof) for (int _i = 0; _i < 16; ++_i) atomicAdd(&P.prof[_i], prof_acc[_i]);     // the coding wavefront's stamps
 #endif
+}
+template <uint32_t BIAS, bool XD = false, bool PP = false>
+__global__ __launch_bounds__(PP ? ZZ_L2P_THREADS : ZZ_L2_THREADS, PP ? ZZ_L2P_WPE : (XD ? 6 : 5)) void k_encode_l2_t(zz_l2_params Q)
+{
+    l2_encode_run<BIAS, XD, PP>(Q, zz_no_batch());
 }
 
 // xdepth: 0 = levels 2,3; 2 / 4 / 8 = the extended levels 4 / 5 / 6 (chain depth)
