@@ -237,6 +237,26 @@ int zz_packet_index_device(zz_ctx* ctx, uint64_t* d_index, uint64_t max_entries,
 int zz_decode_device(zz_ctx* ctx, const void* d_src, uint64_t src_len, void* d_dst, uint64_t cap, uint64_t* out_len,
                      int format, uint32_t packet_size, const uint64_t* d_index, uint64_t entries, void* hip_stream);
 
+/* Many independent streams back to their bytes, one call: the mirror image of zz_encode_batch_device. Item i =
+ * d_srcs[i][0, d_src_lens[i]) -- one complete zlib / gzip / raw stream: any single-member RFC 1950 / 1951 / 1952 stream,
+ * packet-mode or not, any level, written by this library or another -- is decoded into d_dsts[i][0, d_caps[i]);
+ * d_out_lens[i] = its decoded bytes, or ~0; d_status[i] (d_status may be NULL) = ZZ_OK, ZZ_E_DATA (header, block structure,
+ * distance, truncated, bytes behind the trailer, checksum or ISIZE mismatch), ZZ_E_NOSPACE (the output does not fit
+ * d_caps[i]) or ZZ_E_UNSUPPORTED (preset dictionary). Nothing is read outside an item's source or written outside its
+ * destination, and an item that fails leaves the others complete. All six arrays live in device memory. Returns ZZ_OK
+ * when every item decoded; otherwise ZZ_E_DATA if any item's status is ZZ_E_DATA or ZZ_E_UNSUPPORTED, else ZZ_E_NOSPACE.
+ * nitems == 0 returns ZZ_OK at once; a null context, null arrays, a format outside 0..2, more than 2^31 - 1 items or an
+ * unfinished zz_encode_device_async on the context give ZZ_E_ARG before anything is launched. Synchronous; the host reads
+ * back two failure counters, whatever nitems is. Workspace: a few counters.
+ * One item is decoded by ONE wavefront (container, blocks, trailer and checksum), the wavefronts dealing themselves the items
+ * from a counter: an item decodes at a few MB/s, and the call is fast when the batch holds at least as many items as the GPU
+ * holds wavefronts (about 4,096); a stream of hundreds of MiB belongs to zz_decode_device. The call leaves the context's
+ * "last call" and "last decode" state alone: zz_ctx_last_decode_*, zz_verify_last_device and zz_packet_index_device answer
+ * after it as they did before it. */
+int zz_decode_batch_device(zz_ctx* ctx, uint64_t nitems, const void* const* d_srcs, const uint64_t* d_src_lens,
+                           void* const* d_dsts, const uint64_t* d_caps, uint64_t* d_out_lens, int32_t* d_status,
+                           int format, void* hip_stream);
+
 enum { ZZ_DECODE_INDEXED = 1, ZZ_DECODE_DISCOVERED = 2, ZZ_DECODE_SERIAL = 3 };
 /* which path the last zz_decode_device finished on (0: none) */
 int zz_ctx_last_decode_path(const zz_ctx* ctx);

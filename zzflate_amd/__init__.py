@@ -87,6 +87,7 @@ def _load():
         "zz_packet_extent_device": (i32, [vp, u64, pu64, pu64, vp]),
         "zz_packet_index_device": (i32, [vp, vp, u64, pu64, vp]),
         "zz_decode_device": (i32, [vp, vp, u64, vp, u64, pu64, i32, u32, vp, u64, vp]),
+        "zz_decode_batch_device": (i32, [vp, u64, vp, vp, vp, vp, vp, vp, i32, vp]),
         "zz_ctx_last_decode_path": (i32, [vp]),
         "zz_ctx_last_decode_stats": (i32, [vp, pu64, ctypes.POINTER(u32)]),
         "zz_ctx_last_decode_index_device": (i32, [vp, vp, u64, pu64, vp]),
@@ -279,6 +280,18 @@ class Context:
                                     int(level), packet_size, st))
         return out.value
 
+    def _item(self, t):
+        """(data_ptr, nbytes) of a batch item: a contiguous uint8 tensor on this context's device, or such a pair"""
+        import torch
+        if isinstance(t, torch.Tensor):
+            if t.dtype != torch.uint8 or not t.is_contiguous():
+                raise TypeError("items must be contiguous uint8 tensors or (data_ptr, nbytes) pairs")
+            if t.device.type != "cuda" or t.device.index != self.device:
+                raise ValueError(f"items must live on this context's device (cuda:{self.device}), not {t.device}")
+            return t.data_ptr(), t.numel()
+        p, nb = t
+        return int(p), int(nb)
+
     def encode_batch(self, srcs, dsts, format=Format.Zlib, level=1, packet_size=DEFAULT_PACKET, caps=None, stream=None):
         """Many independent streams in one call: item i = ``srcs[i]`` becomes its own complete stream in ``dsts[i]``, the bytes
         ``encode`` would write for it alone. Items are uint8 tensors on this context's device (their whole length) or
@@ -293,16 +306,7 @@ class Context:
         if k == 0:
             return []
 
-        def split(t):
-            if isinstance(t, torch.Tensor):
-                if t.dtype != torch.uint8 or not t.is_contiguous():
-                    raise TypeError("items must be contiguous uint8 tensors or (data_ptr, nbytes) pairs")
-                if t.device.type != "cuda" or t.device.index != self.device:
-                    raise ValueError(f"items must live on this context's device (cuda:{self.device}), not {t.device}")
-                return t.data_ptr(), t.numel()
-            p, nb = t
-            return int(p), int(nb)
-
+        split = self._item
         s = [split(t) for t in srcs]
         d = [split(t) for t in dsts]
         cp = [nb for _, nb in d] if caps is None else [int(c) for c in caps]
@@ -316,6 +320,34 @@ class Context:
         if rc not in (0, E_NOSPACE):
             _check(rc)
         return [None if v == -1 else v for v in out.cpu().tolist()]
+
+    def decode_batch(self, srcs, dsts, format=Format.Zlib, caps=None, stream=None):
+        """Many independent streams back to their bytes in one call: item i = ``srcs[i]`` (one complete zlib / gzip / raw
+        stream, from ``encode_batch`` or anywhere else) is decoded into ``dsts[i]``. Items as ``encode_batch`` takes them;
+        ``caps`` defaults to each destination's size. Returns ``(lens, status)``: ``lens[i]`` the decoded length or ``None``,
+        ``status[i]`` 0, E_DATA, E_NOSPACE or E_UNSUPPORTED -- an item's own failure does not raise, and leaves the others
+        complete. One wavefront decodes one item: fast for thousands of items, slow for one large one (use ``decode``)."""
+        import torch
+        if len(srcs) != len(dsts):
+            raise ValueError(f"{len(srcs)} sources but {len(dsts)} destinations")
+        if caps is not None and len(caps) != len(dsts):
+            raise ValueError(f"{len(caps)} capacities for {len(dsts)} destinations")
+        k = len(srcs)
+        if k == 0:
+            return [], []
+        s = [self._item(t) for t in srcs]
+        d = [self._item(t) for t in dsts]
+        cp = [nb for _, nb in d] if caps is None else [int(c) for c in caps]
+        dev = f"cuda:{self.device}"
+        table = torch.tensor([[p for p, _ in s], [nb for _, nb in s], [p for p, _ in d], cp], dtype=torch.int64).to(dev)
+        out = torch.empty(k, dtype=torch.int64, device=dev)
+        status = torch.empty(k, dtype=torch.int32, device=dev)
+        st = self._stream() if stream is None else stream
+        rc = lib.zz_decode_batch_device(self._h, k, table[0].data_ptr(), table[1].data_ptr(), table[2].data_ptr(),
+                                        table[3].data_ptr(), out.data_ptr(), status.data_ptr(), int(format), st)
+        if rc not in (0, E_NOSPACE, E_DATA):
+            _check(rc)
+        return [None if v == -1 else v for v in out.cpu().tolist()], status.cpu().tolist()
 
     def encode_async(self, src, n, dst, cap, format=Format.Zlib, level=1, packet_size=DEFAULT_PACKET, stream=None):
         """Enqueue ``encode`` on ``stream`` without waiting; ``finish()`` returns the byte count. One call per context at a

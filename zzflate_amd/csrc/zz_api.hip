@@ -142,6 +142,8 @@ struct zz_ctx {
         zz_cks* cks = nullptr; uint64_t cks_cap = 0;
         unsigned long long* tot = nullptr;                    // 64 counters (zz_inf_params::tot)
         zz_inf_serial_out* sres = nullptr; uint32_t* ok = nullptr;
+        unsigned long long* items_ctr = nullptr;              // zz_decode_batch_device: [0..1] failure counters, [2] the dealing counter
+        unsigned long long* items_host = nullptr;             // (pinned) the two failure counters
         int last_path = 0; uint64_t last_pending = 0; uint32_t last_rounds = 0;
         std::vector<uint64_t> last_index;                     // the index discovery recovered (zz_ctx_last_decode_index_device)
     } dec;
@@ -237,6 +239,7 @@ extern "C" void zz_ctx_destroy(zz_ctx* c)
     (void)hipFree(c->dec.st); (void)hipFree(c->dec.pend); (void)hipFree(c->dec.pcnt); (void)hipFree(c->dec.prem);
     (void)hipFree(c->dec.ends); (void)hipFree(c->dec.stat); (void)hipFree(c->dec.cand); (void)hipFree(c->dec.cks);
     (void)hipFree(c->dec.tot); (void)hipFree(c->dec.sres); (void)hipFree(c->dec.ok);
+    (void)hipFree(c->dec.items_ctr); (void)hipHostFree(c->dec.items_host);
     (void)hipFree(c->bat.first); (void)hipFree(c->bat.slotbase); (void)hipFree(c->bat.tails); (void)hipFree(c->bat.desc);
     (void)hipFree(c->bat.d_tot); (void)hipHostFree(c->bat.h_tot);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
@@ -1569,6 +1572,47 @@ extern "C" int zz_encode_batch_device(zz_ctx* c, uint64_t nitems, const void* co
     HIPCHK(hipSetDevice(c->device));
     return encode_batch(c, (uint32_t)nitems, (const uint8_t* const*)d_srcs, d_ns, (uint8_t* const*)d_dsts, d_caps, d_out_lens, format,
                         level, P, (hipStream_t)hip_stream, false);
+}
+
+// ---- a batch of independent streams back to their bytes (zz_inflate.h, k_inflate_items) ---------------------------------------
+static_assert(ZI_ITEM_OK == ZZ_OK && ZI_ITEM_NOSPACE == ZZ_E_NOSPACE && ZI_ITEM_UNSUPPORTED == ZZ_E_UNSUPPORTED && ZI_ITEM_DATA == ZZ_E_DATA,
+              "zi_item reports the C ABI's codes");
+extern "C" int zz_decode_batch_device(zz_ctx* c, uint64_t nitems, const void* const* d_srcs, const uint64_t* d_src_lens,
+                                      void* const* d_dsts, const uint64_t* d_caps, uint64_t* d_out_lens, int32_t* d_status,
+                                      int format, void* hip_stream)
+{
+    if (!c) { set_err("null ctx"); return ZZ_E_ARG; }
+    if (nitems == 0) return ZZ_OK;
+    if (format < ZZ_ZLIB || format > ZZ_DEFLATE) { set_err("format must be ZZ_ZLIB, ZZ_GZIP or ZZ_DEFLATE"); return ZZ_E_ARG; }
+    if (c->pend.active) { set_err("a call enqueued with zz_encode_device_async has not been finished on this context"); return ZZ_E_ARG; }
+    if (!d_srcs || !d_src_lens || !d_dsts || !d_caps || !d_out_lens) { set_err("null array"); return ZZ_E_ARG; }
+    if (nitems > 0x7FFFFFFFull) { set_err("too many items for one call"); return ZZ_E_ARG; }
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t st = (hipStream_t)hip_stream;
+    // workspace: the dealing counter and the two failure counters (and their pinned mirror)
+    if (!c->dec.items_ctr) HIPCHK(hipMalloc(&c->dec.items_ctr, 4 * sizeof(unsigned long long)));
+    if (!c->dec.items_host) HIPCHK(hipHostMalloc((void**)&c->dec.items_host, 2 * sizeof(unsigned long long), hipHostMallocDefault));
+    HIPCHK(hipMemsetAsync(c->dec.items_ctr, 0, 4 * sizeof(unsigned long long), st));
+    zz_inf_items_params q;
+    q.srcs = (const uint8_t* const*)d_srcs; q.src_lens = d_src_lens; q.dsts = (uint8_t* const*)d_dsts; q.caps = d_caps;
+    q.out_lens = d_out_lens; q.status = d_status; q.nitems = (uint32_t)nitems; q.format = format;
+    q.fails = c->dec.items_ctr; q.next = (unsigned int*)(c->dec.items_ctr + 2);
+    const uint64_t resident = 256ull * ZZ_INF_ITEM_WG_PER_CU;      // persistent wavefronts: what the CUs hold at once
+    hipLaunchKernelGGL(k_inflate_items, dim3((uint32_t)(nitems < resident ? nitems : resident)), dim3(ZZ_INF_THREADS), 0, st, q);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(c->dec.items_host, c->dec.items_ctr, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    const unsigned long long bad = c->dec.items_host[0], nospace = c->dec.items_host[1];
+    if (bad) {
+        set_err(std::to_string(bad) + " of " + std::to_string(nitems) + " items are not valid streams of the requested format (or need a preset dictionary)" +
+                (nospace ? ", " + std::to_string(nospace) + " did not fit their destination" : std::string()));
+        return ZZ_E_DATA;
+    }
+    if (nospace) {
+        set_err(std::to_string(nospace) + " of " + std::to_string(nitems) + " items did not fit their destination");
+        return ZZ_E_NOSPACE;
+    }
+    return ZZ_OK;
 }
 
 static int ensure_stage(zz_ctx* c, uint64_t in_bytes, uint64_t out_bytes);

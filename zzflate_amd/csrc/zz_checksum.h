@@ -6,46 +6,12 @@
 // are folded in packet order with `combine` semantics (adler.cpp:5-15) / GF(2) polynomial shifts.
 #pragma once
 #include "zz_wave.h"
-
-#define ZZ_ADLER_MOD 65521u
-#define ZZ_CRC_POLY 0xEDB88320u
+#include "zz_inflate_core.h"
 
 namespace zz {
 
-// ---- GF(2) helpers (host + device) ------------------------------------------------------------------
-// a(x)*b(x) mod P(x), bit-reflected representation (bit 31 = x^0)
-__host__ __device__ inline uint32_t gf2_mulmod(uint32_t a, uint32_t b)
-{
-    uint32_t p = 0;
-    for (uint32_t m = 0x80000000u; m; m >>= 1) {
-        if (a & m) p ^= b;
-        b = (b & 1u) ? (b >> 1) ^ ZZ_CRC_POLY : b >> 1;
-    }
-    return p;
-}
-// x^(8*nbytes) mod P
-__host__ __device__ inline uint32_t gf2_xpow8(uint64_t nbytes)
-{
-    uint32_t r = 0x80000000u;   // x^0
-    uint32_t sq = 0x00800000u;  // x^8
-    for (; nbytes; nbytes >>= 1) {
-        if (nbytes & 1) r = gf2_mulmod(r, sq);
-        sq = gf2_mulmod(sq, sq);
-    }
-    return r;
-}
-// crc(A||B) from the finished CRC-32s of A and B and |B|
-__host__ __device__ inline uint32_t crc32_combine(uint32_t crc1, uint32_t crc2, uint64_t len2)
-{
-    return gf2_mulmod(crc1, gf2_xpow8(len2)) ^ crc2;
-}
-// adler.cpp:5-15: `second` computed with start value 0
-__host__ __device__ inline uint32_t adler_combine(uint32_t first, uint32_t second, uint64_t len2)
-{
-    uint64_t a = (uint64_t)(first & 0xFFFF) + (second & 0xFFFF);
-    uint64_t b = (uint64_t)(first >> 16) + (second >> 16) + (len2 % ZZ_ADLER_MOD) * (first & 0xFFFF);
-    return (uint32_t)(((b % ZZ_ADLER_MOD) << 16) | (a % ZZ_ADLER_MOD));
-}
+// (ZZ_ADLER_MOD, ZZ_CRC_POLY, gf2_mulmod, gf2_xpow8, crc32_combine and adler_combine live in zz_inflate_core.h: the batch decoder's
+// item routine folds its lanes' partials with them, on the device and in its CPU harness)
 
 // ---- Adler-32 partial of one packet, one wavefront ----------------------------------------------------
 // Returns (a, b) for start value 0: a = sum d_i, b = sum (len - i) d_i, both mod 65521. 16 bytes per lane

@@ -18,6 +18,14 @@
 //                                phase 1 then runs from every candidate and the host keeps the chain of true starts.
 //   serial   k_inflate_serial    the same core on one workgroup with the whole output as the window (global memory):
 //                                any single-member stream -- the compatibility path.
+//   batch    k_inflate_items     many independent streams in one call (zz_decode_batch_device): one wavefront per stream, the
+//                                serial path's form of the core (zi_item: container, blocks, trailer and checksum by that one
+//                                wavefront), persistent wavefronts dealing themselves the items from a counter. No window in
+//                                the LDS, no pending bytes, no phase 2, no index: about 9 KiB of LDS and one wavefront per
+//                                workgroup, so sixteen of them are resident on a CU where phase 1 fits three. One item decodes
+//                                at ONE wavefront's speed (a few MB/s): a batch is fast when it holds at least as many items
+//                                as the GPU holds wavefronts (256 CUs x 16); a stream of hundreds of MiB belongs to
+//                                zz_decode_device.
 //
 // Workspace of one batch of B packets (B * P <= ZZ_INF_BATCH_BYTES, B <= ZZ_INF_BATCH_PACKETS): 4 bytes of pointer per
 // output byte, one bit of pending bitmap per output byte and 20 bytes per packet -- at most 264 MiB + 5 MiB, whatever the
@@ -29,6 +37,7 @@
 // the output it has consumed or produced.
 #pragma once
 #include "zz_common.h"
+#include "zz_wave.h"
 #include "zz_inflate_core.h"
 
 namespace zz {
@@ -249,6 +258,54 @@ __global__ __launch_bounds__(ZZ_INF_THREADS) void k_inflate_serial(const uint8_t
     zi_out_linear<zz_inf_fence> o{ zi_view<uint8_t>{ dst, cap }, 0, lane, ZZ_INF_THREADS, {} };
     const zi_result R = zi_run(in, view, 0, o, S, ZI_RUN_STREAM, 0, lane, ZZ_INF_THREADS);
     if (lane == 0) { res->err = R.err; res->final = R.final; res->end = R.end; res->out = R.out; }
+}
+
+// ---- a batch of independent streams: one wavefront per item (zz_decode_batch_device) ------------------------------------
+#define ZZ_INF_ITEM_WG_PER_CU 16                // resident workgroups (= wavefronts) per CU the grid is sized for
+struct zz_inf_items_params {
+    const uint8_t* const* srcs; const uint64_t* src_lens;
+    uint8_t* const* dsts; const uint64_t* caps;
+    uint64_t* out_lens; int32_t* status;       // status may be null
+    uint32_t nitems; int format;
+    unsigned int* next;                         // the next item to deal out (zero on entry)
+    unsigned long long* fails;                  // [0] items with ZZ_E_DATA / ZZ_E_UNSUPPORTED, [1] items with ZZ_E_NOSPACE
+};
+// zi_item's lane group: one wavefront, the input through the LDS stage, sums by cross-lane shuffles
+struct zz_inf_lanes {
+    typedef zz_inf_in in_t;
+    typedef zz_inf_fence fence_t;
+    uint8_t* ibuf; uint32_t lane;
+    __device__ __forceinline__ in_t input(const uint8_t* p, uint64_t n) const { return in_t{ p, n, ibuf, -(int64_t)(2 * ZZ_INF_IBUF), lane }; }
+    __device__ __forceinline__ void sync() const { __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup"); }
+    __device__ __forceinline__ uint64_t sum(uint64_t v) const { return wave_sum64(v); }
+    __device__ __forceinline__ uint32_t fold_xor(uint32_t v) const
+    {
+#pragma unroll
+        for (int o = 32; o >= 1; o >>= 1) v ^= __shfl_xor(v, o);
+        return v;
+    }
+};
+__global__ __launch_bounds__(ZZ_INF_THREADS) void k_inflate_items(zz_inf_items_params Q)
+{
+    __shared__ zi_tables S;
+    __shared__ uint4 ibuf4[ZZ_INF_IBUF / 16];
+    const uint32_t lane = threadIdx.x;
+    zz_inf_lanes w{ (uint8_t*)ibuf4, lane };
+    for (;;) {
+        // lane 0 draws the item, every lane gets its number
+        uint32_t i = 0;
+        if (lane == 0) i = atomicAdd(Q.next, 1u);
+        i = uniform(i);
+        if (i >= Q.nitems) break;
+        const zi_item_result r = zi_item(w, Q.srcs[i], Q.src_lens[i], Q.dsts[i], Q.caps[i], Q.format, S, lane, ZZ_INF_THREADS);
+        if (lane == 0) {
+            Q.out_lens[i] = r.status == ZI_ITEM_OK ? r.out : ~0ull;
+            if (Q.status) Q.status[i] = r.status;
+            if (r.status == ZI_ITEM_NOSPACE) atomicAdd(&Q.fails[1], 1ull);
+            else if (r.status != ZI_ITEM_OK) atomicAdd(&Q.fails[0], 1ull);
+        }
+        __syncthreads();                        // the next item's first stage overwrites the input buffer
+    }
 }
 
 // the trailer against the checksum of the decoded bytes (zz_checksum.h's partials, folded by k_cks_reduce)

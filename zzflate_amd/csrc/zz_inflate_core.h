@@ -1,6 +1,7 @@
 // zz_inflate_core.h -- the RFC 1951 inflate core shared by the device decoder (zz_inflate.h) and its CPU harness
 // (tests/cxx/inflate_harness.cpp): bit reader, block headers, code-length parsing, canonical table construction,
-// symbol decode and every bounds check live here, once.
+// symbol decode and every bounds check live here, once -- and, for the batch decoder (k_inflate_items) and its harness
+// (tests/cxx/inflate_items_harness.cpp), zi_item: one complete stream, container header to checksum, by one group of lanes.
 //
 // The core is written for a group of `nl` lanes that run the same control flow (one wavefront on the device, one
 // thread on the host): every lane decodes every symbol (the bit reader, the tables and the block state are uniform),
@@ -28,6 +29,13 @@
 #define ZI_CHECK(c) do { if (!(c)) { fprintf(stderr, "zz_inflate_core: access out of range at line %d\n", __LINE__); abort(); } } while (0)
 #else
 #define ZI_CHECK(c) ((void)0)
+#endif
+
+// The lanes of a wavefront run in lockstep, so what one lane writes to a table is there when another lane reads it an
+// instruction later: on the device this is nothing. A CPU harness that runs the lanes one after the other defines it as
+// "let every other lane get here" (tests/cxx/inflate_items_harness.cpp).
+#ifndef ZI_LANES_SYNC
+#define ZI_LANES_SYNC() ((void)0)
 #endif
 
 namespace zz {
@@ -70,11 +78,13 @@ ZZ_HD inline bool zi_build(zi_view<uint16_t> tab, zi_tables& S, int n, bool allo
 {
     zi_view<uint8_t> lens{ S.lens, 320 };
     zi_view<uint16_t> cnt{ S.cnt, 16 }, offs{ S.offs, 16 }, sorted{ S.sorted, 320 };
+    ZI_LANES_SYNC();                                        // every lane has finished with what `tab` held
     for (int l = 0; l < 16; ++l) cnt[l] = 0;
     for (int i = 0; i < n; ++i) cnt[lens[i]] = (uint16_t)(cnt[lens[i]] + 1);
     int maxl = 0;
     for (int l = 1; l < 16; ++l) if (cnt[l]) maxl = l;
     for (uint32_t i = lane; i < ZI_TAB; i += nl) tab[i] = (uint16_t)ZI_NOCODE;
+    ZI_LANES_SYNC();                                        // the fills below land on entries other lanes cleared
     if (maxl == 0) return allow_empty;
     int left = 1;
     for (int l = 1; l < 16; ++l) { left = (left << 1) - cnt[l]; if (left < 0) return false; }
@@ -120,6 +130,7 @@ ZZ_HD inline bool zi_build(zi_view<uint16_t> tab, zi_tables& S, int n, bool allo
         }
         code <<= 1;
     }
+    ZI_LANES_SYNC();                                        // the table is whole
     return true;
 }
 
@@ -428,6 +439,133 @@ ZZ_HD inline int64_t zi_header(int format, const uint8_t* hp, uint64_t n)
         p += 2;
     }
     return (int64_t)p;
+}
+
+// ---- checksum folds (shared with zz_checksum.h) -----------------------------------------------------------------
+#define ZZ_ADLER_MOD 65521u
+#define ZZ_CRC_POLY 0xEDB88320u
+
+// ---- GF(2) helpers (host + device) ------------------------------------------------------------------
+// a(x)*b(x) mod P(x), bit-reflected representation (bit 31 = x^0)
+ZZ_HD inline uint32_t gf2_mulmod(uint32_t a, uint32_t b)
+{
+    uint32_t p = 0;
+    for (uint32_t m = 0x80000000u; m; m >>= 1) {
+        if (a & m) p ^= b;
+        b = (b & 1u) ? (b >> 1) ^ ZZ_CRC_POLY : b >> 1;
+    }
+    return p;
+}
+// x^(8*nbytes) mod P
+ZZ_HD inline uint32_t gf2_xpow8(uint64_t nbytes)
+{
+    uint32_t r = 0x80000000u;   // x^0
+    uint32_t sq = 0x00800000u;  // x^8
+    for (; nbytes; nbytes >>= 1) {
+        if (nbytes & 1) r = gf2_mulmod(r, sq);
+        sq = gf2_mulmod(sq, sq);
+    }
+    return r;
+}
+// crc(A||B) from the finished CRC-32s of A and B and |B|
+ZZ_HD inline uint32_t crc32_combine(uint32_t crc1, uint32_t crc2, uint64_t len2)
+{
+    return gf2_mulmod(crc1, gf2_xpow8(len2)) ^ crc2;
+}
+// adler.cpp:5-15: `second` computed with start value 0
+ZZ_HD inline uint32_t adler_combine(uint32_t first, uint32_t second, uint64_t len2)
+{
+    uint64_t a = (uint64_t)(first & 0xFFFF) + (second & 0xFFFF);
+    uint64_t b = (uint64_t)(first >> 16) + (second >> 16) + (len2 % ZZ_ADLER_MOD) * (first & 0xFFFF);
+    return (uint32_t)(((b % ZZ_ADLER_MOD) << 16) | (a % ZZ_ADLER_MOD));
+}
+
+// ---- one complete stream: container header, blocks, trailer, checksum (an item of zz_decode_batch_device) -----------
+// What zz_decode_device does for one stream between the host and three kernels, done by ONE group of lanes: the header by
+// zi_header, the blocks by zi_run onto zi_out_linear over dst[0, cap) (the destination is the window), then exactly
+// trailer_len(format) bytes behind the final block and the checksum of the bytes just written, summed by the same lanes
+// (they stride the output) and folded over them. Reads only src[0, src_len), writes only dst[0, cap), ends for any input.
+//
+// L is the lane group's policy:
+//   L::in_t, in_t input(p, n)   the byte source over p[0, n) (zi_bits' In)
+//   L::fence_t                  zi_out_linear's Fence
+//   void sync()                 what every lane wrote to the output is visible to every lane
+//   uint64_t sum(uint64_t), uint32_t fold_xor(uint32_t)   over the lanes; every lane gets the result
+enum { ZI_ITEM_OK = 0, ZI_ITEM_NOSPACE = -2, ZI_ITEM_UNSUPPORTED = -5, ZI_ITEM_DATA = -6 };   // = ZZ_OK, ZZ_E_NOSPACE, ZZ_E_UNSUPPORTED, ZZ_E_DATA
+struct zi_item_result {
+    int status;              // ZI_ITEM_*
+    uint64_t out;            // decoded bytes (0 unless status is ZI_ITEM_OK)
+};
+
+// Adler-32 of out[0, n): lane j sums the bytes j, j + nl, ..; a = sum d_i, b = sum (n - i) d_i on top of the start value 1
+template <class L>
+ZZ_HD uint32_t zi_adler_lanes(L& w, const zi_view<const uint8_t>& out, uint64_t n, uint32_t lane, uint32_t nl)
+{
+    uint64_t A = 0, C = 0;                                   // sum d_i and sum (i mod 65521) d_i, both reduced
+    uint32_t im = lane % ZZ_ADLER_MOD;                       // i mod 65521 (nl is far below the modulus)
+    for (uint64_t i = lane; i < n;) {
+        uint64_t a = 0, c = 0;                               // 65536 steps of at most 2^24 each
+        for (uint32_t k = 0; k < 65536 && i < n; ++k, i += nl) {
+            const uint32_t d = out[i];
+            a += d; c += (uint64_t)im * d;
+            im += nl; if (im >= ZZ_ADLER_MOD) im -= ZZ_ADLER_MOD;
+        }
+        A = (A + a) % ZZ_ADLER_MOD; C = (C + c) % ZZ_ADLER_MOD;
+    }
+    const uint64_t At = w.sum(A) % ZZ_ADLER_MOD, Ct = w.sum(C) % ZZ_ADLER_MOD;
+    const uint64_t b = ((n % ZZ_ADLER_MOD) * At + ZZ_ADLER_MOD - Ct) % ZZ_ADLER_MOD;
+    return adler_combine(1u, ((uint32_t)b << 16) | (uint32_t)At, n);
+}
+// CRC-32 of out[0, n): lane j takes the j-th slice (a multiple of four bytes), finishes its CRC and shifts it by the bytes
+// behind the slice (crc32_combine with nothing in front); the slices XOR together
+template <class L>
+ZZ_HD uint32_t zi_crc_lanes(L& w, const zi_view<const uint8_t>& out, uint64_t n, uint32_t lane, uint32_t nl)
+{
+    const uint64_t slice = ((n + nl - 1) / nl + 3) & ~(uint64_t)3;
+    uint64_t b0 = (uint64_t)lane * slice, b1 = b0 + slice;
+    if (b0 > n) b0 = n;
+    if (b1 > n) b1 = n;
+    uint32_t c = 0;
+    if (b1 > b0) {
+        c = ~0u;
+        for (uint64_t i = b0; i < b1; ++i) {
+            c ^= out[i];
+            for (int k = 0; k < 8; ++k) c = (c >> 1) ^ ((c & 1u) * ZZ_CRC_POLY);
+        }
+        c = gf2_mulmod(~c, gf2_xpow8(n - b1));
+    }
+    return w.fold_xor(c);
+}
+
+template <class L>
+ZZ_HD zi_item_result zi_item(L& w, const uint8_t* src, uint64_t src_len, uint8_t* dst, uint64_t cap, int format, zi_tables& S,
+                             uint32_t lane, uint32_t nl)
+{
+    zi_item_result r{ ZI_ITEM_DATA, 0 };
+    const int64_t hl = zi_header(format, src, src_len);
+    if (hl == -2) { r.status = ZI_ITEM_UNSUPPORTED; return r; }
+    if (hl < 0) return r;
+    const uint64_t tl = format == 0 ? 4 : format == 1 ? 8 : 0;
+    const zi_view<const uint8_t> view{ src + hl, src_len - (uint64_t)hl };     // the blocks and the trailer
+    typename L::in_t in = w.input(view.p, view.n);
+    zi_out_linear<typename L::fence_t> o{ zi_view<uint8_t>{ dst, cap }, 0, lane, nl, {} };
+    S.kind = 0;
+    const zi_result R = zi_run(in, view, 0, o, S, ZI_RUN_STREAM, 0, lane, nl);
+    if (R.err) { if (R.err == ZI_E_SPACE) r.status = ZI_ITEM_NOSPACE; return r; }
+    if (R.end > view.n || view.n - R.end != tl) return r;                      // truncated trailer, or bytes behind it
+    const zi_view<const uint8_t> t{ view.p + R.end, tl };
+    if (format == 0) {
+        w.sync();
+        const uint32_t want = ((uint32_t)t[0] << 24) | ((uint32_t)t[1] << 16) | ((uint32_t)t[2] << 8) | t[3];
+        if (zi_adler_lanes(w, zi_view<const uint8_t>{ dst, R.out }, R.out, lane, nl) != want) return r;
+    } else if (format == 1) {
+        w.sync();
+        const uint32_t c = t[0] | ((uint32_t)t[1] << 8) | ((uint32_t)t[2] << 16) | ((uint32_t)t[3] << 24);
+        const uint32_t l = t[4] | ((uint32_t)t[5] << 8) | ((uint32_t)t[6] << 16) | ((uint32_t)t[7] << 24);
+        if (l != (uint32_t)R.out || zi_crc_lanes(w, zi_view<const uint8_t>{ dst, R.out }, R.out, lane, nl) != c) return r;
+    }
+    r.status = ZI_ITEM_OK; r.out = R.out;
+    return r;
 }
 
 }  // namespace zz
