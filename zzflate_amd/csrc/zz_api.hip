@@ -86,38 +86,67 @@ extern "C" const char* zz_build_flags(void)
         }                                                                                \
     } while (0)
 
+// The one owner of a context's device memory (zz_buf<T>) and pinned host memory (zz_pin<T>): `cap` elements at `p`, freed when the
+// context is deleted -- a buffer added to zz_ctx needs no line anywhere else. grow() keeps what is large enough; otherwise it frees
+// first and allocates then (the peak stays at one buffer, and hipFree waits for the device), and cap is set only on success.
+template <class T, bool PINNED = false> struct zz_buf {
+    T* p = nullptr;
+    uint64_t cap = 0;
+    zz_buf() = default;
+    zz_buf(const zz_buf&) = delete;
+    zz_buf& operator=(const zz_buf&) = delete;
+    ~zz_buf() { release(); }
+    void release()
+    {
+        if (PINNED) (void)hipHostFree(p); else (void)hipFree(p);
+        p = nullptr; cap = 0;
+    }
+    int grow(uint64_t count)
+    {
+        if (count <= cap) return ZZ_OK;
+        release();
+        if (PINNED) HIPCHK(hipHostMalloc((void**)&p, count * sizeof(T), hipHostMallocDefault));
+        else HIPCHK(hipMalloc((void**)&p, count * sizeof(T)));
+        cap = count;
+        return ZZ_OK;
+    }
+    uint64_t bytes() const { return cap * sizeof(T); }
+    operator T*() const { return p; }
+    T* operator->() const { return p; }
+};
+template <class T> using zz_pin = zz_buf<T, true>;
+
 struct zz_ctx {
     int device = 0;
     // workspace (grown on demand, kept across calls so steady-state calls do not allocate)
-    uint8_t* slots = nullptr;   uint64_t slots_cap = 0;
-    uint32_t* sizes = nullptr;  uint64_t* offsets = nullptr;  zz_cks* cks = nullptr;  uint64_t npk_cap = 0;
-    uint8_t* l2_scratch = nullptr; uint64_t l2_scratch_cap = 0;
-    zz_result* d_res = nullptr; zz_cks_total* d_cks_total = nullptr; uint32_t* d_err = nullptr;
-    zz_result* h_res = nullptr;          // pinned
-    unsigned long long* d_prof = nullptr; // 16 counters for diagnostic (-DZZ_PROF) builds
-    uint8_t* d_tail = nullptr;            // 128 bytes: the end of the shard being encoded, then zeros (k_encode_l1p's over-reads)
+    zz_buf<uint8_t> slots;
+    zz_buf<uint32_t> sizes; zz_buf<uint64_t> offsets; zz_buf<zz_cks> cks;      // per packet: grown together (ensure_workspace)
+    zz_buf<uint8_t> l2_scratch;
+    zz_buf<zz_result> d_res; zz_buf<zz_cks_total> d_cks_total;
+    zz_buf<uint32_t> d_err;              // 4 words; what they mean: read_err_word
+    zz_pin<zz_result> h_res;
+    zz_buf<unsigned long long> d_prof;   // 64 counters for diagnostic (-DZZ_PROF) builds
+    zz_buf<uint8_t> d_tail;              // 128 bytes: the end of the shard being encoded, then zeros (k_encode_l1p's over-reads)
     // staging for the host-buffer entry points
-    uint8_t* stage_in = nullptr;  uint64_t stage_in_cap = 0;
-    uint8_t* stage_out = nullptr; uint64_t stage_out_cap = 0;
+    zz_buf<uint8_t> stage_in, stage_out;
     // slab pipeline of the host-buffer entry points: pinned slabs in and out, device output slabs, three streams
-    uint8_t* pin_in[2] = { nullptr, nullptr };  uint64_t pin_in_cap = 0;
-    uint8_t* pin_out[2] = { nullptr, nullptr }; uint64_t pin_out_cap = 0;
-    uint8_t* slab_out[2] = { nullptr, nullptr }; uint64_t slab_out_cap = 0;
-    uint8_t* slab_in[2] = { nullptr, nullptr };                                    // device input ring: halo + slab each
+    zz_pin<uint8_t> pin_in[2], pin_out[2];
+    zz_buf<uint8_t> slab_out[2];
+    zz_buf<uint8_t> slab_in[2];          // device input ring: halo + slab each
     hipStream_t s_in = nullptr, s_enc = nullptr, s_out = nullptr;
     hipEvent_t ev_in[2] = { nullptr, nullptr }, ev_out[2] = { nullptr, nullptr };
     // what the last packet-mode call did, for zz_verify_last_device
     zz_verify_params last = {};  bool have_last = false;
     bool idx_empty = false; uint64_t idx_empty_bytes = 0;   // the last packet-mode call had an empty input (zz_packet_index_device)
-    unsigned long long* d_verify = nullptr;
-    // zz_encode_batch_device: per item (first packet, slot base, tail), per packet (descriptor), the plan's totals
+    zz_buf<unsigned long long> d_verify;
+    // zz_encode_batch_device: per item (first packet, slot base, tail: grown together), per packet (descriptor), the plan's totals
     struct {
-        uint32_t* first = nullptr; uint64_t* slotbase = nullptr; uint8_t* tails = nullptr; uint64_t items_cap = 0;
-        zz_batch_desc* desc = nullptr; uint64_t desc_cap = 0;
-        zz_batch_totals* d_tot = nullptr; zz_batch_totals* h_tot = nullptr;     // (h_tot pinned)
+        zz_buf<uint32_t> first; zz_buf<uint64_t> slotbase; zz_buf<uint8_t> tails;     // (tails: 128 bytes per item)
+        zz_buf<zz_batch_desc> desc;
+        zz_buf<zz_batch_totals> d_tot; zz_pin<zz_batch_totals> h_tot;
     } bat;
-    uint32_t* d_work = nullptr;          // level 2: packet counter of the persistent workgroups
-    uint64_t* d_log = nullptr; uint64_t log_cap_bytes = 0;   // sequential stream, callback form: EnsureOutputLength log
+    zz_buf<uint32_t> d_work;             // level 2: packet counter of the persistent workgroups
+    zz_buf<uint64_t> d_log;              // sequential stream, callback form: EnsureOutputLength log, two words per entry
     // a call that has been enqueued but not waited for (zz_encode_device_async .. zz_encode_finish)
     struct {
         bool active = false; hipStream_t st = nullptr; uint32_t npk = 0; int level = 0; bool whole = false;
@@ -126,7 +155,7 @@ struct zz_ctx {
         const uint8_t* d_src = nullptr; uint64_t n = 0, halo = 0; bool last_is_final = false; uint8_t* d_dst = nullptr; uint64_t cap = 0;
         int format = 0, cks_kind = 0, level_asked = 0; uint32_t P = 0; uint32_t warm = 0;
     } pend;
-    uint32_t* h_err = nullptr;           // pinned: the kernels' sticky error word
+    zz_pin<uint32_t> h_err;              // the kernels' sticky error word
     uint32_t warm = 0;                   // levels >= 1: warm window in bytes (0 = cold packets, the reference's threaded mode)
     bool extended = false;               // levels 4..6 accepted (beyond the reference)
     bool timing = false;
@@ -134,20 +163,26 @@ struct zz_ctx {
     bool have_time = false;
     // decode (zz_decode_device): one batch of phase-1 / phase-2 workspace, per-packet results of the call, discovery's candidates
     struct {
-        uint32_t* st = nullptr; uint64_t st_cap = 0;          // pointers, 4 bytes per output byte of a batch
-        uint32_t* pend = nullptr; uint64_t pend_cap = 0;      // bitmap words
-        uint32_t* pcnt = nullptr; uint64_t pcnt_cap = 0; uint32_t* prem = nullptr; uint64_t prem_cap = 0;
-        uint64_t* ends = nullptr; uint64_t ends_cap = 0; uint32_t* stat = nullptr; uint64_t stat_cap = 0;
-        uint64_t* cand = nullptr; uint64_t cand_cap = 0;      // candidates, then a recovered index
-        zz_cks* cks = nullptr; uint64_t cks_cap = 0;
-        unsigned long long* tot = nullptr;                    // 64 counters (zz_inf_params::tot)
-        zz_inf_serial_out* sres = nullptr; uint32_t* ok = nullptr;
-        unsigned long long* items_ctr = nullptr;              // zz_decode_batch_device: [0..1] failure counters, [2] the dealing counter
-        unsigned long long* items_host = nullptr;             // (pinned) the two failure counters
+        zz_buf<uint32_t> st;                                  // pointers, 4 bytes per output byte of a batch
+        zz_buf<uint32_t> pend;                                // bitmap words
+        zz_buf<uint32_t> pcnt, prem;
+        zz_buf<uint64_t> ends; zz_buf<uint32_t> stat;
+        zz_buf<uint64_t> cand;                                // candidates, then a recovered index
+        zz_buf<zz_cks> cks;
+        zz_buf<unsigned long long> tot;                       // 64 counters (zz_inf_params::tot)
+        zz_buf<zz_inf_serial_out> sres; zz_buf<uint32_t> ok;
+        zz_buf<unsigned long long> items_ctr;                 // zz_decode_batch_device: [0..1] failure counters, [2] the dealing counter
+        zz_pin<unsigned long long> items_host;                // the two failure counters
         int last_path = 0; uint64_t last_pending = 0; uint32_t last_rounds = 0;
         std::vector<uint64_t> last_index;                     // the index discovery recovered (zz_ctx_last_decode_index_device)
     } dec;
 };
+// one call per context at a time: every entry point that would use the buffers of an enqueued call refuses
+static bool call_pending(const zz_ctx* c)
+{
+    if (c->pend.active) set_err("a call enqueued with zz_encode_device_async has not been finished on this context");
+    return c->pend.active;
+}
 
 // Small host values (an empty input's block, a result record whose size is known up front) reach the device as kernel
 // ARGUMENTS -- copied at launch -- not as asynchronous copies from stack locals, which would still be read after an
@@ -183,7 +218,6 @@ extern "C" uint64_t zz_bound(uint64_t n, int format, int level, uint32_t P)
 }
 
 static bool lds_order_ok(int device);
-extern "C" void zz_ctx_destroy(zz_ctx* c);
 extern "C" int zz_ctx_create(int device, zz_ctx** out)
 {
     if (!out) { set_err("null out"); return ZZ_E_ARG; }
@@ -199,15 +233,15 @@ extern "C" int zz_ctx_create(int device, zz_ctx** out)
     zz_ctx* c = new zz_ctx();
     c->device = device;
     const int rc = [&]() -> int {
-        HIPCHK(hipMalloc(&c->d_res, sizeof(zz_result)));
-        HIPCHK(hipMalloc(&c->d_cks_total, sizeof(zz_cks_total)));
-        HIPCHK(hipMalloc(&c->d_err, 4 * sizeof(uint32_t)));          // [0] slot overflow, [1] stream truncated, [2] log entries
-        HIPCHK(hipMalloc(&c->d_work, 16 * sizeof(uint32_t)));
-        HIPCHK(hipMalloc(&c->d_prof, 64 * sizeof(unsigned long long)));
-        HIPCHK(hipMalloc(&c->d_tail, 128));
+        if (int rc = c->d_res.grow(1)) return rc;
+        if (int rc = c->d_cks_total.grow(1)) return rc;
+        if (int rc = c->d_err.grow(4)) return rc;
+        if (int rc = c->d_work.grow(16)) return rc;
+        if (int rc = c->d_prof.grow(64)) return rc;
+        if (int rc = c->d_tail.grow(128)) return rc;
         HIPCHK(hipMemset(c->d_prof, 0, 64 * sizeof(unsigned long long)));
-        HIPCHK(hipHostMalloc((void**)&c->h_res, sizeof(zz_result), hipHostMallocDefault));
-        HIPCHK(hipHostMalloc((void**)&c->h_err, 4 * sizeof(uint32_t), hipHostMallocDefault));
+        if (int rc = c->h_res.grow(1)) return rc;
+        if (int rc = c->h_err.grow(4)) return rc;
         HIPCHK(hipEventCreate(&c->ev0));
         HIPCHK(hipEventCreate(&c->ev1));
         (void)lds_order_ok(device);          // the probe, once per device, HERE: the launch sites only read its cached verdict
@@ -223,35 +257,23 @@ extern "C" void zz_ctx_destroy(zz_ctx* c)
     if (!c) return;
     (void)hipSetDevice(c->device);
     if (c->pend.active) { (void)hipStreamSynchronize(c->pend.st); c->pend.active = false; }   // an enqueued call still uses the buffers
-    (void)hipFree(c->slots); (void)hipFree(c->sizes); (void)hipFree(c->offsets); (void)hipFree(c->cks);
-    (void)hipFree(c->l2_scratch);
-    (void)hipFree(c->d_res); (void)hipFree(c->d_cks_total); (void)hipFree(c->d_err); (void)hipFree(c->d_prof); (void)hipFree(c->d_tail);
-    (void)hipFree(c->stage_in); (void)hipFree(c->stage_out); (void)hipFree(c->d_verify); (void)hipFree(c->d_work); (void)hipFree(c->d_log);
     for (int i = 0; i < 2; ++i) {
-        (void)hipHostFree(c->pin_in[i]); (void)hipHostFree(c->pin_out[i]); (void)hipFree(c->slab_out[i]); (void)hipFree(c->slab_in[i]);
         if (c->ev_in[i]) (void)hipEventDestroy(c->ev_in[i]);
         if (c->ev_out[i]) (void)hipEventDestroy(c->ev_out[i]);
     }
     if (c->s_in) (void)hipStreamDestroy(c->s_in);
     if (c->s_enc) (void)hipStreamDestroy(c->s_enc);
     if (c->s_out) (void)hipStreamDestroy(c->s_out);
-    (void)hipHostFree(c->h_res); (void)hipHostFree(c->h_err);
-    (void)hipFree(c->dec.st); (void)hipFree(c->dec.pend); (void)hipFree(c->dec.pcnt); (void)hipFree(c->dec.prem);
-    (void)hipFree(c->dec.ends); (void)hipFree(c->dec.stat); (void)hipFree(c->dec.cand); (void)hipFree(c->dec.cks);
-    (void)hipFree(c->dec.tot); (void)hipFree(c->dec.sres); (void)hipFree(c->dec.ok);
-    (void)hipFree(c->dec.items_ctr); (void)hipHostFree(c->dec.items_host);
-    (void)hipFree(c->bat.first); (void)hipFree(c->bat.slotbase); (void)hipFree(c->bat.tails); (void)hipFree(c->bat.desc);
-    (void)hipFree(c->bat.d_tot); (void)hipHostFree(c->bat.h_tot);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
-    delete c;
+    delete c;                            // frees every buffer (zz_buf)
 }
 
 extern "C" uint64_t zz_ctx_workspace_bytes(const zz_ctx* c)
 {
     if (!c) return 0;
-    return c->slots_cap + c->npk_cap * (4 + 8 + sizeof(zz_cks)) + c->l2_scratch_cap + c->stage_in_cap + c->stage_out_cap +
-           c->bat.items_cap * (4 + 8 + 128) + c->bat.desc_cap * sizeof(zz_batch_desc);
+    return c->slots.bytes() + c->sizes.bytes() + c->offsets.bytes() + c->cks.bytes() + c->l2_scratch.bytes() + c->stage_in.bytes() +
+           c->stage_out.bytes() + c->bat.first.bytes() + c->bat.slotbase.bytes() + c->bat.tails.bytes() + c->bat.desc.bytes();
 }
 // diagnostic (not part of the public header): workgroups of the level's encode kernel the runtime places on one CU
 extern "C" int zz_debug_occupancy(int level)
@@ -488,30 +510,21 @@ extern "C" double zz_ctx_last_kernel_ms(zz_ctx* c)
 
 static int ensure_workspace(zz_ctx* c, int level, uint64_t npk, uint32_t stride, int xdepth = 0, uint32_t P = 0)
 {
-    if (npk > c->npk_cap) {
-        (void)hipFree(c->sizes); (void)hipFree(c->offsets); (void)hipFree(c->cks);
-        c->sizes = nullptr; c->offsets = nullptr; c->cks = nullptr; c->npk_cap = 0;
-        HIPCHK(hipMalloc(&c->sizes, npk * sizeof(uint32_t)));
-        HIPCHK(hipMalloc(&c->offsets, npk * sizeof(uint64_t)));
-        HIPCHK(hipMalloc(&c->cks, npk * sizeof(zz_cks)));
-        c->npk_cap = npk;
+    if (npk > c->cks.cap) {              // (the last of the three: a failure half way leaves it empty, and the next call starts over)
+        c->sizes.release(); c->offsets.release(); c->cks.release();
+        if (int rc = c->sizes.grow(npk)) return rc;
+        if (int rc = c->offsets.grow(npk)) return rc;
+        if (int rc = c->cks.grow(npk)) return rc;
     }
-    if (level != 0) {
-        uint64_t need = npk * stride;
-        if (need > c->slots_cap) {
-            (void)hipFree(c->slots); c->slots = nullptr; c->slots_cap = 0;
-            HIPCHK(hipMalloc(&c->slots, need));
-            c->slots_cap = need;
-        }
-    }
-    if (level >= 2) {
-        uint64_t need = l2_scratch_bytes((uint32_t)npk, xdepth, P);
-        if (need > c->l2_scratch_cap) {
-            (void)hipFree(c->l2_scratch); c->l2_scratch = nullptr; c->l2_scratch_cap = 0;
-            HIPCHK(hipMalloc(&c->l2_scratch, need));
-            c->l2_scratch_cap = need;
-        }
-    }
+    if (level != 0) if (int rc = c->slots.grow(npk * stride)) return rc;
+    if (level >= 2) if (int rc = c->l2_scratch.grow(l2_scratch_bytes((uint32_t)npk, xdepth, P))) return rc;
+    return ZZ_OK;
+}
+// staging of the host-buffer entry points and of zz_encode_multi_device's pulls (64 bytes of room behind what was asked for)
+static int ensure_stage(zz_ctx* c, uint64_t in_bytes, uint64_t out_bytes)
+{
+    if (in_bytes > c->stage_in.cap) if (int rc = c->stage_in.grow(in_bytes + 64)) return rc;
+    if (out_bytes > c->stage_out.cap) if (int rc = c->stage_out.grow(out_bytes + 64)) return rc;
     return ZZ_OK;
 }
 
@@ -528,11 +541,53 @@ static bool l2_classic()
     static const bool classic = [] { const char* e = getenv("ZZFLATE_L2_KERNEL"); return e && !strcmp(e, "classic"); }();
     return classic;
 }
+// Which kernel form a packet-mode launch takes -- the one place that decides it, for single calls, batches (warm = 0, xdepth = 0) and the
+// zz_debug_l?_kernel queries. l1p: level 1 on k_encode_l1p (two parsing wavefronts) instead of k_encode_l1; l2p: levels 2,3 on
+// k_encode_l2p (its insert is an ordered exchange: zz_level2p.h, ZZ_L2P_XCHG) instead of k_encode_l2_t<0, false>; both want cold packets,
+// a positive LDS-order verdict and no ZZFLATE_L?_KERNEL=classic, and one_parser (the rerun behind a violation) rules them out.
+// order_checked: the launch relies on the LDS's lane order and checks it as it goes (error value 4): those two, and the warm window's pre-hash.
+struct launch_plan { bool l1p, l2p, order_checked; };
+static launch_plan plan_launch(const zz_ctx* c, int level, uint32_t warm, int xdepth, bool one_parser)
+{
+    launch_plan p;
+    p.l1p = level == 1 && !warm && !one_parser && !l1_classic() && lds_order_cached(c->device);
+    p.l2p = level >= 2 && !warm && xdepth == 0 && !one_parser && !l2_classic() && (!ZZ_L2P_XCHG || lds_order_cached(c->device));
+    p.order_checked = p.l1p || (warm != 0 && xdepth == 0) || (p.l2p && ZZ_L2P_XCHG);
+    return p;
+}
+// tests (zz_debug_force_lds_violation): one of the launches that were to report a violated order is this one
+static bool take_forced_violation()
+{
+    int left = g_force_violation.load();
+    while (left > 0 && !g_force_violation.compare_exchange_weak(left, left - 1)) {}
+    return left > 0;
+}
+// The packet kernels' sticky error word (zz_packet_params::err = d_err[0]; the sequential stream also keeps "truncated" in d_err[1] and
+// its log's entries in d_err[2]), read from h_err[0] once the call's stream has been waited for:
+//   value 4 (ZZ_ERR_LDS_ORDER): a kernel saw the LDS leave a LOWER lane's store in a slot that a higher lane of the same instruction wrote
+//     too (zz_level1p.h P2; zz_level1.h warm_prehash; zz_level2p.h's exchange). What it wrote is a valid stream, but not necessarily the
+//     reference's: the device loses its verdict and the caller runs the call again on the one-parser kernels (ERR_RERUN), which ask the
+//     LDS for nothing of the kind (same bytes where the two-parser ones are right);
+//   value 8: a wavefront of k_encode_l2p gave up waiting for its neighbour;
+//   anything else (ZZ_ERR_SLOT_OVERFLOW): a packet did not fit its slot.
+enum { ERR_RERUN = 1 };              // (the ZZ_E_* codes are negative)
+static int read_err_word(zz_ctx* c, bool order_checked)
+{
+    const uint32_t e = c->h_err[0];
+    if (e & 4u) {
+        lds_order_revoke(c->device);
+        if (!order_checked) { set_err("internal: LDS-order violation reported by a kernel that does not check it"); return ZZ_E_HIP; }
+        return ERR_RERUN;
+    }
+    if (e & 8u) { set_err("internal: a wavefront of the level-2 kernel waited for its neighbour longer than a packet can take (zz_level2p.h, l2p_wait_ge)"); return ZZ_E_HIP; }
+    if (e) { set_err("internal: packet slot overflow"); return ZZ_E_NOSPACE; }
+    return ZZ_OK;
+}
 // (not part of the public header) which level-1 kernel a cold packet-mode call on this context would launch now: 2 = k_encode_l1p
 // (two parsing wavefronts), 1 = k_encode_l1 (ZZFLATE_L1_KERNEL=classic, or the device's LDS-order verdict is negative)
-extern "C" int zz_debug_l1_kernel(const zz_ctx* c) { return (c && !l1_classic() && lds_order_cached(c->device)) ? 2 : 1; }
+extern "C" int zz_debug_l1_kernel(const zz_ctx* c) { return (c && plan_launch(c, 1, 0, 0, false).l1p) ? 2 : 1; }
 // (the same for levels 2,3: 2 = k_encode_l2p, 1 = the two-wavefront k_encode_l2_t<0, false>)
-extern "C" int zz_debug_l2_kernel(const zz_ctx* c) { return (c && !l2_classic() && (!ZZ_L2P_XCHG || lds_order_cached(c->device))) ? 2 : 1; }
+extern "C" int zz_debug_l2_kernel(const zz_ctx* c) { return (c && plan_launch(c, 2, 0, 0, false).l2p) ? 2 : 1; }
 // The common pipeline. with_container: write header/trailer (whole stream) or not (shard).
 static int encode_finish(zz_ctx* c, zz_result* host_res);
 // `host_res` == nullptr: enqueue only (zz_encode_device_async); the caller collects with encode_finish.
@@ -541,8 +596,7 @@ static int encode_common(zz_ctx* c, const uint8_t* d_src, uint64_t n, uint64_t h
                          uint32_t P, hipStream_t st, zz_result* host_res, bool one_parser = false)
 {
     const int level_asked = level;
-    bool order_checked = false;
-    if (c->pend.active) { set_err("a call enqueued with zz_encode_device_async has not been finished on this context"); return ZZ_E_ARG; }
+    if (call_pending(c)) return ZZ_E_ARG;
     // Levels 4..6 are beyond the reference (which rejects them, zzflate.cpp:201,230) and only exist when switched on:
     // hash chains of depth 2 / 4 / 8 over a window of 8 / 32 / 32 KiB in front of every packet, lazy matching, package-merge
     // code lengths (zz_level6.h), in the level-2 kernel's frame (dynamic blocks, stored fallback).
@@ -564,6 +618,7 @@ static int encode_common(zz_ctx* c, const uint8_t* d_src, uint64_t n, uint64_t h
     if (npk64 > 0x7FFFFFFFull) { set_err("too many packets for one call"); return ZZ_E_ARG; }
     const uint32_t npk = (uint32_t)npk64;
     const uint32_t stride = slot_stride_for(level, P);
+    const launch_plan plan = plan_launch(c, level, warm, xdepth, one_parser);
     c->have_time = false;
     c->have_last = false;            // whatever zz_verify_last_device could look at is about to change
     c->idx_empty = false;
@@ -590,17 +645,7 @@ static int encode_common(zz_ctx* c, const uint8_t* d_src, uint64_t n, uint64_t h
         pp.src = d_src; pp.n = n; pp.halo = halo; pp.packet_size = P; pp.npk = npk;
         pp.last_is_final = last_is_final ? 1 : 0; pp.cks_kind = cks_kind; pp.warm = warm;
         pp.slots = c->slots; pp.slot_stride = stride; pp.sizes = c->sizes; pp.cks = c->cks; pp.err = c->d_err; pp.prof = c->d_prof; pp.tail = c->d_tail;
-        pp.dbg_viol = 0;
-        // does this launch rely on the LDS's lane order (and check it as it goes: error bit 4)? k_encode_l1p; the warm window's pre-hash
-        const bool l1p = level == 1 && !warm && !one_parser && !l1_classic() && lds_order_cached(c->device);
-        // ... and k_encode_l2p (levels 2,3, cold): its insert is an ordered exchange (zz_level2p.h, ZZ_L2P_XCHG)
-        const bool l2p = level >= 2 && !warm && xdepth == 0 && !one_parser && !l2_classic() && (!ZZ_L2P_XCHG || lds_order_cached(c->device));
-        order_checked = l1p || (warm != 0 && xdepth == 0) || (l2p && ZZ_L2P_XCHG);
-        if (order_checked) {
-            int left = g_force_violation.load();
-            while (left > 0 && !g_force_violation.compare_exchange_weak(left, left - 1)) {}
-            if (left > 0) pp.dbg_viol = 1;
-        }
+        pp.dbg_viol = plan.order_checked && take_forced_violation() ? 1 : 0;
 
         if (c->timing) HIPCHK(hipEventRecord(c->ev0, st));   // the CRC-32 pass of the gzip container is part of the timed work
         if (cks_kind == ZZ_CKS_CRC) {
@@ -627,11 +672,11 @@ static int encode_common(zz_ctx* c, const uint8_t* d_src, uint64_t n, uint64_t h
             // (a warm window exists only where the LDS-order verdict is positive: zz_ctx_set_warm_window; k_encode_l1w = the one-parser form, A/B)
             if (pp.warm && !l1_classic()) hipLaunchKernelGGL(k_encode_l1pw, dim3(npk), dim3(ZZ_L1P_THREADS), pad_lds, st, pp);
             else if (pp.warm) hipLaunchKernelGGL(k_encode_l1w, dim3(npk), dim3(ZZ_L1_THREADS), pad_lds, st, pp);
-            else if (!l1p) hipLaunchKernelGGL(k_encode_l1, dim3(npk), dim3(ZZ_L1_THREADS), pad_lds, st, pp);
+            else if (!plan.l1p) hipLaunchKernelGGL(k_encode_l1, dim3(npk), dim3(ZZ_L1_THREADS), pad_lds, st, pp);
             else hipLaunchKernelGGL(k_encode_l1p, dim3(npk), dim3(ZZ_L1P_THREADS), pad_lds, st, pp);
         } else {
             hipLaunchKernelGGL(k_fill_tail, dim3(1), dim3(128), 0, st, pp.src, pp.n, c->d_tail);
-            launch_level2(pp, c->l2_scratch, c->d_work, st, xdepth, l2p);
+            launch_level2(pp, c->l2_scratch, c->d_work, st, xdepth, plan.l2p);
         }
         if (c->timing) { HIPCHK(hipEventRecord(c->ev1, st)); c->have_time = true; }
         if (level != 0) {
@@ -656,7 +701,7 @@ static int encode_common(zz_ctx* c, const uint8_t* d_src, uint64_t n, uint64_t h
         v.l0_stride = (uint32_t)l0_packet_bytes(P, false);
     }
     c->pend.active = true; c->pend.st = st; c->pend.npk = npk; c->pend.level = level; c->pend.whole = with_container;
-    c->pend.order_checked = order_checked;
+    c->pend.order_checked = plan.order_checked;
     c->pend.d_src = d_src; c->pend.n = n; c->pend.halo = halo; c->pend.last_is_final = last_is_final; c->pend.d_dst = d_dst; c->pend.cap = cap;
     c->pend.format = format; c->pend.cks_kind = cks_kind; c->pend.level_asked = level_asked; c->pend.P = P; c->pend.warm = warm;
     if (!host_res) return ZZ_OK;
@@ -669,14 +714,9 @@ static int encode_finish(zz_ctx* c, zz_result* host_res)
     c->pend.active = false;
     HIPCHK(hipStreamSynchronize(c->pend.st));
     *host_res = *c->h_res;
-    if (c->h_err[0] & 4u) {
-        // A kernel of this call saw the LDS leave a LOWER lane's store in a slot that a higher lane of the same instruction wrote too
-        // (zz_level1p.h P2; zz_level1.h warm_prehash; zz_level2p.h's exchange): what it wrote is a valid stream, but not necessarily
-        // the reference's. The device loses its verdict; levels 1..3 run the CALL again on the one-parser kernels, which ask the LDS
-        // for nothing of the kind (same bytes where the two-parser ones are right); a warm window has no such form and is refused.
-        lds_order_revoke(c->device);
-        if (!c->pend.order_checked) { set_err("internal: LDS-order violation reported by a kernel that does not check it"); return ZZ_E_HIP; }
-        if (c->pend.warm) {
+    const int ew = read_err_word(c, c->pend.order_checked);
+    if (ew == ERR_RERUN) {
+        if (c->pend.warm) {          // a warm window has no one-parser form
             set_err("warm window: this device's LDS served equal addresses out of lane order during the call (checked in the kernel); "
                     "the stream is valid DEFLATE but not the defined one -- warm windows are refused on this device from now on");
             return ZZ_E_UNSUPPORTED;
@@ -685,8 +725,7 @@ static int encode_finish(zz_ctx* c, zz_result* host_res)
         return encode_common(c, q.d_src, q.n, q.halo, q.last_is_final, q.d_dst, q.cap, q.format, q.cks_kind, q.whole, q.level_asked, q.P,
                              q.st, host_res, true);
     }
-    if (c->h_err[0] & 8u) { set_err("internal: a wavefront of the level-2 kernel waited for its neighbour longer than a packet can take (zz_level2p.h, l2p_wait_ge)"); return ZZ_E_HIP; }
-    if (c->h_err[0]) { set_err("internal: packet slot overflow"); return ZZ_E_NOSPACE; }
+    if (ew) return ew;
     if (host_res->err) { set_err("destination too small for the compressed stream"); return ZZ_E_NOSPACE; }
     if (c->pend.npk) { c->last.stream_bytes = host_res->stream_bytes; c->have_last = true; }
     else if (c->pend.whole || c->pend.last_is_final) { c->idx_empty = true; c->idx_empty_bytes = host_res->stream_bytes; }
@@ -701,7 +740,7 @@ extern "C" int zz_verify_last_device(zz_ctx* c, uint64_t* bad_packets, uint64_t*
     if (!c->have_last) { set_err("no packet-mode call to verify on this context"); return ZZ_E_ARG; }
     HIPCHK(hipSetDevice(c->device));
     hipStream_t st = (hipStream_t)hip_stream;
-    if (!c->d_verify) HIPCHK(hipMalloc(&c->d_verify, 2 * sizeof(unsigned long long)));
+    if (int rc = c->d_verify.grow(2)) return rc;
     const unsigned long long init[2] = { 0ull, ~0ull };
     HIPCHK(hipMemcpyAsync(c->d_verify, init, sizeof init, hipMemcpyHostToDevice, st));
     zz_verify_params v = c->last;
@@ -785,18 +824,10 @@ extern "C" int zz_ctx_last_decode_stats(const zz_ctx* c, uint64_t* pending_bytes
     return ZZ_OK;
 }
 
-template <class T> static int dec_grow(T** p, uint64_t* cap, uint64_t count)
-{
-    if (count <= *cap) return ZZ_OK;
-    (void)hipFree(*p); *p = nullptr; *cap = 0;
-    HIPCHK(hipMalloc((void**)p, count * sizeof(T)));
-    *cap = count;
-    return ZZ_OK;
-}
 // the parallel paths' workspace: when it cannot be had, the call goes to the serial path, which needs none
-template <class T> static bool dec_try_grow(T** p, uint64_t* cap, uint64_t count)
+template <class T> static bool dec_try_grow(zz_buf<T>& b, uint64_t count)
 {
-    if (dec_grow(p, cap, count) == ZZ_OK) return true;
+    if (b.grow(count) == ZZ_OK) return true;
     (void)hipGetLastError();
     return false;
 }
@@ -819,9 +850,8 @@ static int dec_packets(zz_ctx* c, const uint8_t* s, uint64_t sn, const uint64_t*
     if (B > npk) B = npk;
     if (B == 0) B = 1;
     const uint64_t per = mode == ZZ_INF_INDEXED ? B : npk;      // results kept per batch, or per candidate (bounded)
-    if (!dec_try_grow(&D.st, &D.st_cap, B * P) || !dec_try_grow(&D.pend, &D.pend_cap, B * words) ||
-        !dec_try_grow(&D.pcnt, &D.pcnt_cap, B) || !dec_try_grow(&D.prem, &D.prem_cap, B) ||
-        !dec_try_grow(&D.ends, &D.ends_cap, per) || !dec_try_grow(&D.stat, &D.stat_cap, per))
+    if (!dec_try_grow(D.st, B * P) || !dec_try_grow(D.pend, B * words) || !dec_try_grow(D.pcnt, B) || !dec_try_grow(D.prem, B) ||
+        !dec_try_grow(D.ends, per) || !dec_try_grow(D.stat, per))
         return DEC_SERIAL;
     HIPCHK(hipMemsetAsync(D.tot, 0, 64 * sizeof(unsigned long long), st));
     const uint32_t rounds = dec_ceil_log2(B) + 2;               // a chain has at most one link per packet of a batch
@@ -889,7 +919,7 @@ static int dec_discover(zz_ctx* c, const uint8_t* s, uint64_t sn, uint32_t P, ui
     // block): twice the packets that can fit bounds the speculative work on adversarial input
     uint64_t cap_c = 2 * (sn / ((uint64_t)P / 1032 + 6)) + 64;
     if (cap_c > ZZ_INF_MAX_CANDIDATES) cap_c = ZZ_INF_MAX_CANDIDATES;
-    if (!dec_try_grow(&D.cand, &D.cand_cap, cap_c + 1)) return DEC_SERIAL;
+    if (!dec_try_grow(D.cand, cap_c + 1)) return DEC_SERIAL;
     HIPCHK(hipMemsetAsync(D.tot, 0, 64 * sizeof(unsigned long long), st));
     {
         uint64_t g = (sn + 255) / 256;
@@ -965,8 +995,7 @@ static int dec_check_trailer(zz_ctx* c, const uint8_t* trailer, int format, cons
     const uint64_t npk = (n + CP - 1) / CP;
     HIPCHK(hipMemsetAsync(c->d_cks_total, 0, sizeof(zz_cks_total), st));
     if (npk) {
-        int rc = dec_grow(&D.cks, &D.cks_cap, npk);
-        if (rc) return rc;
+        if (int rc = D.cks.grow(npk)) return rc;
         zz_packet_params pp = {};
         pp.src = dst; pp.n = n; pp.packet_size = CP; pp.npk = (uint32_t)npk; pp.cks_kind = kind; pp.cks = D.cks;
         if (kind == ZZ_CKS_ADLER) hipLaunchKernelGGL(k_adler_packets, dim3(npk < 16384 ? (uint32_t)npk : 16384), dim3(ZZ_WAVE), 0, st, pp);
@@ -990,18 +1019,16 @@ extern "C" int zz_decode_device(zz_ctx* c, const void* d_src_v, uint64_t src_len
     if (format < ZZ_ZLIB || format > ZZ_DEFLATE) { set_err("format must be ZZ_ZLIB, ZZ_GZIP or ZZ_DEFLATE"); return ZZ_E_ARG; }
     if (P > ZZ_MAX_PACKET_SIZE) { set_err("packet size must be 0..32768"); return ZZ_E_ARG; }
     if ((!d_src_v && src_len) || (!d_dst_v && cap)) { set_err("null buffer"); return ZZ_E_ARG; }
-    if (c->pend.active) { set_err("a call enqueued with zz_encode_device_async has not been finished on this context"); return ZZ_E_ARG; }
+    if (call_pending(c)) return ZZ_E_ARG;
     const uint8_t* d_src = (const uint8_t*)d_src_v;
     uint8_t* d_dst = (uint8_t*)d_dst_v;
     HIPCHK(hipSetDevice(c->device));
     hipStream_t st = (hipStream_t)hip_stream;
     auto& D = c->dec;
     D.last_path = 0; D.last_pending = 0; D.last_rounds = 0; D.last_index.clear();
-    if (!D.tot) {
-        HIPCHK(hipMalloc(&D.tot, 64 * sizeof(unsigned long long)));
-        HIPCHK(hipMalloc(&D.sres, sizeof(zz_inf_serial_out)));
-        HIPCHK(hipMalloc(&D.ok, 4));
-    }
+    if (int rc = D.tot.grow(64)) return rc;
+    if (int rc = D.sres.grow(1)) return rc;
+    if (int rc = D.ok.grow(1)) return rc;
     // the container header, read on the host (it may hold a file name of any length)
     int64_t hl = 0;
     if (format != ZZ_DEFLATE) {
@@ -1072,7 +1099,7 @@ extern "C" int zz_decode_device(zz_ctx* c, const void* d_src_v, uint64_t src_len
 static int encode_stream(zz_ctx* c, const uint8_t* d_src, uint64_t n, uint8_t* d_dst, uint64_t cap, int format, int level,
                          bool chunked, std::vector<uint64_t>* chunk_sizes, hipStream_t st, zz_result* host_res)
 {
-    if (c->pend.active) { set_err("a call enqueued with zz_encode_device_async has not been finished on this context"); return ZZ_E_ARG; }
+    if (call_pending(c)) return ZZ_E_ARG;
     if (level < 0 || level > 3) { set_err("level must be 0..3 (zzflate.cpp:201,230)"); return ZZ_E_LEVEL; }
     if (!d_dst || (!d_src && n)) { set_err("null buffer"); return ZZ_E_ARG; }
     if (chunk_sizes) chunk_sizes->clear();
@@ -1128,21 +1155,13 @@ static int encode_stream(zz_ctx* c, const uint8_t* d_src, uint64_t n, uint8_t* d
         const uint32_t P = 32768, npk_c = (uint32_t)((n + P - 1) / P);   // checksum chunks
         int rc = ensure_workspace(c, 0, npk_c, 0);
         if (rc) return rc;
-        if (bound > c->slots_cap) {
-            (void)hipFree(c->slots); c->slots = nullptr; c->slots_cap = 0;
-            HIPCHK(hipMalloc(&c->slots, bound));
-            c->slots_cap = bound;
-        }
+        if ((rc = c->slots.grow(bound))) return rc;
         zz_stream_ctl ctl;
         memset(&ctl, 0, sizeof ctl);
         ctl.cap = avail; ctl.chunked = chunked ? 1 : 0; ctl.truncated = c->d_err + 1; ctl.log_n = c->d_err + 2;
         if (chunked) {
             log_cap = (uint32_t)(n / 32768 + 64);                        // far more than the blocks a stream can have
-            if ((uint64_t)log_cap * 16 > c->log_cap_bytes) {
-                (void)hipFree(c->d_log); c->d_log = nullptr; c->log_cap_bytes = 0;
-                HIPCHK(hipMalloc(&c->d_log, (uint64_t)log_cap * 16));
-                c->log_cap_bytes = (uint64_t)log_cap * 16;
-            }
+            if ((rc = c->d_log.grow((uint64_t)log_cap * 2))) return rc;
             ctl.log = c->d_log; ctl.log_cap = log_cap;
         }
         pp.packet_size = P; pp.npk = npk_c; pp.cks_kind = cks_kind; pp.cks = c->cks; pp.sizes = c->sizes;
@@ -1150,11 +1169,7 @@ static int encode_stream(zz_ctx* c, const uint8_t* d_src, uint64_t n, uint8_t* d
         else if (cks_kind == ZZ_CKS_ADLER) hipLaunchKernelGGL(k_adler_packets, dim3(npk_c < 4096 ? npk_c : 4096), dim3(ZZ_WAVE), 0, st, pp);
         zz_packet_params ps = pp;
         ps.npk = 1; ps.slots = c->slots; ps.slot_stride = (uint32_t)(bound > 0xFFFFFFF0ull ? 0xFFFFFFF0ull : bound); ps.cks_kind = ZZ_CKS_NONE;
-        if (level >= 2 && (uint64_t)ZZ_ST_SCRATCH_BYTES > c->l2_scratch_cap) {
-            (void)hipFree(c->l2_scratch); c->l2_scratch = nullptr; c->l2_scratch_cap = 0;
-            HIPCHK(hipMalloc(&c->l2_scratch, ZZ_ST_SCRATCH_BYTES));
-            c->l2_scratch_cap = ZZ_ST_SCRATCH_BYTES;
-        }
+        if (level >= 2 && (rc = c->l2_scratch.grow(ZZ_ST_SCRATCH_BYTES))) return rc;
         if (c->timing) HIPCHK(hipEventRecord(c->ev0, st));
         if (level == 1) hipLaunchKernelGGL(k_stream_l1, dim3(1), dim3(ZZ_WAVE), 0, st, ps, ctl);
         else { zz_st_params q; q.pk = ps; q.scratch = c->l2_scratch; q.ctl = ctl; hipLaunchKernelGGL(k_stream_l2, dim3(1), dim3(ZZ_WAVE), 0, st, q); }
@@ -1229,7 +1244,7 @@ static int encode_ranges(zz_ctx* c, const uint8_t* d_src, uint64_t n, uint8_t* d
     if (level == 1) { set_err("ranges: the reference's threaded level-1 stream is invalid (block lengths follow from destLen / count); use packet mode"); return ZZ_E_LEVEL; }
     if (n < 100ull * count)                                               // zzflate.cpp:84: the single encoder
         return encode_stream(c, d_src, n, d_dst, cap, format, level, false, nullptr, st, host_res);
-    if (c->pend.active) { set_err("a call enqueued with zz_encode_device_async has not been finished on this context"); return ZZ_E_ARG; }
+    if (call_pending(c)) return ZZ_E_ARG;
     if (level < 0 || level > 3) { set_err("level must be 0..3 (zzflate.cpp:201,230)"); return ZZ_E_LEVEL; }
     if (!d_dst || !d_src) { set_err("null buffer"); return ZZ_E_ARG; }
     if (n >= (1ull << 31)) { set_err("ranges: input must be < 2 GiB (the reference funnels lengths through int)"); return ZZ_E_ARG; }
@@ -1268,16 +1283,8 @@ static int encode_ranges(zz_ctx* c, const uint8_t* d_src, uint64_t n, uint8_t* d
         // per range: every block may fall back to stored blocks of <= 65535 bytes, plus the closing stored byte
         const uint64_t bound = (step + (step / 65535 + 2) * 5 + (step / 400000 + 2) * 8 + 64 + 15) & ~15ull;
         if (bound > 0xFFFFFFF0ull) { set_err("ranges: range too large"); return ZZ_E_ARG; }
-        if (bound * count > c->slots_cap) {
-            (void)hipFree(c->slots); c->slots = nullptr; c->slots_cap = 0;
-            HIPCHK(hipMalloc(&c->slots, bound * count));
-            c->slots_cap = bound * count;
-        }
-        if ((uint64_t)ZZ_ST_SCRATCH_BYTES * count > c->l2_scratch_cap) {
-            (void)hipFree(c->l2_scratch); c->l2_scratch = nullptr; c->l2_scratch_cap = 0;
-            HIPCHK(hipMalloc(&c->l2_scratch, (uint64_t)ZZ_ST_SCRATCH_BYTES * count));
-            c->l2_scratch_cap = (uint64_t)ZZ_ST_SCRATCH_BYTES * count;
-        }
+        if ((rc = c->slots.grow(bound * count))) return rc;
+        if ((rc = c->l2_scratch.grow((uint64_t)ZZ_ST_SCRATCH_BYTES * count))) return rc;
         zz_st_params q;
         memset(&q, 0, sizeof q);
         q.pk = pp; q.pk.npk = count; q.pk.slots = c->slots; q.pk.slot_stride = (uint32_t)bound; q.pk.cks_kind = ZZ_CKS_NONE;
@@ -1427,14 +1434,6 @@ extern "C" int zz_encode_shard_finish(zz_ctx* c, uint64_t* out_len, uint32_t* ck
 }
 
 // ---- many independent streams in one call (zz_batch.h) --------------------------------------------------------------------
-template <class T> static int bat_grow(T** p, uint64_t* cap, uint64_t count)
-{
-    if (count <= *cap) return ZZ_OK;
-    (void)hipFree(*p); *p = nullptr; *cap = 0;
-    HIPCHK(hipMalloc(p, count * sizeof(T)));
-    *cap = count;
-    return ZZ_OK;
-}
 static int encode_batch(zz_ctx* c, uint32_t nitems, const uint8_t* const* d_srcs, const uint64_t* d_ns, uint8_t* const* d_dsts,
                         const uint64_t* d_caps, uint64_t* d_out_lens, int format, int level, uint32_t P, hipStream_t st, bool one_parser)
 {
@@ -1443,19 +1442,15 @@ static int encode_batch(zz_ctx* c, uint32_t nitems, const uint8_t* const* d_srcs
     c->have_last = false;            // verify / extent / index describe single calls only
     c->idx_empty = false;
     // per-item workspace: first packet (+1 entry), slot base, tail
-    if ((uint64_t)nitems + 1 > c->bat.items_cap) {
-        (void)hipFree(c->bat.first); (void)hipFree(c->bat.slotbase); (void)hipFree(c->bat.tails);
-        c->bat.first = nullptr; c->bat.slotbase = nullptr; c->bat.tails = nullptr; c->bat.items_cap = 0;
-        const uint64_t m = (uint64_t)nitems + 1;
-        HIPCHK(hipMalloc(&c->bat.first, m * sizeof(uint32_t)));
-        HIPCHK(hipMalloc(&c->bat.slotbase, m * sizeof(uint64_t)));
-        HIPCHK(hipMalloc(&c->bat.tails, m * 128));
-        c->bat.items_cap = m;
+    const uint64_t m = (uint64_t)nitems + 1;
+    if (m * 128 > c->bat.tails.cap) {    // (the last of the three, as in ensure_workspace)
+        c->bat.first.release(); c->bat.slotbase.release(); c->bat.tails.release();
+        if (int rc = c->bat.first.grow(m)) return rc;
+        if (int rc = c->bat.slotbase.grow(m)) return rc;
+        if (int rc = c->bat.tails.grow(m * 128)) return rc;
     }
-    if (!c->bat.d_tot) {
-        HIPCHK(hipMalloc(&c->bat.d_tot, sizeof(zz_batch_totals)));
-        HIPCHK(hipHostMalloc((void**)&c->bat.h_tot, sizeof(zz_batch_totals), hipHostMallocDefault));
-    }
+    if (int rc = c->bat.d_tot.grow(1)) return rc;
+    if (int rc = c->bat.h_tot.grow(1)) return rc;
     HIPCHK(hipMemsetAsync(c->d_err, 0, sizeof(uint32_t), st));
     // the plan; its two totals are the one thing the host reads before the launches (grid and workspace sizes)
     hipLaunchKernelGGL(k_batch_plan, dim3(1), dim3(ZZ_SCAN_THREADS), 0, st, d_ns, nitems, P, level, c->bat.first, c->bat.slotbase, c->bat.d_tot);
@@ -1465,25 +1460,14 @@ static int encode_batch(zz_ctx* c, uint32_t nitems, const uint8_t* const* d_srcs
     const uint64_t npk64 = c->bat.h_tot->npk, slot_bytes = c->bat.h_tot->slot_bytes + 256;   // (+ room behind the last slot)
     if (npk64 > 0x7FFFFFFFull) { set_err("too many packets for one call"); return ZZ_E_ARG; }
     const uint32_t npk = (uint32_t)npk64;
-    bool order_checked = false;
+    // the same kernel choice as a single call, and the same run-time check behind the LDS-order verdict
+    const launch_plan plan = plan_launch(c, level, 0, 0, one_parser);
     if (npk) {
         int rc = ensure_workspace(c, 0, npk, 0);                                  // sizes, offsets, checksum partials
         if (rc) return rc;
-        if (slot_bytes > c->slots_cap) {
-            (void)hipFree(c->slots); c->slots = nullptr; c->slots_cap = 0;
-            HIPCHK(hipMalloc(&c->slots, slot_bytes));
-            c->slots_cap = slot_bytes;
-        }
-        if (level >= 2) {
-            const uint64_t need = l2_scratch_bytes(npk, 0, P);
-            if (need > c->l2_scratch_cap) {
-                (void)hipFree(c->l2_scratch); c->l2_scratch = nullptr; c->l2_scratch_cap = 0;
-                HIPCHK(hipMalloc(&c->l2_scratch, need));
-                c->l2_scratch_cap = need;
-            }
-        }
-        rc = bat_grow(&c->bat.desc, &c->bat.desc_cap, npk);
-        if (rc) return rc;
+        if ((rc = c->slots.grow(slot_bytes))) return rc;
+        if (level >= 2 && (rc = c->l2_scratch.grow(l2_scratch_bytes(npk, 0, P)))) return rc;
+        if ((rc = c->bat.desc.grow(npk))) return rc;
     }
     zz_batch_map M;
     M.desc = c->bat.desc; M.srcs = d_srcs; M.ns = d_ns; M.first = c->bat.first; M.tails = c->bat.tails; M.npk = npk; M.level = level;
@@ -1493,16 +1477,9 @@ static int encode_batch(zz_ctx* c, uint32_t nitems, const uint8_t* const* d_srcs
             hipLaunchKernelGGL(k_batch_tails, dim3(nitems < 65536 ? nitems : 65536), dim3(128), 0, st, d_srcs, d_ns, nitems, c->bat.tails);
         zz_packet_params pp = {};
         pp.packet_size = P; pp.cks_kind = cks_kind; pp.slots = c->slots; pp.sizes = c->sizes; pp.cks = c->cks; pp.err = c->d_err;
-        pp.prof = c->d_prof; pp.warm = 0; pp.last_is_final = 1; pp.dbg_viol = 0;
-        // the same kernel choice as a single call (encode_common), and the same run-time check behind the LDS-order verdict
-        const bool l1p = level == 1 && !one_parser && !l1_classic() && lds_order_cached(c->device);
-        const bool l2p = level >= 2 && !one_parser && !l2_classic() && (!ZZ_L2P_XCHG || lds_order_cached(c->device));
-        order_checked = l1p || (l2p && ZZ_L2P_XCHG);
-        if (order_checked) {
-            int left = g_force_violation.load();
-            while (left > 0 && !g_force_violation.compare_exchange_weak(left, left - 1)) {}
-            if (left > 0) pp.dbg_viol = 1;
-        }
+        pp.prof = c->d_prof; pp.warm = 0; pp.last_is_final = 1;
+        pp.npk = npk;                        // (the launch's packets; a packet's own view counts its item's: zz_packet_view)
+        pp.dbg_viol = plan.order_checked && take_forced_violation() ? 1 : 0;
         if (c->timing) HIPCHK(hipEventRecord(c->ev0, st));
         if (cks_kind == ZZ_CKS_CRC) {
             hipLaunchKernelGGL(k_crc32_packets_batch, dim3(npk < 2048 ? npk : 2048), dim3(ZZ_CRC_THREADS), 0, st, pp, M);
@@ -1512,13 +1489,10 @@ static int encode_batch(zz_ctx* c, uint32_t nitems, const uint8_t* const* d_srcs
             zz_l0_batch_params q; q.pk = pp; q.dsts = d_dsts; q.caps = d_caps; q.format = format;
             hipLaunchKernelGGL(k_encode_l0_batch, dim3(npk < 16384 ? npk : 16384), dim3(256), 0, st, q, M);
         } else if (level == 1) {
-            if (l1p) hipLaunchKernelGGL(k_encode_l1p_batch, dim3(npk), dim3(ZZ_L1P_THREADS), 0, st, pp, M);
+            if (plan.l1p) hipLaunchKernelGGL(k_encode_l1p_batch, dim3(npk), dim3(ZZ_L1P_THREADS), 0, st, pp, M);
             else hipLaunchKernelGGL(k_encode_l1_batch, dim3(npk), dim3(ZZ_L1_THREADS), 0, st, pp, M);
         } else {
-            zz_l2_params q; q.pk = pp; q.scratch = c->l2_scratch; q.work = c->d_work; q.m = nullptr; q.k0 = 0; q.k1 = npk;
-            HIPCHK(hipMemsetAsync(c->d_work, 0, sizeof(uint32_t), st));
-            if (l2p) hipLaunchKernelGGL(k_encode_l2_batch_t<true>, dim3(l2_grid(npk, false, ZZ_L2P_WPE >= 7 ? 9 : 8)), dim3(ZZ_L2P_THREADS), 0, st, q, M);
-            else hipLaunchKernelGGL(k_encode_l2_batch_t<false>, dim3(l2_grid(npk)), dim3(ZZ_L2_THREADS), 0, st, q, M);
+            launch_level2(pp, c->l2_scratch, c->d_work, st, 0, plan.l2p, &M);
         }
         if (c->timing) { HIPCHK(hipEventRecord(c->ev1, st)); c->have_time = true; }
         if (level != 0) hipLaunchKernelGGL(k_scan_sizes, dim3(1), dim3(ZZ_SCAN_THREADS), 0, st, c->sizes, npk, c->offsets, c->d_res);
@@ -1537,14 +1511,10 @@ static int encode_batch(zz_ctx* c, uint32_t nitems, const uint8_t* const* d_srcs
     HIPCHK(hipMemcpyAsync(c->bat.h_tot, c->bat.d_tot, sizeof(zz_batch_totals), hipMemcpyDeviceToHost, st));
     HIPCHK(hipMemcpyAsync(c->h_err, c->d_err, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
-    if (c->h_err[0] & 4u) {
-        // as encode_finish: the device loses its LDS-order verdict and the whole batch runs again on the one-parser kernels
-        lds_order_revoke(c->device);
-        if (!order_checked) { set_err("internal: LDS-order violation reported by a kernel that does not check it"); return ZZ_E_HIP; }
+    const int ew = read_err_word(c, plan.order_checked);
+    if (ew == ERR_RERUN)                 // as encode_finish: the whole batch runs again on the one-parser kernels
         return encode_batch(c, nitems, d_srcs, d_ns, d_dsts, d_caps, d_out_lens, format, level, P, st, true);
-    }
-    if (c->h_err[0] & 8u) { set_err("internal: a wavefront of the level-2 kernel waited for its neighbour longer than a packet can take (zz_level2p.h, l2p_wait_ge)"); return ZZ_E_HIP; }
-    if (c->h_err[0]) { set_err("internal: packet slot overflow"); return ZZ_E_NOSPACE; }
+    if (ew) return ew;
     if (c->bat.h_tot->nospace) {
         set_err(std::to_string(c->bat.h_tot->nospace) + " of " + std::to_string(nitems) + " items did not fit their destination");
         return ZZ_E_NOSPACE;
@@ -1560,7 +1530,7 @@ extern "C" int zz_encode_batch_device(zz_ctx* c, uint64_t nitems, const void* co
     if (nitems == 0) return ZZ_OK;
     if (!d_srcs || !d_ns || !d_dsts || !d_caps || !d_out_lens) { set_err("null array"); return ZZ_E_ARG; }
     if (nitems > 0x7FFFFFFFull) { set_err("too many items for one call"); return ZZ_E_ARG; }
-    if (c->pend.active) { set_err("a call enqueued with zz_encode_device_async has not been finished on this context"); return ZZ_E_ARG; }
+    if (call_pending(c)) return ZZ_E_ARG;
     if (c->warm || c->extended) {
         set_err("batches take cold packets of levels 0..3: switch the warm window and the extended levels off on this context");
         return ZZ_E_UNSUPPORTED;
@@ -1584,14 +1554,14 @@ extern "C" int zz_decode_batch_device(zz_ctx* c, uint64_t nitems, const void* co
     if (!c) { set_err("null ctx"); return ZZ_E_ARG; }
     if (nitems == 0) return ZZ_OK;
     if (format < ZZ_ZLIB || format > ZZ_DEFLATE) { set_err("format must be ZZ_ZLIB, ZZ_GZIP or ZZ_DEFLATE"); return ZZ_E_ARG; }
-    if (c->pend.active) { set_err("a call enqueued with zz_encode_device_async has not been finished on this context"); return ZZ_E_ARG; }
+    if (call_pending(c)) return ZZ_E_ARG;
     if (!d_srcs || !d_src_lens || !d_dsts || !d_caps || !d_out_lens) { set_err("null array"); return ZZ_E_ARG; }
     if (nitems > 0x7FFFFFFFull) { set_err("too many items for one call"); return ZZ_E_ARG; }
     HIPCHK(hipSetDevice(c->device));
     hipStream_t st = (hipStream_t)hip_stream;
     // workspace: the dealing counter and the two failure counters (and their pinned mirror)
-    if (!c->dec.items_ctr) HIPCHK(hipMalloc(&c->dec.items_ctr, 4 * sizeof(unsigned long long)));
-    if (!c->dec.items_host) HIPCHK(hipHostMalloc((void**)&c->dec.items_host, 2 * sizeof(unsigned long long), hipHostMallocDefault));
+    if (int rc = c->dec.items_ctr.grow(4)) return rc;
+    if (int rc = c->dec.items_host.grow(2)) return rc;
     HIPCHK(hipMemsetAsync(c->dec.items_ctr, 0, 4 * sizeof(unsigned long long), st));
     zz_inf_items_params q;
     q.srcs = (const uint8_t* const*)d_srcs; q.src_lens = d_src_lens; q.dsts = (uint8_t* const*)d_dsts; q.caps = d_caps;
@@ -1615,9 +1585,6 @@ extern "C" int zz_decode_batch_device(zz_ctx* c, uint64_t nitems, const void* co
     return ZZ_OK;
 }
 
-static int ensure_stage(zz_ctx* c, uint64_t in_bytes, uint64_t out_bytes);
-extern "C" int zz_header(int format, uint8_t out[10]);
-extern "C" int zz_trailer(int format, uint32_t v, uint64_t n, uint8_t out[8]);
 // The reference's fan-out and join (WriteDeflateStream, zzflate.cpp:97-155: ranges -> std::async encoders -> in-order
 // memmove) for data that is ALREADY RESIDENT on several GPUs of one process -- the north star's dataflow without
 // torch.distributed. Shard i (contiguous ranges of one stream, in order, every shard but the last a whole number of
@@ -1700,7 +1667,7 @@ extern "C" int zz_encode_multi_device(zz_ctx* const* ctxs, int nshards, const vo
         uint8_t* out = nullptr;
         uint64_t ocap = 0;
         if (i == 0) { out = dst + hl; ocap = cap - hl; }               // final place: offset known
-        else { int rc = ensure_stage(c, 0, bound[i]); if (rc) return rc; out = c->stage_out; ocap = c->stage_out_cap; }
+        else { int rc = ensure_stage(c, 0, bound[i]); if (rc) return rc; out = c->stage_out; ocap = c->stage_out.cap; }
         int rc = zz_encode_shard_device_async(c, d_src[i], n[i], halo ? halo[i] : 0, i + 1 == nshards, out, ocap, format, level, P,
                                               (void*)c->s_enc);
         if (rc) {           // finish what was enqueued so far: the contexts stay usable
@@ -1935,21 +1902,6 @@ struct ctx_lease {                       // contexts borrowed for one host call
     }
 };
 
-static int ensure_stage(zz_ctx* c, uint64_t in_bytes, uint64_t out_bytes)
-{
-    if (in_bytes > c->stage_in_cap) {
-        (void)hipFree(c->stage_in); c->stage_in = nullptr; c->stage_in_cap = 0;
-        HIPCHK(hipMalloc(&c->stage_in, in_bytes + 64));
-        c->stage_in_cap = in_bytes + 64;
-    }
-    if (out_bytes > c->stage_out_cap) {
-        (void)hipFree(c->stage_out); c->stage_out = nullptr; c->stage_out_cap = 0;
-        HIPCHK(hipMalloc(&c->stage_out, out_bytes + 64));
-        c->stage_out_cap = out_bytes + 64;
-    }
-    return ZZ_OK;
-}
-
 // ---- host-buffer entry points ------------------------------------------------------------------------------------
 // Where the compressed bytes go: straight into the caller's destination (ZzFlateEncode, zzflate.cpp:225-242) or
 // through the callback in library-owned chunks (ZzFlateEncodeToCallback, zzflate.cpp:197-222): at most 1,000,000 bytes
@@ -2022,24 +1974,22 @@ static int ensure_pipe(zz_ctx* c, uint64_t slab, uint64_t slab_bound)
             HIPCHK(hipEventCreateWithFlags(&c->ev_out[i], hipEventDisableTiming));
         }
     }
+    // each pair is freed before any of it is allocated again; the test is on the buffer allocated last, so that a failure half way
+    // starts over on the next call
     const uint64_t in_bytes = ZZ_SLAB_HALO + slab;
-    if (in_bytes > c->pin_in_cap) {
-        for (int i = 0; i < 2; ++i) { (void)hipHostFree(c->pin_in[i]); c->pin_in[i] = nullptr; (void)hipFree(c->slab_in[i]); c->slab_in[i] = nullptr; }
-        c->pin_in_cap = 0;
+    if (in_bytes + 64 > c->slab_in[1].cap) {
+        for (int i = 0; i < 2; ++i) { c->pin_in[i].release(); c->slab_in[i].release(); }
         for (int i = 0; i < 2; ++i) {
-            HIPCHK(hipHostMalloc((void**)&c->pin_in[i], in_bytes, hipHostMallocDefault));
-            HIPCHK(hipMalloc(&c->slab_in[i], in_bytes + 64));
+            if (int rc = c->pin_in[i].grow(in_bytes)) return rc;
+            if (int rc = c->slab_in[i].grow(in_bytes + 64)) return rc;
         }
-        c->pin_in_cap = in_bytes;
     }
-    if (slab_bound > c->pin_out_cap) {
-        for (int i = 0; i < 2; ++i) { (void)hipHostFree(c->pin_out[i]); c->pin_out[i] = nullptr; (void)hipFree(c->slab_out[i]); c->slab_out[i] = nullptr; }
-        c->pin_out_cap = c->slab_out_cap = 0;
+    if (slab_bound + 64 > c->slab_out[1].cap) {
+        for (int i = 0; i < 2; ++i) { c->pin_out[i].release(); c->slab_out[i].release(); }
         for (int i = 0; i < 2; ++i) {
-            HIPCHK(hipHostMalloc((void**)&c->pin_out[i], slab_bound, hipHostMallocDefault));
-            HIPCHK(hipMalloc(&c->slab_out[i], slab_bound + 64));
+            if (int rc = c->pin_out[i].grow(slab_bound)) return rc;
+            if (int rc = c->slab_out[i].grow(slab_bound + 64)) return rc;
         }
-        c->pin_out_cap = c->slab_out_cap = slab_bound;
     }
     return ZZ_OK;
 }
@@ -2107,7 +2057,7 @@ static int encode_host_slabs(const std::vector<zz_ctx*>& ctxs, const uint8_t* sr
                     if (err) return ZZ_OK;
                 }
                 uint64_t w = 0; uint32_t pc = 0;
-                rc = zz_encode_shard_device(c, c->slab_in[b] + ZZ_SLAB_HALO, len, h, i + 1 == nslab, c->slab_out[b], c->slab_out_cap, &w, &pc,
+                rc = zz_encode_shard_device(c, c->slab_in[b] + ZZ_SLAB_HALO, len, h, i + 1 == nslab, c->slab_out[b], c->pin_out[b].cap, &w, &pc,
                                             ck, level, P, (void*)c->s_enc);     // returns when the slab is encoded
                 if (rc) return rc;
                 HIPCHK(hipMemcpyAsync(c->pin_out[b], c->slab_out[b], w, hipMemcpyDeviceToHost, c->s_out));
@@ -2302,7 +2252,8 @@ extern "C" uint64_t zz_debug_host_staging_bytes(void)
 {
     std::lock_guard<std::mutex> lk(g_mu);
     uint64_t t = 0;
-    for (auto& e : g_pool) t += e.c->stage_in_cap + e.c->stage_out_cap + 2 * (e.c->pin_in_cap ? e.c->pin_in_cap + 64 : 0) + 2 * (e.c->slab_out_cap ? e.c->slab_out_cap + 64 : 0);
+    for (auto& e : g_pool)
+        t += e.c->stage_in.bytes() + e.c->stage_out.bytes() + e.c->slab_in[0].bytes() + e.c->slab_in[1].bytes() + e.c->slab_out[0].bytes() + e.c->slab_out[1].bytes();
     return t;
 }
 

@@ -1589,35 +1589,44 @@ static inline uint64_t l2_scratch_bytes(uint32_t npk, int xdepth, uint32_t P)
     if (xdepth) need += l6_m_bytes(npk, P) + (uint64_t)l6_match_grid() * 32768u * 2u * (uint32_t)xdepth;   // + the chains of every resident packet
     return need;
 }
+template <bool PP> __global__ __launch_bounds__(PP ? ZZ_L2P_THREADS : ZZ_L2_THREADS, PP ? ZZ_L2P_WPE : 5) void k_encode_l2_batch_t(zz_l2_params Q, zz_batch_map M);   // zz_batch.h
 // two_parser: levels 2,3 with cold packets on k_encode_l2p (the caller decides: not behind ZZFLATE_L2_KERNEL=classic, and -- its insert
 // is an ordered LDS exchange -- only where the device's LDS-order verdict is positive)
-static inline void launch_level2(const zz_packet_params& pp, uint8_t* scratch, uint32_t* work, hipStream_t st, int xdepth = 0, bool two_parser = true)
+// M: a batch -- the batch forms of the two cold kernels over its pp.npk packets (no window, no extended levels)
+static inline void launch_level2(const zz_packet_params& pp, uint8_t* scratch, uint32_t* work, hipStream_t st, int xdepth = 0, bool two_parser = true,
+                                 const zz_batch_map* M = nullptr)
 {
     zz_l2_params q; q.pk = pp; q.scratch = scratch; q.work = work; q.m = nullptr; q.k0 = 0; q.k1 = pp.npk;
-    if (!xdepth) {
+    const dim3 g1(l2_grid(pp.npk)), b1(ZZ_L2_THREADS), g2(l2_grid(pp.npk, false, ZZ_L2P_WPE >= 7 ? 9 : 8)), b2(ZZ_L2P_THREADS);   // one parser, two
+    if (!xdepth && !M) {
         (void)hipMemsetAsync(work, 0, sizeof(uint32_t), st);
-        const dim3 g(l2_grid(pp.npk)), b(ZZ_L2_THREADS);
-        if (pp.warm) hipLaunchKernelGGL((k_encode_l2_t<32768u, false>), g, b, 0, st, q);
-        else if (!two_parser) hipLaunchKernelGGL((k_encode_l2_t<0u, false>), g, b, 0, st, q);
-        else hipLaunchKernelGGL((k_encode_l2_t<0u, false, true>), dim3(l2_grid(pp.npk, false, ZZ_L2P_WPE >= 7 ? 9 : 8)), dim3(ZZ_L2P_THREADS), 0, st, q);
+        if (pp.warm) hipLaunchKernelGGL((k_encode_l2_t<32768u, false>), g1, b1, 0, st, q);
+        else if (!two_parser) hipLaunchKernelGGL((k_encode_l2_t<0u, false>), g1, b1, 0, st, q);
+        else hipLaunchKernelGGL((k_encode_l2_t<0u, false, true>), g2, b2, 0, st, q);
         return;
     }
-    uint32_t* const m = (uint32_t*)(scratch + (uint64_t)l2_grid(pp.npk, true) * ZZ_L2_SCRATCH_BYTES);
-    const uint32_t batch = l6_batch_packets(pp.npk, pp.packet_size);
-    const uint32_t mgrid = l6_match_grid();
-    uint16_t* const chains = (uint16_t*)((uint8_t*)m + l6_m_bytes(pp.npk, pp.packet_size));
-    for (uint32_t k0 = 0; k0 < pp.npk; k0 += batch) {
-        const uint32_t k1 = pp.npk - k0 < batch ? pp.npk : k0 + batch;
-        (void)hipMemsetAsync(work, 0, 2 * sizeof(uint32_t), st);
-        zz_l6m_params qm; qm.pk = pp; qm.m = m; qm.chains = chains; qm.work = work + 1; qm.k0 = k0; qm.k1 = k1;
-        const dim3 gm((k1 - k0) < mgrid ? (k1 - k0) : mgrid), bm(ZZ_L6M_THREADS);
-        if (xdepth == 2) hipLaunchKernelGGL((k_l6_matches<2>), gm, bm, 0, st, qm);
-        else if (xdepth == 4) hipLaunchKernelGGL((k_l6_matches<4>), gm, bm, 0, st, qm);
-        else hipLaunchKernelGGL((k_l6_matches<8>), gm, bm, 0, st, qm);
-        q.m = m; q.k0 = k0; q.k1 = k1;
-        const dim3 g(l2_grid(k1 - k0, true)), b(ZZ_L2_THREADS);
-        hipLaunchKernelGGL((k_encode_l2_t<32768u, true>), g, b, 0, st, q);
+    if (xdepth) {
+        uint32_t* const m = (uint32_t*)(scratch + (uint64_t)l2_grid(pp.npk, true) * ZZ_L2_SCRATCH_BYTES);
+        const uint32_t batch = l6_batch_packets(pp.npk, pp.packet_size);
+        const uint32_t mgrid = l6_match_grid();
+        uint16_t* const chains = (uint16_t*)((uint8_t*)m + l6_m_bytes(pp.npk, pp.packet_size));
+        for (uint32_t k0 = 0; k0 < pp.npk; k0 += batch) {
+            const uint32_t k1 = pp.npk - k0 < batch ? pp.npk : k0 + batch;
+            (void)hipMemsetAsync(work, 0, 2 * sizeof(uint32_t), st);
+            zz_l6m_params qm; qm.pk = pp; qm.m = m; qm.chains = chains; qm.work = work + 1; qm.k0 = k0; qm.k1 = k1;
+            const dim3 gm((k1 - k0) < mgrid ? (k1 - k0) : mgrid), bm(ZZ_L6M_THREADS);
+            if (xdepth == 2) hipLaunchKernelGGL((k_l6_matches<2>), gm, bm, 0, st, qm);
+            else if (xdepth == 4) hipLaunchKernelGGL((k_l6_matches<4>), gm, bm, 0, st, qm);
+            else hipLaunchKernelGGL((k_l6_matches<8>), gm, bm, 0, st, qm);
+            q.m = m; q.k0 = k0; q.k1 = k1;
+            const dim3 g(l2_grid(k1 - k0, true)), b(ZZ_L2_THREADS);
+            hipLaunchKernelGGL((k_encode_l2_t<32768u, true>), g, b, 0, st, q);
+        }
+        return;
     }
+    (void)hipMemsetAsync(work, 0, sizeof(uint32_t), st);
+    if (two_parser) hipLaunchKernelGGL((k_encode_l2_batch_t<true>), g2, b2, 0, st, q, *M);
+    else hipLaunchKernelGGL((k_encode_l2_batch_t<false>), g1, b1, 0, st, q, *M);
 }
 
 }  // namespace zz
