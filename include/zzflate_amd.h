@@ -257,6 +257,36 @@ int zz_decode_batch_device(zz_ctx* ctx, uint64_t nitems, const void* const* d_sr
                            void* const* d_dsts, const uint64_t* d_caps, uint64_t* d_out_lens, int32_t* d_status,
                            int format, void* hip_stream);
 
+/* Random access into a stored stream: decoded bytes [first, first + nbytes) of a packet-mode stream, from the stream and its
+ * packet index alone. d_src[0, src_len) is the WHOLE zlib / gzip / raw stream, d_index its `entries` = packets + 1 offsets as
+ * zz_packet_index_device or zz_ctx_last_decode_index_device return them (the index is required: finding packet starts needs the
+ * whole stream and stays with zz_decode_device), packet_size 1..32768 the one it was written with. With L the stream's decoded
+ * length, d_dst[0, m) receives bytes [first, first + m), m = min(nbytes, L - first) -- the range is clipped at the stream's end,
+ * m = 0 for L <= first < packets * packet_size -- and *out_len = m. Nothing is written outside d_dst[0, min(m, cap)).
+ *   ZZ_E_ARG, before anything is launched: a null context, source, index or out_len (or a null d_dst with cap > 0); packet_size
+ *     outside 1..32768; a format outside 0..2; entries < 2; first >= (entries - 1) * packet_size; first + nbytes overflows; an
+ *     unfinished zz_encode_device_async on the context. nbytes == 0 with arguments that pass returns ZZ_OK and *out_len = 0 at once.
+ *   ZZ_E_NOSPACE: m > cap; *out_len = ~0, bytes past cap are untouched.   ZZ_E_UNSUPPORTED: a preset dictionary (FDICT).
+ *   ZZ_E_DATA: a bad container header; index[0] != 0 or index[last] not the stream's DEFLATE length; a decoded packet that is
+ *     not what the index says (exactly packet_size bytes, ending at the next start, BFINAL on the last packet only) or that
+ *     refers to bytes in front of the stream.
+ * What is decoded: the packets the range touches and a look-back in front of them, for bytes whose match source lies in an
+ * earlier packet; when a byte of the range still points in front of the decoded packets, the call repeats with four times the
+ * look-back. The cost is bounded by the packets touched -- there is no serial path, so a damaged packet is
+ * refused at the parallel rate -- and a call never takes less than one wavefront needs for one packet.
+ * NOT CHECKED: the trailer's checksum (Adler-32, CRC-32, ISIZE). It covers bytes this call never decodes, so a corrupt byte
+ * that leaves a packet's structure intact (a changed literal, a changed stored byte) comes back as a wrong byte; packets
+ * outside the decoded ones are not looked at at all. zz_decode_device checks the whole stream.
+ * Workspace: as zz_decode_device's batch plus one byte per output byte of a batch (64 MiB). Synchronous. Leaves the
+ * context's "last call" and "last decode" state alone, as zz_decode_batch_device does. */
+int zz_decode_range_device(zz_ctx* ctx, const void* d_src, uint64_t src_len, int format, uint32_t packet_size,
+                           const uint64_t* d_index, uint64_t entries, uint64_t first, uint64_t nbytes,
+                           void* d_dst, uint64_t cap, uint64_t* out_len, void* hip_stream);
+/* what the last successful zz_decode_range_device did: the first packet it decoded (the range's first packet minus the final
+ * look-back), the packets decoded in the final attempt, the attempts, and the bytes phase 1 left pending in the final attempt */
+int zz_ctx_last_decode_range_stats(const zz_ctx* ctx, uint64_t* first_packet, uint64_t* packets,
+                                   uint32_t* attempts, uint64_t* pending_bytes);
+
 enum { ZZ_DECODE_INDEXED = 1, ZZ_DECODE_DISCOVERED = 2, ZZ_DECODE_SERIAL = 3 };
 /* which path the last zz_decode_device finished on (0: none) */
 int zz_ctx_last_decode_path(const zz_ctx* ctx);

@@ -88,6 +88,8 @@ def _load():
         "zz_packet_index_device": (i32, [vp, vp, u64, pu64, vp]),
         "zz_decode_device": (i32, [vp, vp, u64, vp, u64, pu64, i32, u32, vp, u64, vp]),
         "zz_decode_batch_device": (i32, [vp, u64, vp, vp, vp, vp, vp, vp, i32, vp]),
+        "zz_decode_range_device": (i32, [vp, vp, u64, i32, u32, vp, u64, u64, u64, vp, u64, pu64, vp]),
+        "zz_ctx_last_decode_range_stats": (i32, [vp, pu64, pu64, ctypes.POINTER(u32), pu64]),
         "zz_ctx_last_decode_path": (i32, [vp]),
         "zz_ctx_last_decode_stats": (i32, [vp, pu64, ctypes.POINTER(u32)]),
         "zz_ctx_last_decode_index_device": (i32, [vp, vp, u64, pu64, vp]),
@@ -217,7 +219,7 @@ def generate_host(kind, seed, first_byte, n):
 GEN_TEXT, GEN_RANDOM, GEN_LOG, GEN_MIX = 0, 1, 2, 3
 # which path a decode finished on (Context.last_decode_path)
 DECODE_INDEXED, DECODE_DISCOVERED, DECODE_SERIAL = 1, 2, 3
-E_NOSPACE, E_UNSUPPORTED, E_DATA = -2, -5, -6
+E_NOSPACE, E_ARG, E_UNSUPPORTED, E_DATA = -2, -4, -5, -6
 
 
 class Context:
@@ -459,6 +461,33 @@ class Context:
         _check(lib.zz_decode_device(self._h, self._ptr(src), src_len, self._ptr(dst), cap, ctypes.byref(out), int(format),
                                     packet_size, ip, ne, st))
         return out.value
+
+    def decode_range(self, src, src_len, dst, cap, first, nbytes, format=Format.Zlib, packet_size=DEFAULT_PACKET, index=None,
+                     stream=None):
+        """Decoded bytes ``[first, first + nbytes)`` of the packet-mode stream ``src[:src_len]`` into ``dst`` (``cap`` bytes);
+        returns how many there are (the range is clipped at the stream's end). ``index`` is the stream's packet index (an int64
+        tensor from ``packet_index`` or ``last_decode_index``) and is required; ``packet_size`` is the one the stream was written
+        with. Only the packets the range touches and a look-back in front of them are decoded; the trailer's checksum is NOT
+        checked (it covers bytes this call never decodes). Raises ZzFlateError (E_ARG, E_DATA, E_NOSPACE, E_UNSUPPORTED)."""
+        import torch
+        if index is None:
+            raise TypeError("decode_range needs the stream's packet index (packet_index() or last_decode_index())")
+        if not isinstance(index, torch.Tensor) or index.dtype != torch.int64 or index.dim() != 1 or not index.is_contiguous():
+            raise TypeError("index must be a contiguous one-dimensional int64 tensor (as packet_index() returns)")
+        if index.device.type != "cuda" or index.device.index != self.device:
+            raise ValueError(f"index must live on this context's device (cuda:{self.device}), not {index.device}")
+        out = ctypes.c_uint64(0)
+        st = self._stream() if stream is None else stream
+        _check(lib.zz_decode_range_device(self._h, self._ptr(src), src_len, int(format), packet_size, index.data_ptr(),
+                                          index.numel(), first, nbytes, self._ptr(dst), cap, ctypes.byref(out), st))
+        return out.value
+
+    def last_decode_range_stats(self):
+        """(first packet decoded, packets decoded in the final attempt, attempts, pending bytes of the final attempt) of the last
+        successful ``decode_range``."""
+        fp, npk, pend, tries = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint32(0)
+        _check(lib.zz_ctx_last_decode_range_stats(self._h, ctypes.byref(fp), ctypes.byref(npk), ctypes.byref(tries), ctypes.byref(pend)))
+        return fp.value, npk.value, tries.value, pend.value
 
     def last_decode_path(self):
         """DECODE_INDEXED, DECODE_DISCOVERED or DECODE_SERIAL: the path the last decode finished on (0: none)."""

@@ -174,6 +174,9 @@ struct zz_ctx {
         zz_buf<unsigned long long> items_ctr;                 // zz_decode_batch_device: [0..1] failure counters, [2] the dealing counter
         zz_pin<unsigned long long> items_host;                // the two failure counters
         int last_path = 0; uint64_t last_pending = 0; uint32_t last_rounds = 0;
+        // zz_decode_range_device: the carried bytes and one batch (ZI_BIAS + B * P), the carried bytes' external bits, its stats
+        zz_buf<uint8_t> stage; zz_buf<uint32_t> xcarry;
+        struct { uint64_t first_packet = 0, packets = 0, pending = 0; uint32_t attempts = 0; } range;
         std::vector<uint64_t> last_index;                     // the index discovery recovered (zz_ctx_last_decode_index_device)
     } dec;
 };
@@ -1011,6 +1014,30 @@ static int dec_check_trailer(zz_ctx* c, const uint8_t* trailer, int format, cons
     return ZZ_OK;
 }
 
+// the container header, read on the host (it may hold a file name of any length): *hl = its length; the stream holds at
+// least the header and the trailer
+static int dec_container(const uint8_t* d_src, uint64_t src_len, int format, hipStream_t st, int64_t* hl_out)
+{
+    int64_t hl = 0;
+    if (format != ZZ_DEFLATE) {
+        uint64_t have = src_len < 4096 ? src_len : 4096;
+        std::vector<uint8_t> h;
+        for (;;) {
+            h.resize(have);
+            if (have) HIPCHK(hipMemcpyAsync(h.data(), d_src, have, hipMemcpyDeviceToHost, st));
+            HIPCHK(hipStreamSynchronize(st));
+            hl = zi_header(format, h.data(), have);
+            if (hl != -1 || have == src_len) break;
+            have = src_len - have < 3 * have ? src_len : 4 * have;
+        }
+        if (hl == -2) { set_err("the stream needs a preset dictionary (FDICT): not supported"); return ZZ_E_UNSUPPORTED; }
+        if (hl < 0) { set_err("not a valid stream of the requested format: bad container header"); return ZZ_E_DATA; }
+    }
+    if (src_len < (uint64_t)hl + (uint64_t)trailer_len(format)) { set_err("not a valid stream of the requested format: truncated"); return ZZ_E_DATA; }
+    *hl_out = hl;
+    return ZZ_OK;
+}
+
 extern "C" int zz_decode_device(zz_ctx* c, const void* d_src_v, uint64_t src_len, void* d_dst_v, uint64_t cap, uint64_t* out_len,
                                 int format, uint32_t P, const uint64_t* d_index, uint64_t entries, void* hip_stream)
 {
@@ -1029,24 +1056,9 @@ extern "C" int zz_decode_device(zz_ctx* c, const void* d_src_v, uint64_t src_len
     if (int rc = D.tot.grow(64)) return rc;
     if (int rc = D.sres.grow(1)) return rc;
     if (int rc = D.ok.grow(1)) return rc;
-    // the container header, read on the host (it may hold a file name of any length)
     int64_t hl = 0;
-    if (format != ZZ_DEFLATE) {
-        uint64_t have = src_len < 4096 ? src_len : 4096;
-        std::vector<uint8_t> h;
-        for (;;) {
-            h.resize(have);
-            if (have) HIPCHK(hipMemcpyAsync(h.data(), d_src, have, hipMemcpyDeviceToHost, st));
-            HIPCHK(hipStreamSynchronize(st));
-            hl = zi_header(format, h.data(), have);
-            if (hl != -1 || have == src_len) break;
-            have = src_len - have < 3 * have ? src_len : 4 * have;
-        }
-        if (hl == -2) { set_err("the stream needs a preset dictionary (FDICT): not supported"); return ZZ_E_UNSUPPORTED; }
-        if (hl < 0) { set_err("not a valid stream of the requested format: bad container header"); return ZZ_E_DATA; }
-    }
+    if (int rc = dec_container(d_src, src_len, format, st, &hl)) return rc;
     const uint64_t tl = (uint64_t)trailer_len(format);
-    if (src_len < (uint64_t)hl + tl) { set_err("not a valid stream of the requested format: truncated"); return ZZ_E_DATA; }
     const uint8_t* s = d_src + hl;
     const uint64_t sn = src_len - hl - tl;
     uint64_t out = 0;
@@ -1084,6 +1096,146 @@ extern "C" int zz_decode_device(zz_ctx* c, const void* d_src_v, uint64_t src_len
     if (rc) return rc;
     if (!good) { set_err("not a valid stream of the requested format: checksum or ISIZE mismatch"); return ZZ_E_DATA; }
     *out_len = out;
+    return ZZ_OK;
+}
+
+// ---- bytes [first, first + nbytes) of an indexed stream (zz_inflate.h's range kernels; the rules in zz_inflate_core.h) -----
+// One attempt: packets [kb, k1) through phase 1 and the rounds, batch by batch, onto the stage; the window's bytes of every batch
+// but the last go to d_dst at once (such a batch holds full packets only), the last batch's after the host has seen the
+// attempt's counters: *ext = external bytes inside the window (then nothing more is copied: the caller tries again),
+// *m = the bytes the range holds.
+static int dec_range_attempt(zz_ctx* c, const uint8_t* s, uint64_t sn, const uint64_t* d_index, uint64_t npk, uint32_t P,
+                             uint64_t kb, uint64_t k1, uint64_t first, uint64_t nbytes, uint8_t* dst, uint64_t cap, hipStream_t st,
+                             uint64_t* ext, uint64_t* pending, uint64_t* m)
+{
+    auto& D = c->dec;
+    const uint32_t words = ((P + 31) / 32 + 3) & ~3u;
+    uint64_t B = ZZ_INF_BATCH_BYTES / P;
+    if (B > ZZ_INF_BATCH_PACKETS) B = ZZ_INF_BATCH_PACKETS;
+    if (B > k1 - kb) B = k1 - kb;
+    if (int rc = D.stage.grow(ZI_BIAS + B * P + 16)) return rc;
+    if (int rc = D.st.grow(B * P)) return rc;
+    if (int rc = D.pend.grow(B * words)) return rc;
+    if (int rc = D.pcnt.grow(B)) return rc;
+    if (int rc = D.prem.grow(B)) return rc;
+    if (int rc = D.ends.grow(B)) return rc;
+    if (int rc = D.stat.grow(B)) return rc;
+    HIPCHK(hipMemsetAsync(D.tot, 0, 64 * sizeof(unsigned long long), st));
+    HIPCHK(hipMemsetAsync(D.xcarry, 0xFF, ZI_BIAS / 8, st));   // the first batch: whatever lies below it is external
+    const uint32_t rounds = dec_ceil_log2(B) + 2;
+    const size_t lds = (size_t)words * 4 + ZZ_INF_IBUF + ((P + 15) & ~15u);
+    const uint64_t wend = nbytes < k1 * P - first ? first + nbytes : k1 * P;       // the window's end, as far as packets go
+    for (uint64_t kf = kb; kf < k1; kf += B) {
+        const uint32_t nb = (uint32_t)(k1 - kf < B ? k1 - kf : B);
+        const uint64_t base = kf * P;
+        zz_inf_params Q;
+        Q.s = s; Q.sn = sn; Q.starts = d_index; Q.nstarts = npk + 1; Q.k0 = kf; Q.npk = nb; Q.npk_total = npk;
+        Q.P = P; Q.mode = ZZ_INF_INDEXED; Q.dst = D.stage + ZI_BIAS; Q.cap = (uint64_t)nb * P;
+        Q.st = D.st; Q.pend = D.pend; Q.words = words; Q.pcnt = D.pcnt; Q.prem = D.prem; Q.ends = D.ends; Q.stat = D.stat; Q.tot = D.tot;
+        Q.ebase = kf;
+        hipLaunchKernelGGL(k_inflate_packets_range, dim3(nb), dim3(ZZ_INF_THREADS), lds, st, Q);
+        zz_res_params R{ D.stage, ZI_BIAS, P, nb, words, D.st, D.pend, D.pcnt, D.prem, D.tot };
+        zz_res_range X{ D.xcarry, (int64_t)first - (int64_t)base, (int64_t)wend - (int64_t)base };
+        for (uint32_t r = 1; r <= rounds; ++r) hipLaunchKernelGGL(k_inflate_resolve_range, dim3(nb), dim3(ZZ_INF_RES_THREADS), 0, st, R, X, r);
+        // this batch's share of the window: stream bytes [lo, hi)
+        const uint64_t lo = first > base ? first : base;
+        uint64_t hi = base + (uint64_t)nb * P < wend ? base + (uint64_t)nb * P : wend;
+        const bool last = kf + nb == k1;
+        if (last) {
+            unsigned long long tot[64];
+            uint32_t stat = 0;
+            HIPCHK(hipGetLastError());
+            HIPCHK(hipMemcpyAsync(tot, D.tot, sizeof tot, hipMemcpyDeviceToHost, st));
+            HIPCHK(hipMemcpyAsync(&stat, D.stat + (nb - 1), 4, hipMemcpyDeviceToHost, st));
+            HIPCHK(hipStreamSynchronize(st));
+            if (tot[63] != 0) { set_err("not a valid stream of the requested format: " + std::to_string(tot[63]) + " of the range's packets do not decode as the index says"); return ZZ_E_DATA; }
+            if (tot[1 + rounds] != 0) { set_err("pending bytes left unresolved"); return ZZ_E_DATA; }   // (cannot happen: the rounds suffice for any chain)
+            *ext = tot[61]; *pending = tot[0];
+            uint64_t have = nbytes;                                 // bytes of the stream from `first` on, if its end is in sight
+            if (k1 == npk) { const uint64_t L = (npk - 1) * (uint64_t)P + (stat >> 3); have = L > first ? L - first : 0; }
+            *m = nbytes < have ? nbytes : have;
+            if (*ext != 0) return ZZ_OK;
+            if (hi > first + *m) hi = first + *m;
+        }
+        if (hi > first && hi - first > cap) hi = first + cap;                     // nothing past cap, whatever the call's result will be
+        if (hi > lo) {
+            const uint64_t n = hi - lo;
+            uint64_t g = (n / 16 + 255) / 256;
+            if (g > 4096) g = 4096;
+            if (g == 0) g = 1;
+            hipLaunchKernelGGL(k_inflate_range_copy, dim3((uint32_t)g), dim3(256), 0, st, D.stage + ZI_BIAS + (lo - base), dst + (lo - first), n);
+        }
+        if (!last) hipLaunchKernelGGL(k_inflate_range_carry, dim3(ZI_BIAS / 256), dim3(256), 0, st, D.stage.p, (uint64_t)nb * P, P, words,
+                                      D.st.p, D.pend.p, D.pcnt.p, D.xcarry.p);
+    }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(st));
+    return ZZ_OK;
+}
+
+extern "C" int zz_decode_range_device(zz_ctx* c, const void* d_src_v, uint64_t src_len, int format, uint32_t P,
+                                      const uint64_t* d_index, uint64_t entries, uint64_t first, uint64_t nbytes,
+                                      void* d_dst_v, uint64_t cap, uint64_t* out_len, void* hip_stream)
+{
+    if (!c || !d_src_v || !d_index || !out_len) { set_err("null argument"); return ZZ_E_ARG; }
+    *out_len = 0;
+    if (P < 1 || P > ZZ_MAX_PACKET_SIZE) { set_err("packet size must be 1..32768"); return ZZ_E_ARG; }
+    if (format < ZZ_ZLIB || format > ZZ_DEFLATE) { set_err("format must be ZZ_ZLIB, ZZ_GZIP or ZZ_DEFLATE"); return ZZ_E_ARG; }
+    if (entries < 2) { set_err("the index needs at least two entries (packets + 1)"); return ZZ_E_ARG; }
+    const uint64_t npk = entries - 1;
+    if (first / P >= npk) { set_err("the range starts behind the index's last packet"); return ZZ_E_ARG; }
+    if (first + nbytes < first) { set_err("first + nbytes overflows"); return ZZ_E_ARG; }
+    if (!d_dst_v && cap) { set_err("null buffer"); return ZZ_E_ARG; }
+    if (nbytes == 0) return ZZ_OK;                                  // nothing to do: the context is not looked at
+    if (call_pending(c)) return ZZ_E_ARG;
+    const uint8_t* d_src = (const uint8_t*)d_src_v;
+    uint8_t* d_dst = (uint8_t*)d_dst_v;
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t st = (hipStream_t)hip_stream;
+    auto& D = c->dec;
+    if (int rc = D.tot.grow(64)) return rc;
+    if (int rc = D.xcarry.grow(ZI_BIAS / 32)) return rc;
+    int64_t hl = 0;
+    if (int rc = dec_container(d_src, src_len, format, st, &hl)) return rc;
+    const uint8_t* s = d_src + hl;
+    const uint64_t sn = src_len - hl - (uint64_t)trailer_len(format);
+    uint64_t ends[2];
+    HIPCHK(hipMemcpyAsync(&ends[0], d_index, 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(&ends[1], d_index + npk, 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (ends[0] != 0 || ends[1] != sn) { set_err("the index does not describe this stream: its ends are not the DEFLATE bytes' ends"); return ZZ_E_DATA; }
+    const uint64_t k0 = first / P;
+    const uint64_t lastk = (first + nbytes - 1) / P;
+    const uint64_t k1 = lastk + 1 < npk ? lastk + 1 : npk;
+    uint64_t h = zi_range_first_lookback(P, k0);
+    for (uint32_t tries = 1;; ++tries) {
+        const uint64_t kb = k0 - h;
+        uint64_t ext = 0, pending = 0, m = 0;
+        if (int rc = dec_range_attempt(c, s, sn, d_index, npk, P, kb, k1, first, nbytes, d_dst, cap, st, &ext, &pending, &m)) return rc;
+        if (ext != 0) {
+            if (kb == 0) { set_err("not a valid stream of the requested format: a reference in front of the stream"); return ZZ_E_DATA; }   // (phase 1 refuses these)
+            h = zi_range_next_lookback(h, k0);
+            continue;
+        }
+        if (m > cap) {
+            *out_len = ~0ull;
+            set_err("destination too small for the range (" + std::to_string(m) + " bytes)");
+            return ZZ_E_NOSPACE;
+        }
+        D.range.first_packet = kb; D.range.packets = k1 - kb; D.range.attempts = tries; D.range.pending = pending;
+        *out_len = m;
+        return ZZ_OK;
+    }
+}
+
+extern "C" int zz_ctx_last_decode_range_stats(const zz_ctx* c, uint64_t* first_packet, uint64_t* packets, uint32_t* attempts,
+                                              uint64_t* pending_bytes)
+{
+    if (!c) { set_err("null context"); return ZZ_E_ARG; }
+    if (first_packet) *first_packet = c->dec.range.first_packet;
+    if (packets) *packets = c->dec.range.packets;
+    if (attempts) *attempts = c->dec.range.attempts;
+    if (pending_bytes) *pending_bytes = c->dec.range.pending;
     return ZZ_OK;
 }
 

@@ -117,7 +117,9 @@ __device__ __forceinline__ uint32_t inf_wave_sum(uint32_t v)
 }
 
 // dynamic LDS: bitmap words * 4 + ZZ_INF_IBUF + P rounded up to 16
-__global__ __launch_bounds__(ZZ_INF_THREADS) void k_inflate_packets(zz_inf_params Q)
+// RANGE (k_inflate_packets_range, zz_decode_range_device): Q.dst is the stage of this batch and holds npk * P bytes, so packet b's
+// bytes go to b * P -- where the pointers count from -- and always fit; everything else, `abs` and the checks included, is the same.
+template <bool RANGE> __device__ __forceinline__ void inflate_packets_body(zz_inf_params Q)
 {
     extern __shared__ uint4 inf_dyn[];
     __shared__ zi_tables S;
@@ -158,12 +160,12 @@ __global__ __launch_bounds__(ZZ_INF_THREADS) void k_inflate_packets(zz_inf_param
     }
     // a packet that decodes but does not fit is not written: the call's result is ZZ_E_NOSPACE if it is a true packet, and
     // discovery can still walk over it if it is not
-    const bool fits = !R.err && abs <= Q.cap && Q.cap - abs >= R.out;
+    const bool fits = !R.err && (RANGE || (abs <= Q.cap && Q.cap - abs >= R.out));
     np = inf_wave_sum(np);
     __syncthreads();
     if (fits) {
         // the window to its place (16-byte stores where the destination allows them)
-        uint8_t* d = Q.dst + abs;
+        uint8_t* d = Q.dst + (RANGE ? (uint64_t)b * Q.P : abs);
         const uint32_t nb = (uint32_t)R.out;
         if ((((uintptr_t)d) & 15) == 0) {
             const uint32_t n16 = nb >> 4;
@@ -184,6 +186,8 @@ __global__ __launch_bounds__(ZZ_INF_THREADS) void k_inflate_packets(zz_inf_param
         else if (!fits) atomicAdd(&Q.tot[62], 1ull);
     }
 }
+__global__ __launch_bounds__(ZZ_INF_THREADS) void k_inflate_packets(zz_inf_params Q) { inflate_packets_body<false>(Q); }
+__global__ __launch_bounds__(ZZ_INF_THREADS) void k_inflate_packets_range(zz_inf_params Q) { inflate_packets_body<true>(Q); }
 
 // phase 2, round `round` (1-based) over the batch [k0, k0 + npk); `base` = absolute output position of its first byte
 struct zz_res_params {
@@ -191,27 +195,34 @@ struct zz_res_params {
     uint32_t* st; const uint32_t* pend; const uint32_t* pcnt; uint32_t* prem;
     unsigned long long* tot;
 };
-__global__ __launch_bounds__(ZZ_INF_RES_THREADS) void k_inflate_resolve(zz_res_params Q, uint32_t round)
+// what the range form (k_inflate_resolve_range) knows on top: dst is the stage -- ZI_BIAS carried bytes of the batch before, then
+// this batch's -- and base = ZI_BIAS, so a target below the batch base reads a carried byte; `carry` has one bit per carried
+// byte: external (zz_inflate_core.h). Bytes that turn external inside [wlo, whi) (relative to the batch base) are counted in tot[61].
+struct zz_res_range { const uint32_t* carry; int64_t wlo, whi; };
+template <bool RANGE> __device__ __forceinline__ void inflate_resolve_body(zz_res_params Q, zz_res_range X, uint32_t round)
 {
     __shared__ uint32_t red[ZZ_INF_RES_THREADS / ZZ_WAVE];
     const uint32_t k = blockIdx.x;
     if (Q.pcnt[k] == 0 || Q.prem[k] == 0) return;         // uniform per workgroup
     const uint32_t t = threadIdx.x;
-    uint32_t left = 0;
+    uint32_t left = 0, nx = 0;
     for (uint32_t q = t; q < Q.P; q += ZZ_INF_RES_THREADS) {
         if (!((Q.pend[(uint64_t)k * Q.words + (q >> 5)] >> (q & 31)) & 1u)) continue;
         const uint64_t x = (uint64_t)k * Q.P + q;
         const uint32_t s = Q.st[x];
-        if (s >> 27) continue;                            // final since an earlier round
+        if (s >> 27) continue;                            // final (or external) since an earlier round
         const int64_t y = (int64_t)(s & ZI_PTR_MASK) - (int64_t)ZI_BIAS;
         bool fin = y < 0;                                 // an earlier batch: final (phase 1 refused anything in front of the stream)
-        if (!fin) {
+        bool ext = false;
+        if (RANGE && fin) { ext = zi_range_external(y, zi_view<const uint32_t>{ X.carry, ZI_BIAS / 32 }); fin = !ext; }
+        if (y >= 0) {
             const uint64_t ky = (uint64_t)y / Q.P, qy = (uint64_t)y % Q.P;
             fin = Q.pcnt[ky] == 0 || !((Q.pend[ky * Q.words + (qy >> 5)] >> (qy & 31)) & 1u);
             if (!fin) {
                 const uint32_t sy = Q.st[y];
                 const uint32_t ry = sy >> 27;
-                if (ry != 0 && ry < round) fin = true;      // final before this round began: its byte is in place
+                if (RANGE && ry == ZI_ROUND_EXTERNAL) ext = true;   // it stays external, whenever the target was marked
+                else if (ry != 0 && ry < round) fin = true; // final before this round began: its byte is in place
                 else { Q.st[x] = sy & ZI_PTR_MASK; ++left; } // adopt its pointer (the old one or this round's: both lead there)
             }
         }
@@ -219,6 +230,14 @@ __global__ __launch_bounds__(ZZ_INF_RES_THREADS) void k_inflate_resolve(zz_res_p
             Q.dst[Q.base + x] = Q.dst[(int64_t)Q.base + y];
             Q.st[x] = (s & ZI_PTR_MASK) | (round << 27);
         }
+        if (RANGE && ext) {
+            Q.st[x] = (s & ZI_PTR_MASK) | (ZI_ROUND_EXTERNAL << 27);
+            if ((int64_t)x >= X.wlo && (int64_t)x < X.whi) ++nx;
+        }
+    }
+    if (RANGE) {
+        nx = inf_wave_sum(nx);
+        if ((t & 63) == 0 && nx) atomicAdd(&Q.tot[61], (unsigned long long)nx);
     }
     left = inf_wave_sum(left);
     if ((t & 63) == 0) red[t >> 6] = left;
@@ -229,6 +248,48 @@ __global__ __launch_bounds__(ZZ_INF_RES_THREADS) void k_inflate_resolve(zz_res_p
         Q.prem[k] = sum;
         if (sum) atomicAdd(&Q.tot[1 + round], (unsigned long long)sum);
     }
+}
+__global__ __launch_bounds__(ZZ_INF_RES_THREADS) void k_inflate_resolve(zz_res_params Q, uint32_t round)
+{
+    inflate_resolve_body<false>(Q, zz_res_range{ nullptr, 0, 0 }, round);
+}
+__global__ __launch_bounds__(ZZ_INF_RES_THREADS) void k_inflate_resolve_range(zz_res_params Q, zz_res_range X, uint32_t round)
+{
+    inflate_resolve_body<true>(Q, X, round);
+}
+
+// range decode, between two batches: the last ZI_BIAS bytes of the finished batch (stage[ZI_BIAS + n - ZI_BIAS + i]) move to the
+// front of the stage, and next[i / 32] says which of them are external. One thread per byte: ZI_BIAS / 256 workgroups of 256.
+// n >= ZI_BIAS is the caller's (a batch that is not the last is full): the bytes read and the bytes written do not overlap.
+// `next` may be the bitmap the batch's rounds read: nothing here reads it.
+__global__ __launch_bounds__(256) void k_inflate_range_carry(uint8_t* stage, uint64_t n, uint32_t P, uint32_t words, const uint32_t* st,
+                                                             const uint32_t* pend, const uint32_t* pcnt, uint32_t* next)
+{
+    const uint32_t i = blockIdx.x * 256 + threadIdx.x;       // < ZI_BIAS
+    const uint64_t x = n - ZI_BIAS + i;
+    stage[i] = stage[(uint64_t)ZI_BIAS + x];
+    const uint64_t k = x / P; const uint32_t q = (uint32_t)(x % P);
+    const bool ext = pcnt[k] != 0 && ((pend[k * words + (q >> 5)] >> (q & 31)) & 1u) && (st[x] >> 27) == ZI_ROUND_EXTERNAL;
+    const unsigned long long m = __ballot(ext);
+    if ((threadIdx.x & 63) == 0) { next[i >> 5] = (uint32_t)m; next[(i >> 5) + 1] = (uint32_t)(m >> 32); }
+}
+
+// range decode: n bytes from the stage to the caller's destination; 16-byte stores once the destination is aligned (the source
+// is read as it lies). Grid-stride, any launch shape.
+__global__ __launch_bounds__(256) void k_inflate_range_copy(const uint8_t* src, uint8_t* dst, uint64_t n)
+{
+    const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x, nt = (uint64_t)gridDim.x * blockDim.x;
+    uint64_t head = (16 - ((uintptr_t)dst & 15)) & 15;
+    if (head > n) head = n;
+    const uint64_t n16 = (n - head) >> 4;
+    if (t < head) dst[t] = src[t];
+    for (uint64_t i = t; i < n16; i += nt) {
+        uint4 v;
+        __builtin_memcpy(&v, src + head + (i << 4), 16);
+        *(uint4*)(dst + head + (i << 4)) = v;
+    }
+    const uint64_t done = head + (n16 << 4);
+    if (t < n - done) dst[done + t] = src[done + t];
 }
 
 // discovery: every `01 00 FE FF` in s[0, sn) gives the candidate start i + 5 (if that is inside the stream). The

@@ -397,6 +397,40 @@ struct zi_or_plain {
     ZZ_HD void operator()(zi_view<uint32_t>& m, uint64_t q) const { m[q >> 5] |= 1u << (q & 31); }
 };
 
+// ---- a range of an indexed stream (zz_decode_range_device; tests/cxx/inflate_range_harness.cpp runs the same rules) ----
+// Bytes [first, first + n) need the packets [k0, k1) that hold them and `h` look-back packets in front: phase 1 runs on
+// [kb, k1), kb = k0 - h, with pointers relative to kb * P. A pending byte whose chain leaves the decoded packets at the front is
+// EXTERNAL: nothing there is known, so it is not resolved, and a byte that adopts an external pointer is external too (the pointer
+// word's round field holds ZI_ROUND_EXTERNAL, which no round number reaches). If an external byte lies inside the requested
+// window and kb > 0, the call repeats with a longer look-back; with kb == 0 nothing can be external.
+//
+// Batches: behind the first batch, a pointer below the batch base reaches at most ZI_BIAS bytes into the batch before it. Those
+// bytes are carried in front of the batch's bytes (so `base + y` with y < 0 reads them), and one bit per carried byte says whether
+// it is external; for the first batch of an attempt every bit is set.
+#define ZI_ROUND_EXTERNAL 31u
+// the look-back of the first attempt: one backward extension (levels 2, 3: a match found inside the packet grows backward by at
+// most 258 bytes, so its source starts at most 258 bytes in front of the packet). Levels 0 and 1 with cold packets never
+// point in front of a packet, so for them these packets are decoded for nothing -- one or two, beside the range's own.
+ZZ_HD inline uint64_t zi_range_first_lookback(uint32_t P, uint64_t k0)
+{
+    const uint64_t h = (258u + (uint64_t)P - 1) / P;
+    return h < k0 ? h : k0;
+}
+// the next look-back after `h` was not enough: four times as many packets, all of them (k0) at the most. A failed attempt costs
+// the time one wavefront needs for a packet (milliseconds) while further look-back packets decode beside it on idle CUs, so the
+// step is generous; the attempts' work is a geometric series, at most 4/3 of the last one's look-back.
+ZZ_HD inline uint64_t zi_range_next_lookback(uint64_t h, uint64_t k0)
+{
+    if (h >= k0 / 4) return k0;
+    return h ? 4 * h : 1;
+}
+// the target y (relative to the batch base, y < 0: below it, at most ZI_BIAS below) of a pending byte: is it external?
+ZZ_HD inline bool zi_range_external(int64_t y, const zi_view<const uint32_t>& carry)
+{
+    const uint64_t c = (uint64_t)(y + (int64_t)ZI_BIAS);
+    return ((carry[c >> 5] >> (c & 31)) & 1u) != 0;
+}
+
 // ---- the container --------------------------------------------------------------------------------------------
 // Header length of a zlib / gzip / raw stream held in h[0, n); <0: -1 not a valid header (or truncated), -2 preset dictionary.
 ZZ_HD inline int64_t zi_header(int format, const uint8_t* hp, uint64_t n)
