@@ -287,6 +287,46 @@ int zz_decode_range_device(zz_ctx* ctx, const void* d_src, uint64_t src_len, int
 int zz_ctx_last_decode_range_stats(const zz_ctx* ctx, uint64_t* first_packet, uint64_t* packets,
                                    uint32_t* attempts, uint64_t* pending_bytes);
 
+/* Many reads of one stored stream in one call: read r = decoded bytes [d_firsts[r], d_firsts[r] + d_nbytes[r]) into
+ * d_dsts[r][0, d_caps[r]), exactly what zz_decode_range_device gives that read alone, but the nranges reads share one set of
+ * launches. The stream, its index, format and packet_size are as zz_decode_range_device takes them; the six arrays of nranges
+ * entries live in DEVICE memory (d_status may be NULL). With L the stream's decoded length, d_out_lens[r] = m = min(nbytes,
+ * L - first) (0 for a start behind the end inside the last packet's span, 0 with ZZ_OK for nbytes == 0); nothing is written
+ * outside d_dsts[r][0, min(m, cap)). A read whose status is not ZZ_OK has d_out_lens[r] = ~0 and the first cap bytes of its
+ * destination are unspecified; it leaves every other read complete.
+ *   d_status[r]: ZZ_OK; ZZ_E_ARG: first >= (entries - 1) * packet_size, or first + nbytes overflows (the arrays live on the
+ *     device, so these are refused there); ZZ_E_NOSPACE: m > cap; ZZ_E_DATA: a packet this read decodes is not what the index
+ *     says or refers to bytes in front of the stream; ZZ_E_UNSUPPORTED: the read's packets plus look-back exceed one batch (64 MiB
+ *     of output, 2^18 packets), at first or after the look-back has grown -- such a read belongs to zz_decode_range_device,
+ *     which carries bytes from batch to batch; this call does not.
+ *   Returns ZZ_OK when every read is ZZ_OK; otherwise ZZ_E_DATA if any read is, else ZZ_E_UNSUPPORTED, else ZZ_E_ARG, else
+ *     ZZ_E_NOSPACE.
+ *   ZZ_E_ARG, before anything is launched: a null context, source, index, d_firsts, d_nbytes, d_dsts, d_caps or d_out_lens;
+ *     packet_size outside 1..32768; a format outside 0..2; entries < 2; nranges > 2^31 - 1; an unfinished zz_encode_device_async
+ *     on the context. nranges == 0 with arguments that pass returns ZZ_OK at once.
+ *   Failures of the call itself, after the host reads zz_decode_range_device makes: a bad container header (ZZ_E_DATA), a preset
+ *     dictionary (ZZ_E_UNSUPPORTED), index[0] != 0 or index[last] not the stream's DEFLATE length (ZZ_E_DATA); every d_status[r]
+ *     is then that code and every d_out_lens[r] = ~0.
+ * Reads may overlap each other (each decodes its own copy of the packets); destinations that overlap are the caller's error.
+ * NOT CHECKED: the trailer's checksum (Adler-32, CRC-32, ISIZE), for zz_decode_range_device's reason: it covers bytes this call
+ * never decodes.
+ * How: every read's packets and look-back form a segment on a stage; the segments of many reads go through phase 1 and the
+ * rounds together, a wave of at most two batches of packets at a time; a read that still points in front of its segment comes
+ * back in the next attempt with four times the look-back, the others are finished. Per attempt the host
+ * reads a fixed number of words, whatever nranges is.
+ * Workspace: at most twice zz_decode_range_device's (a wave holds fewer than two batches of packets: per packet its bytes, four
+ * bytes of pointer per byte, the bitmap, 44 bytes) plus 48 bytes per read; sized by the call's largest wave. Synchronous.
+ * Leaves the context's "last call", "last decode" and zz_ctx_last_decode_range_stats state alone. */
+int zz_decode_ranges_device(zz_ctx* ctx, const void* d_src, uint64_t src_len, int format, uint32_t packet_size,
+                            const uint64_t* d_index, uint64_t entries,
+                            uint64_t nranges, const uint64_t* d_firsts, const uint64_t* d_nbytes,
+                            void* const* d_dsts, const uint64_t* d_caps,
+                            uint64_t* d_out_lens, int32_t* d_status, void* hip_stream);
+/* what the last zz_decode_ranges_device did: stage packets decoded, summed over its attempts; the attempts; the reads that
+ * needed more than one attempt; the waves, summed over its attempts */
+int zz_ctx_last_decode_ranges_stats(const zz_ctx* ctx, uint64_t* packets, uint32_t* attempts,
+                                    uint64_t* retried_ranges, uint32_t* waves);
+
 enum { ZZ_DECODE_INDEXED = 1, ZZ_DECODE_DISCOVERED = 2, ZZ_DECODE_SERIAL = 3 };
 /* which path the last zz_decode_device finished on (0: none) */
 int zz_ctx_last_decode_path(const zz_ctx* ctx);

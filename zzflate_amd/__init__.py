@@ -90,6 +90,8 @@ def _load():
         "zz_decode_batch_device": (i32, [vp, u64, vp, vp, vp, vp, vp, vp, i32, vp]),
         "zz_decode_range_device": (i32, [vp, vp, u64, i32, u32, vp, u64, u64, u64, vp, u64, pu64, vp]),
         "zz_ctx_last_decode_range_stats": (i32, [vp, pu64, pu64, ctypes.POINTER(u32), pu64]),
+        "zz_decode_ranges_device": (i32, [vp, vp, u64, i32, u32, vp, u64, u64, vp, vp, vp, vp, vp, vp, vp]),
+        "zz_ctx_last_decode_ranges_stats": (i32, [vp, pu64, ctypes.POINTER(u32), pu64, ctypes.POINTER(u32)]),
         "zz_ctx_last_decode_path": (i32, [vp]),
         "zz_ctx_last_decode_stats": (i32, [vp, pu64, ctypes.POINTER(u32)]),
         "zz_ctx_last_decode_index_device": (i32, [vp, vp, u64, pu64, vp]),
@@ -488,6 +490,57 @@ class Context:
         fp, npk, pend, tries = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint32(0)
         _check(lib.zz_ctx_last_decode_range_stats(self._h, ctypes.byref(fp), ctypes.byref(npk), ctypes.byref(tries), ctypes.byref(pend)))
         return fp.value, npk.value, tries.value, pend.value
+
+    def decode_ranges(self, src, src_len, firsts, nbytes, dsts, caps=None, format=Format.Zlib, packet_size=DEFAULT_PACKET,
+                      index=None, stream=None):
+        """Many reads of one stored stream in one call: read r = decoded bytes ``[firsts[r], firsts[r] + nbytes[r])`` of the
+        packet-mode stream ``src[:src_len]`` into ``dsts[r]``, what ``decode_range`` gives it alone. ``dsts`` are items as
+        ``decode_batch`` takes them; ``caps`` defaults to ``min(nbytes[r], destination size)``; ``index`` is required. Returns
+        ``(lens, status)``: ``lens[r]`` the bytes read (clipped at the stream's end) or ``None``, ``status[r]`` 0, E_ARG,
+        E_NOSPACE, E_DATA or E_UNSUPPORTED -- a read's own failure does not raise and leaves the others complete; a failure of
+        the call (arguments, container header, an index that is not this stream's) raises. The trailer's checksum is NOT
+        checked."""
+        import torch
+        if index is None:
+            raise TypeError("decode_ranges needs the stream's packet index (packet_index() or last_decode_index())")
+        if not isinstance(index, torch.Tensor) or index.dtype != torch.int64 or index.dim() != 1 or not index.is_contiguous():
+            raise TypeError("index must be a contiguous one-dimensional int64 tensor (as packet_index() returns)")
+        if index.device.type != "cuda" or index.device.index != self.device:
+            raise ValueError(f"index must live on this context's device (cuda:{self.device}), not {index.device}")
+        k = len(firsts)
+        if len(nbytes) != k or len(dsts) != k:
+            raise ValueError(f"{k} starts but {len(nbytes)} lengths and {len(dsts)} destinations")
+        if caps is not None and len(caps) != k:
+            raise ValueError(f"{len(caps)} capacities for {k} reads")
+        if k == 0:
+            return [], []
+        d = [self._item(t) for t in dsts]
+        cp = [min(int(n), nb) for n, (_, nb) in zip(nbytes, d)] if caps is None else [int(c) for c in caps]
+        dev = f"cuda:{self.device}"
+        mask = (1 << 64) - 1
+
+        def i64(v):                                    # uint64 values travel as the int64 of the same bits
+            v = int(v) & mask
+            return v - (1 << 64) if v >> 63 else v
+        table = torch.tensor([[i64(v) for v in firsts], [i64(v) for v in nbytes], [i64(p) for p, _ in d], [i64(v) for v in cp]],
+                             dtype=torch.int64).to(dev)
+        out = torch.empty(k, dtype=torch.int64, device=dev)
+        status = torch.empty(k, dtype=torch.int32, device=dev)
+        st = self._stream() if stream is None else stream
+        rc = lib.zz_decode_ranges_device(self._h, self._ptr(src), src_len, int(format), packet_size, index.data_ptr(), index.numel(),
+                                         k, table[0].data_ptr(), table[1].data_ptr(), table[2].data_ptr(), table[3].data_ptr(),
+                                         out.data_ptr(), status.data_ptr(), st)
+        if rc != 0 and not lib.zz_last_error().startswith(b"reads: "):
+            _check(rc)                                 # the call itself failed (the library words a read's own failure "reads: ...")
+        status = status.cpu().tolist()
+        return [None if sv != 0 else v for v, sv in zip(out.cpu().tolist(), status)], status
+
+    def last_decode_ranges_stats(self):
+        """(stage packets decoded over all attempts, attempts, reads that needed more than one attempt, waves) of the last
+        ``decode_ranges``."""
+        npk, retried, tries, waves = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint32(0), ctypes.c_uint32(0)
+        _check(lib.zz_ctx_last_decode_ranges_stats(self._h, ctypes.byref(npk), ctypes.byref(tries), ctypes.byref(retried), ctypes.byref(waves)))
+        return npk.value, tries.value, retried.value, waves.value
 
     def last_decode_path(self):
         """DECODE_INDEXED, DECODE_DISCOVERED or DECODE_SERIAL: the path the last decode finished on (0: none)."""

@@ -30,6 +30,7 @@
 #include "zz_datagen.h"
 #include "zz_verify.h"
 #include "zz_inflate.h"
+#include "zz_inflate_ranges.h"
 #include "zz_batch.h"
 
 using namespace zz;
@@ -177,6 +178,10 @@ struct zz_ctx {
         // zz_decode_range_device: the carried bytes and one batch (ZI_BIAS + B * P), the carried bytes' external bits, its stats
         zz_buf<uint8_t> stage; zz_buf<uint32_t> xcarry;
         struct { uint64_t first_packet = 0, packets = 0, pending = 0; uint32_t attempts = 0; } range;
+        // zz_decode_ranges_device: per read its record, per stage packet of a wave its descriptor, what the host reads per attempt
+        zz_buf<zi_read> rng_reads; zz_buf<zi_read_desc> rng_desc;
+        zz_buf<zz_rng_totals> rng_tot; zz_pin<zz_rng_totals> rng_host;
+        struct { uint64_t packets = 0, retried = 0; uint32_t attempts = 0, waves = 0; } ranges;
         std::vector<uint64_t> last_index;                     // the index discovery recovered (zz_ctx_last_decode_index_device)
     } dec;
 };
@@ -1236,6 +1241,130 @@ extern "C" int zz_ctx_last_decode_range_stats(const zz_ctx* c, uint64_t* first_p
     if (packets) *packets = c->dec.range.packets;
     if (attempts) *attempts = c->dec.range.attempts;
     if (pending_bytes) *pending_bytes = c->dec.range.pending;
+    return ZZ_OK;
+}
+
+// ---- many reads of one indexed stream in one call (zz_inflate_ranges.h; the rules in zz_inflate_core.h) -------------------
+// A read's own failure is worded "reads: ..." in zz_last_error (the Python layer tells it from a failure of the call by that).
+// Per attempt: the plan, one wait for its totals and wave table, then per wave descriptors, phase 1, the rounds, the verdict and
+// the copy, nothing of which the host waits for; the next attempt's plan finds what is left.
+extern "C" int zz_decode_ranges_device(zz_ctx* c, const void* d_src_v, uint64_t src_len, int format, uint32_t P,
+                                       const uint64_t* d_index, uint64_t entries,
+                                       uint64_t nranges, const uint64_t* d_firsts, const uint64_t* d_nbytes,
+                                       void* const* d_dsts, const uint64_t* d_caps,
+                                       uint64_t* d_out_lens, int32_t* d_status, void* hip_stream)
+{
+    if (!c || !d_src_v || !d_index || !d_firsts || !d_nbytes || !d_dsts || !d_caps || !d_out_lens) { set_err("null argument"); return ZZ_E_ARG; }
+    if (P < 1 || P > ZZ_MAX_PACKET_SIZE) { set_err("packet size must be 1..32768"); return ZZ_E_ARG; }
+    if (format < ZZ_ZLIB || format > ZZ_DEFLATE) { set_err("format must be ZZ_ZLIB, ZZ_GZIP or ZZ_DEFLATE"); return ZZ_E_ARG; }
+    if (entries < 2) { set_err("the index needs at least two entries (packets + 1)"); return ZZ_E_ARG; }
+    if (nranges > 0x7fffffffull) { set_err("at most 2^31 - 1 reads per call"); return ZZ_E_ARG; }
+    if (nranges == 0) return ZZ_OK;                                 // nothing to do: the context is not looked at
+    if (call_pending(c)) return ZZ_E_ARG;
+    const uint64_t npk = entries - 1;
+    const uint8_t* d_src = (const uint8_t*)d_src_v;
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t st = (hipStream_t)hip_stream;
+    auto& D = c->dec;
+    D.ranges.packets = 0; D.ranges.retried = 0; D.ranges.attempts = 0; D.ranges.waves = 0;
+    // a failure of the call itself: every read gets the code
+    auto fail_all = [&](int code) -> int {
+        hipLaunchKernelGGL(k_ranges_fill, dim3((uint32_t)std::min<uint64_t>((nranges + 255) / 256, 4096)), dim3(256), 0, st, d_out_lens, d_status,
+                           nranges, (int32_t)code);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipStreamSynchronize(st));
+        return code;
+    };
+    int64_t hl = 0;
+    if (int rc = dec_container(d_src, src_len, format, st, &hl)) {
+        if (rc == ZZ_E_DATA || rc == ZZ_E_UNSUPPORTED) return fail_all(rc);
+        return rc;
+    }
+    const uint8_t* s = d_src + hl;
+    const uint64_t sn = src_len - hl - (uint64_t)trailer_len(format);
+    uint64_t ends[2];
+    HIPCHK(hipMemcpyAsync(&ends[0], d_index, 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(&ends[1], d_index + npk, 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (ends[0] != 0 || ends[1] != sn) {
+        set_err("the index does not describe this stream: its ends are not the DEFLATE bytes' ends");
+        return fail_all(ZZ_E_DATA);
+    }
+    if (int rc = D.tot.grow(64)) return rc;
+    if (int rc = D.rng_reads.grow(nranges)) return rc;
+    if (int rc = D.rng_tot.grow(1)) return rc;
+    if (int rc = D.rng_host.grow(1)) return rc;
+    const uint32_t words = ((P + 31) / 32 + 3) & ~3u;
+    uint64_t B = ZZ_INF_BATCH_BYTES / P;
+    if (B > ZZ_INF_BATCH_PACKETS) B = ZZ_INF_BATCH_PACKETS;
+    zz_rng_params Q{ d_firsts, d_nbytes, (uint8_t* const*)d_dsts, d_caps, d_out_lens, d_status, nranges, npk, P, B, B, D.rng_reads, D.rng_tot };
+    const size_t lds = (size_t)words * 4 + ZZ_INF_IBUF + ((P + 15) & ~15u);
+    const zz_rng_totals& T = *D.rng_host.p;
+    for (uint32_t tries = 1;; ++tries) {
+        hipLaunchKernelGGL(k_ranges_plan, dim3(1), dim3(ZZ_RNG_PLAN_THREADS), 0, st, Q, tries == 1 ? 1 : 0);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(D.rng_host.p, D.rng_tot.p, sizeof(zz_rng_totals), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        if (T.nwaves == 0) {
+            if (T.deferred != 0) { set_err("range plan made no progress"); return ZZ_E_HIP; }    // (cannot happen: wave 0 always takes a segment)
+            break;
+        }
+        D.ranges.attempts = tries; D.ranges.packets += T.stage_end;
+        const uint32_t rounds = dec_ceil_log2(T.longest) + 2;
+        // the workspace follows the attempt's largest wave (nothing is grown while a wave's kernels run)
+        uint64_t big = 0, prev = T.stage_end;
+        for (uint64_t w = T.nwaves; w-- > 0;) {
+            if (T.wave_first[w] == ~0ull) continue;
+            big = std::max<uint64_t>(big, prev - T.wave_first[w]);
+            prev = T.wave_first[w];
+        }
+        if (int rc = D.stage.grow(big * P + 16)) return rc;
+        if (int rc = D.st.grow(big * P)) return rc;
+        if (int rc = D.pend.grow(big * words)) return rc;
+        if (int rc = D.pcnt.grow(big)) return rc;
+        if (int rc = D.prem.grow(big)) return rc;
+        if (int rc = D.ends.grow(big)) return rc;
+        if (int rc = D.stat.grow(big)) return rc;
+        if (int rc = D.rng_desc.grow(big)) return rc;
+        for (uint64_t w = 0; w < T.nwaves; ++w) {
+            if (T.wave_first[w] == ~0ull) continue;                 // (a segment longer than a wave's capacity went over it)
+            uint64_t nx = w + 1;
+            while (nx < T.nwaves && T.wave_first[nx] == ~0ull) ++nx;
+            const uint64_t g0 = T.wave_first[w], g1 = nx < T.nwaves ? T.wave_first[nx] : T.stage_end;
+            const uint64_t rlo = T.wave_read[w], rhi = nx < T.nwaves ? T.wave_read[nx] : nranges;
+            const uint32_t nb = (uint32_t)(g1 - g0);                // < 2 * B, <= big
+            ++D.ranges.waves;
+            hipLaunchKernelGGL(k_ranges_desc, dim3((nb + 255) / 256), dim3(256), 0, st, Q, g0, nb, rlo, rhi, D.rng_desc.p);
+            zz_inf_params I;
+            I.s = s; I.sn = sn; I.starts = d_index; I.nstarts = npk + 1; I.k0 = 0; I.npk = nb; I.npk_total = npk;
+            I.P = P; I.mode = ZZ_INF_INDEXED; I.dst = D.stage; I.cap = (uint64_t)nb * P;
+            I.st = D.st; I.pend = D.pend; I.words = words; I.pcnt = D.pcnt; I.prem = D.prem; I.ends = D.ends; I.stat = D.stat; I.tot = D.tot;
+            I.ebase = 0;
+            zz_inf_ranges X{ D.rng_desc.p, D.rng_reads.p };
+            hipLaunchKernelGGL(k_inflate_packets_ranges, dim3(nb), dim3(ZZ_INF_THREADS), lds, st, I, X);
+            zz_res_params R{ D.stage, 0, P, nb, words, D.st, D.pend, D.pcnt, D.prem, D.tot };
+            for (uint32_t r = 1; r <= rounds; ++r) hipLaunchKernelGGL(k_inflate_resolve_ranges, dim3(nb), dim3(ZZ_INF_RES_THREADS), 0, st, R, X, r);
+            hipLaunchKernelGGL(k_ranges_verdict, dim3((uint32_t)((rhi - rlo + 255) / 256)), dim3(256), 0, st, Q, g0, rlo, rhi, D.stat.p);
+            hipLaunchKernelGGL(k_ranges_copy, dim3(nb), dim3(256), 0, st, Q, D.rng_desc.p, D.stage.p);
+            HIPCHK(hipGetLastError());
+        }
+    }
+    D.ranges.retried = T.retried;
+    if (T.n_data) { set_err("reads: " + std::to_string(T.n_data) + " met a packet that does not decode as the index says"); return ZZ_E_DATA; }
+    if (T.n_unsupported) { set_err("reads: " + std::to_string(T.n_unsupported) + " need more than one batch of packets: use zz_decode_range_device"); return ZZ_E_UNSUPPORTED; }
+    if (T.n_arg) { set_err("reads: " + std::to_string(T.n_arg) + " start behind the index's last packet or overflow"); return ZZ_E_ARG; }
+    if (T.n_nospace) { set_err("reads: " + std::to_string(T.n_nospace) + " do not fit their destinations"); return ZZ_E_NOSPACE; }
+    return ZZ_OK;
+}
+
+extern "C" int zz_ctx_last_decode_ranges_stats(const zz_ctx* c, uint64_t* packets, uint32_t* attempts, uint64_t* retried_ranges,
+                                               uint32_t* waves)
+{
+    if (!c) { set_err("null context"); return ZZ_E_ARG; }
+    if (packets) *packets = c->dec.ranges.packets;
+    if (attempts) *attempts = c->dec.ranges.attempts;
+    if (retried_ranges) *retried_ranges = c->dec.ranges.retried;
+    if (waves) *waves = c->dec.ranges.waves;
     return ZZ_OK;
 }
 

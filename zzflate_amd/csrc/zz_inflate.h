@@ -119,13 +119,20 @@ __device__ __forceinline__ uint32_t inf_wave_sum(uint32_t v)
 // dynamic LDS: bitmap words * 4 + ZZ_INF_IBUF + P rounded up to 16
 // RANGE (k_inflate_packets_range, zz_decode_range_device): Q.dst is the stage of this batch and holds npk * P bytes, so packet b's
 // bytes go to b * P -- where the pointers count from -- and always fit; everything else, `abs` and the checks included, is the same.
-template <bool RANGE> __device__ __forceinline__ void inflate_packets_body(zz_inf_params Q)
+// RANGES (form 2, k_inflate_packets_ranges, zz_inflate_ranges.h): the workgroup's packet is what its descriptor says -- stream
+// packet d.k of read d.read, whose segment starts at stage packet d.seg0 of the wave; the pointers count from the segment's first
+// byte, a failed packet is charged to its read, and ends / stat are kept per stage packet.
+struct zz_inf_ranges { const zi_read_desc* desc; zi_read* reads; };
+template <int FORM> __device__ __forceinline__ void inflate_packets_body(zz_inf_params Q, zz_inf_ranges X)
 {
+    constexpr bool RANGE = FORM != 0;
     extern __shared__ uint4 inf_dyn[];
     __shared__ zi_tables S;
     const uint32_t lane = threadIdx.x;
     const uint32_t b = blockIdx.x;
-    const uint64_t k = Q.k0 + b;
+    zi_read_desc D{};
+    if (FORM == 2) D = X.desc[b];
+    const uint64_t k = FORM == 2 ? D.k : Q.k0 + b;
     uint32_t* pend = (uint32_t*)inf_dyn;
     uint8_t* ibuf = (uint8_t*)inf_dyn + (uint64_t)Q.words * 4;
     uint8_t* win = ibuf + ZZ_INF_IBUF;
@@ -150,7 +157,7 @@ template <bool RANGE> __device__ __forceinline__ void inflate_packets_body(zz_in
         zz_inf_in in{ view.p, view.n, ibuf, -(int64_t)(2 * ZZ_INF_IBUF), lane };
         zi_out_packet<zz_inf_fence, zz_inf_or> o{ zi_view<uint8_t>{ win, Q.P }, zi_view<uint32_t>{ pend, Q.words },
                                                   zi_view<uint32_t>{ Q.st + (uint64_t)b * Q.P, Q.P },
-                                                  abs, (int64_t)((uint64_t)b * Q.P), 0, 0, false, lane, ZZ_INF_THREADS, {}, {} };
+                                                  abs, (int64_t)((uint64_t)(FORM == 2 ? b - D.seg0 : b) * Q.P), 0, 0, false, lane, ZZ_INF_THREADS, {}, {} };
         R = zi_run(in, view, 0, o, S, Q.mode == ZZ_INF_INDEXED ? ZI_RUN_INDEXED : ZI_RUN_DISCOVER, Q.P, lane, ZZ_INF_THREADS);
         np = o.npend;
         if (!R.err && Q.mode == ZZ_INF_INDEXED) {
@@ -179,15 +186,22 @@ template <bool RANGE> __device__ __forceinline__ void inflate_packets_body(zz_in
     }
     // phase 2 looks at a packet only through these: a packet that failed or was not written has nothing pending
     if (lane == 0) { const uint32_t v = fits ? np : 0u; Q.pcnt[b] = v; Q.prem[b] = v; }
-    if (lane == 0 && k < Q.nstarts) {
+    if (FORM == 2) {
+        if (lane == 0) {
+            Q.ends[b] = R.err ? 0 : start + R.end;
+            Q.stat[b] = R.err ? 0u : (1u | (R.final ? 2u : 0u) | ((uint32_t)R.out << 3));
+            if (R.err) atomicAdd(&X.reads[D.read].fail, 1u);
+        }
+    } else if (lane == 0 && k < Q.nstarts) {
         Q.ends[k - Q.ebase] = R.err ? 0 : start + R.end;
         Q.stat[k - Q.ebase] = R.err ? 0u : (1u | (R.final ? 2u : 0u) | (fits ? 0u : 4u) | ((uint32_t)R.out << 3));
         if (R.err) atomicAdd(&Q.tot[63], 1ull);
         else if (!fits) atomicAdd(&Q.tot[62], 1ull);
     }
 }
-__global__ __launch_bounds__(ZZ_INF_THREADS) void k_inflate_packets(zz_inf_params Q) { inflate_packets_body<false>(Q); }
-__global__ __launch_bounds__(ZZ_INF_THREADS) void k_inflate_packets_range(zz_inf_params Q) { inflate_packets_body<true>(Q); }
+__global__ __launch_bounds__(ZZ_INF_THREADS) void k_inflate_packets(zz_inf_params Q) { inflate_packets_body<0>(Q, zz_inf_ranges{ nullptr, nullptr }); }
+__global__ __launch_bounds__(ZZ_INF_THREADS) void k_inflate_packets_range(zz_inf_params Q) { inflate_packets_body<1>(Q, zz_inf_ranges{ nullptr, nullptr }); }
+__global__ __launch_bounds__(ZZ_INF_THREADS) void k_inflate_packets_ranges(zz_inf_params Q, zz_inf_ranges X) { inflate_packets_body<2>(Q, X); }
 
 // phase 2, round `round` (1-based) over the batch [k0, k0 + npk); `base` = absolute output position of its first byte
 struct zz_res_params {
@@ -199,13 +213,20 @@ struct zz_res_params {
 // this batch's -- and base = ZI_BIAS, so a target below the batch base reads a carried byte; `carry` has one bit per carried
 // byte: external (zz_inflate_core.h). Bytes that turn external inside [wlo, whi) (relative to the batch base) are counted in tot[61].
 struct zz_res_range { const uint32_t* carry; int64_t wlo, whi; };
-template <bool RANGE> __device__ __forceinline__ void inflate_resolve_body(zz_res_params Q, zz_res_range X, uint32_t round)
+// RANGES (form 2, k_inflate_resolve_ranges): the stage holds a wave of segments and base = 0; a pointer counts from its segment's
+// first byte, stage packet d.seg0, and a target below that is external -- nothing is carried, segments do not span batches. The
+// external bytes inside the read's window (bytes [d.lo, d.hi) of this packet) are counted in the read's record.
+template <int FORM> __device__ __forceinline__ void inflate_resolve_body(zz_res_params Q, zz_res_range X, zz_inf_ranges Z, uint32_t round)
 {
+    constexpr bool RANGE = FORM != 0;
     __shared__ uint32_t red[ZZ_INF_RES_THREADS / ZZ_WAVE];
     const uint32_t k = blockIdx.x;
     if (Q.pcnt[k] == 0 || Q.prem[k] == 0) return;         // uniform per workgroup
     const uint32_t t = threadIdx.x;
     uint32_t left = 0, nx = 0;
+    zi_read_desc D{};
+    if (FORM == 2) D = Z.desc[k];
+    const uint64_t sb = FORM == 2 ? (uint64_t)D.seg0 * Q.P : 0;          // where the pointers of this packet count from
     for (uint32_t q = t; q < Q.P; q += ZZ_INF_RES_THREADS) {
         if (!((Q.pend[(uint64_t)k * Q.words + (q >> 5)] >> (q & 31)) & 1u)) continue;
         const uint64_t x = (uint64_t)k * Q.P + q;
@@ -214,12 +235,13 @@ template <bool RANGE> __device__ __forceinline__ void inflate_resolve_body(zz_re
         const int64_t y = (int64_t)(s & ZI_PTR_MASK) - (int64_t)ZI_BIAS;
         bool fin = y < 0;                                 // an earlier batch: final (phase 1 refused anything in front of the stream)
         bool ext = false;
-        if (RANGE && fin) { ext = zi_range_external(y, zi_view<const uint32_t>{ X.carry, ZI_BIAS / 32 }); fin = !ext; }
+        if (FORM == 1 && fin) { ext = zi_range_external(y, zi_view<const uint32_t>{ X.carry, ZI_BIAS / 32 }); fin = !ext; }
+        if (FORM == 2 && fin) { ext = true; fin = false; }
         if (y >= 0) {
-            const uint64_t ky = (uint64_t)y / Q.P, qy = (uint64_t)y % Q.P;
+            const uint64_t ky = (sb + (uint64_t)y) / Q.P, qy = (uint64_t)y % Q.P;
             fin = Q.pcnt[ky] == 0 || !((Q.pend[ky * Q.words + (qy >> 5)] >> (qy & 31)) & 1u);
             if (!fin) {
-                const uint32_t sy = Q.st[y];
+                const uint32_t sy = Q.st[sb + y];
                 const uint32_t ry = sy >> 27;
                 if (RANGE && ry == ZI_ROUND_EXTERNAL) ext = true;   // it stays external, whenever the target was marked
                 else if (ry != 0 && ry < round) fin = true; // final before this round began: its byte is in place
@@ -227,17 +249,18 @@ template <bool RANGE> __device__ __forceinline__ void inflate_resolve_body(zz_re
             }
         }
         if (fin) {
-            Q.dst[Q.base + x] = Q.dst[(int64_t)Q.base + y];
+            Q.dst[Q.base + x] = Q.dst[(int64_t)(Q.base + sb) + y];
             Q.st[x] = (s & ZI_PTR_MASK) | (round << 27);
         }
         if (RANGE && ext) {
             Q.st[x] = (s & ZI_PTR_MASK) | (ZI_ROUND_EXTERNAL << 27);
-            if ((int64_t)x >= X.wlo && (int64_t)x < X.whi) ++nx;
+            if (FORM == 2 ? (q >= D.lo && q < D.hi) : ((int64_t)x >= X.wlo && (int64_t)x < X.whi)) ++nx;
         }
     }
     if (RANGE) {
         nx = inf_wave_sum(nx);
-        if ((t & 63) == 0 && nx) atomicAdd(&Q.tot[61], (unsigned long long)nx);
+        if (FORM == 2) { if ((t & 63) == 0 && nx) atomicAdd(&Z.reads[D.read].ext, nx); }
+        else if ((t & 63) == 0 && nx) atomicAdd(&Q.tot[61], (unsigned long long)nx);
     }
     left = inf_wave_sum(left);
     if ((t & 63) == 0) red[t >> 6] = left;
@@ -251,11 +274,15 @@ template <bool RANGE> __device__ __forceinline__ void inflate_resolve_body(zz_re
 }
 __global__ __launch_bounds__(ZZ_INF_RES_THREADS) void k_inflate_resolve(zz_res_params Q, uint32_t round)
 {
-    inflate_resolve_body<false>(Q, zz_res_range{ nullptr, 0, 0 }, round);
+    inflate_resolve_body<0>(Q, zz_res_range{ nullptr, 0, 0 }, zz_inf_ranges{ nullptr, nullptr }, round);
 }
 __global__ __launch_bounds__(ZZ_INF_RES_THREADS) void k_inflate_resolve_range(zz_res_params Q, zz_res_range X, uint32_t round)
 {
-    inflate_resolve_body<true>(Q, X, round);
+    inflate_resolve_body<1>(Q, X, zz_inf_ranges{ nullptr, nullptr }, round);
+}
+__global__ __launch_bounds__(ZZ_INF_RES_THREADS) void k_inflate_resolve_ranges(zz_res_params Q, zz_inf_ranges Z, uint32_t round)
+{
+    inflate_resolve_body<2>(Q, zz_res_range{ nullptr, 0, 0 }, Z, round);
 }
 
 // range decode, between two batches: the last ZI_BIAS bytes of the finished batch (stage[ZI_BIAS + n - ZI_BIAS + i]) move to the

@@ -431,6 +431,96 @@ ZZ_HD inline bool zi_range_external(int64_t y, const zi_view<const uint32_t>& ca
     return ((carry[c >> 5] >> (c & 31)) & 1u) != 0;
 }
 
+// ---- many ranges of one indexed stream in one call (zz_decode_ranges_device; tests/cxx/inflate_ranges_harness.cpp) ---------
+// Every read r has its own SEGMENT: packets [k0 - h_r, k1) decoded onto a stage, with pointers relative to the segment's first
+// byte. A target below the segment's base is external (there are no batches here, so nothing is carried); a read with an
+// external byte inside its window is unfinished and comes back in the next attempt with zi_range_next_lookback's look-back.
+// Segments follow one another on the stage in the order of the reads; a WAVE is the run of segments whose first stage packet
+// lies in [w * W, (w + 1) * W): whole segments, fewer than W + (longest segment) packets.
+enum { ZI_RS_NEW = 0, ZI_RS_AGAIN = 1, ZI_RS_DONE = 2 };        // a read's state: not planned yet, unfinished, settled
+// a read's status (= ZZ_OK, ZZ_E_NOSPACE, ZZ_E_ARG, ZZ_E_UNSUPPORTED, ZZ_E_DATA), and "unfinished"
+enum { ZI_RV_OK = 0, ZI_RV_NOSPACE = -2, ZI_RV_ARG = -4, ZI_RV_UNSUPPORTED = -5, ZI_RV_DATA = -6, ZI_RV_AGAIN = 1 };
+struct zi_read {
+    uint64_t h;            // the look-back of the coming (or running) attempt
+    uint64_t base;         // first stage packet of its segment in this attempt (an exclusive prefix over the reads)
+    uint64_t m;            // bytes it returns (valid once settled ZI_RV_OK)
+    uint32_t npk;          // packets of its segment in this attempt; 0: settled, or deferred to a later attempt
+    uint32_t state;
+    uint32_t fail;         // packets of the segment that failed phase 1 in this attempt
+    uint32_t ext;          // external bytes inside its window in this attempt
+    uint32_t tries;        // attempts that decoded a segment for it
+    int32_t status;
+};
+// one per stage packet of a wave
+struct zi_read_desc {
+    uint64_t k;            // the stream's packet
+    uint32_t read;
+    uint32_t seg0;         // the segment's first stage packet, counted from the wave's
+    uint32_t lo, hi;       // bytes [lo, hi) of this packet lie inside the read's window (lo == hi: none)
+};
+// the packets a read touches: [k0, k1), k1 clipped at the last packet. ZI_RV_ARG for a start behind the index or an overflow.
+ZZ_HD inline int zi_ranges_span(uint64_t first, uint64_t nbytes, uint32_t P, uint64_t npk, uint64_t* k0, uint64_t* k1)
+{
+    if (first / P >= npk || first + nbytes < first) return ZI_RV_ARG;
+    *k0 = first / P;
+    const uint64_t lastk = nbytes ? (first + nbytes - 1) / P : *k0;
+    *k1 = lastk + 1 < npk ? lastk + 1 : npk;
+    return ZI_RV_OK;
+}
+// The plan's share of one read: settles what needs no stage (ZI_RV_ARG, an empty read, a segment above `limit` packets:
+// ZI_RV_UNSUPPORTED) and returns the packets of the segment it wants in this attempt (0: none).
+ZZ_HD inline uint64_t zi_ranges_plan(zi_read& R, uint64_t first, uint64_t nbytes, uint32_t P, uint64_t npk, uint64_t limit)
+{
+    if (R.state == ZI_RS_DONE) return 0;
+    uint64_t k0 = 0, k1 = 0;
+    const int rc = zi_ranges_span(first, nbytes, P, npk, &k0, &k1);
+    if (rc) { R.state = ZI_RS_DONE; R.status = rc; return 0; }
+    if (nbytes == 0) { R.state = ZI_RS_DONE; R.status = ZI_RV_OK; R.m = 0; return 0; }
+    if (R.state == ZI_RS_NEW) { R.h = zi_range_first_lookback(P, k0); R.state = ZI_RS_AGAIN; }
+    const uint64_t l = k1 - (k0 - R.h);
+    if (l > limit) { R.state = ZI_RS_DONE; R.status = ZI_RV_UNSUPPORTED; return 0; }
+    return l;
+}
+ZZ_HD inline uint64_t zi_ranges_wave(uint64_t base, uint64_t W) { return base / W; }
+// the descriptor of stage packet j (0-based) of read `r`'s segment, whose first stage packet is `seg0` of the wave
+ZZ_HD inline zi_read_desc zi_ranges_desc(const zi_read& R, uint32_t r, uint64_t j, uint32_t seg0, uint64_t first, uint64_t nbytes, uint32_t P)
+{
+    zi_read_desc d;
+    d.k = first / P - R.h + j;
+    d.read = r; d.seg0 = seg0;
+    const uint64_t a = d.k * P, end = first + nbytes;            // (no overflow: the plan refused it)
+    d.lo = first > a ? (first - a < P ? (uint32_t)(first - a) : P) : 0u;
+    d.hi = end > a ? (end - a < P ? (uint32_t)(end - a) : P) : 0u;
+    if (d.hi < d.lo) d.hi = d.lo;
+    return d;
+}
+// The verdict on a read after its segment's phase 1 and rounds. `last_out`: bytes the segment's last packet produced (read only
+// when the segment reaches the stream's end). ZI_RV_AGAIN: unfinished, R.h grown; otherwise settled with that status.
+ZZ_HD inline int zi_ranges_verdict(zi_read& R, uint64_t first, uint64_t nbytes, uint64_t cap, uint32_t P, uint64_t npk, uint64_t limit,
+                                   uint32_t last_out)
+{
+    uint64_t k0 = 0, k1 = 0;
+    (void)zi_ranges_span(first, nbytes, P, npk, &k0, &k1);
+    ++R.tries;
+    int v;
+    if (R.fail) v = ZI_RV_DATA;
+    else if (R.ext) {
+        if (R.h >= k0) v = ZI_RV_DATA;                           // (phase 1 refuses what points in front of the stream)
+        else {
+            R.h = zi_range_next_lookback(R.h, k0);
+            v = k1 - (k0 - R.h) > limit ? ZI_RV_UNSUPPORTED : ZI_RV_AGAIN;
+        }
+    } else {
+        uint64_t have = nbytes;                                  // bytes of the stream from `first` on, if its end is in sight
+        if (k1 == npk) { const uint64_t L = (npk - 1) * (uint64_t)P + last_out; have = L > first ? L - first : 0; }
+        R.m = nbytes < have ? nbytes : have;
+        v = R.m > cap ? ZI_RV_NOSPACE : ZI_RV_OK;
+    }
+    R.fail = 0; R.ext = 0;
+    if (v != ZI_RV_AGAIN) { R.state = ZI_RS_DONE; R.status = v; }
+    return v;
+}
+
 // ---- the container --------------------------------------------------------------------------------------------
 // Header length of a zlib / gzip / raw stream held in h[0, n); <0: -1 not a valid header (or truncated), -2 preset dictionary.
 ZZ_HD inline int64_t zi_header(int format, const uint8_t* hp, uint64_t n)
