@@ -110,6 +110,7 @@ def _load():
         "zz_debug_peer_state": (i32, [i32, i32]),
         "zz_debug_last_pulls": (None, [ctypes.POINTER(i32), ctypes.POINTER(i32)]),
         "zz_debug_lds_order_verdict": (i32, [i32]),
+        "zz_debug_code_lengths": (i32, [vp, u32, vp, vp, vp, vp, vp, vp]),
         "zz_last_error": (ctypes.c_char_p, []),
         "zz_version": (ctypes.c_char_p, []),
         "zz_build_flags": (ctypes.c_char_p, []),

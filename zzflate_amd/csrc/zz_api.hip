@@ -406,6 +406,50 @@ extern "C" int zz_debug_lds_atomic_order(zz_ctx* c, uint32_t trials, unsigned lo
     if (checked) *checked = 512ull * 1024ull * 6ull * trials;
     return ZZ_OK;
 }
+// diagnostic (not part of the public header): the code construction of levels 2..6 on histograms of the caller's (k_debug_code_lengths,
+// zz_level2.h). All pointers are host memory. Case c: desc[4c] = mode (0: the frequency-floor limiter calc_lengths_w, 1: package-merge
+// pm_lengths_w), desc[4c + 1] = n (286 / 30 / 19), desc[4c + 2] = maxlen (15 / 15 / 7: the pairs the packet kernels use), freqs[288c ..
+// 288c + n). Out: lens[288c ..], codes[288c ..] = (len << 16) | bits, and for n = 286 / 30 recs[320c ..] = value | payload << 8,
+// meta[20c .. 20c + 19) the meta frequencies, meta[20c + 19] the record count. The limiter's heap keeps a count and a tree index in
+// one word (count << 10 | index, the root's count included: sums below 2^22) and package-merge sorts on count << 9 | symbol and adds
+// weights in 32 bits; a packet's counts sum to at most 32,769. The hook admits sums up to 2^20, a margin below the first of those
+// bounds and far above a packet: ZZ_E_ARG otherwise.
+extern "C" int zz_debug_code_lengths(zz_ctx* c, uint32_t ncases, const uint32_t* desc, const uint32_t* freqs, uint8_t* lens, uint32_t* codes,
+                                     uint16_t* recs, uint32_t* meta)
+{
+    if (!c || !desc || !freqs || !lens || !codes || !recs || !meta) { set_err("null argument"); return ZZ_E_ARG; }
+    if (ncases == 0) return ZZ_OK;
+    if (ncases > 65536u) { set_err("too many cases"); return ZZ_E_ARG; }
+    for (uint32_t k = 0; k < ncases; ++k) {
+        const uint32_t mode = desc[4 * k], n = desc[4 * k + 1], maxlen = desc[4 * k + 2];
+        uint64_t sum = 0;
+        if (mode > 1 || !((n == 286 && maxlen == 15) || (n == 30 && maxlen == 15) || (n == 19 && maxlen == 7))) { set_err("bad case descriptor"); return ZZ_E_ARG; }
+        for (uint32_t i = 0; i < n; ++i) sum += freqs[288ull * k + i];
+        if (sum > (1u << 20)) { set_err("counts of a case sum to more than 2^20"); return ZZ_E_ARG; }
+    }
+    HIPCHK(hipSetDevice(c->device));
+    zz_buf<uint32_t> d_desc, d_freqs, d_codes, d_meta;
+    zz_buf<uint8_t> d_lens;
+    zz_buf<uint16_t> d_recs;
+    int rc;
+    if ((rc = d_desc.grow(4ull * ncases)) || (rc = d_freqs.grow(288ull * ncases)) || (rc = d_codes.grow(288ull * ncases)) ||
+        (rc = d_meta.grow(20ull * ncases)) || (rc = d_lens.grow(288ull * ncases)) || (rc = d_recs.grow(320ull * ncases))) return rc;
+    HIPCHK(hipMemcpy(d_desc, desc, 4ull * ncases * sizeof(uint32_t), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d_freqs, freqs, 288ull * ncases * sizeof(uint32_t), hipMemcpyHostToDevice));
+    HIPCHK(hipMemset(d_lens, 0, 288ull * ncases));
+    HIPCHK(hipMemset(d_codes, 0, 288ull * ncases * sizeof(uint32_t)));
+    HIPCHK(hipMemset(d_recs, 0, 320ull * ncases * sizeof(uint16_t)));
+    HIPCHK(hipMemset(d_meta, 0, 20ull * ncases * sizeof(uint32_t)));
+    zz_dbg_cl_params q; q.desc = d_desc; q.freqs = d_freqs; q.lens = d_lens; q.codes = d_codes; q.recs = d_recs; q.meta = d_meta;
+    hipLaunchKernelGGL(k_debug_code_lengths, dim3(ncases), dim3(ZZ_WAVE), 0, 0, q);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(lens, d_lens, 288ull * ncases, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(codes, d_codes, 288ull * ncases * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(recs, d_recs, 320ull * ncases * sizeof(uint16_t), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(meta, d_meta, 20ull * ncases * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return ZZ_OK;
+}
 // ---- the run-time guard for that property ---------------------------------------------------------------------------------
 // Three things in this library are only correct where the LDS serves equal addresses of one instruction in ascending lane order
 // and one wavefront's instructions in issue order -- which gfx950 does and its ISA manual does not promise: the warm window's

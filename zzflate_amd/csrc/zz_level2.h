@@ -1108,6 +1108,37 @@ struct zz_l2_params {
 // the barriers. 27 wavefronts per CU: seven on one SIMD => at most 72 VGPRs.
 // MAP: zz_no_batch (one shard: the packets of Q.pk) or zz_batch_map (a batch, k_encode_l2_batch_t: Q.k0 .. Q.k1 number the batch's
 // packets, and every packet sees its own item through zz_packet_view).
+// The code construction's part of that carve-up, in one place: the packet kernels and k_debug_code_lengths (below) lay the
+// Huffman scratch, the package-merge scratch, the lengths, the run-length records, the counts and the code tables out alike.
+#define ZZ_L2_LDS_LENS 6912u          // 320: lit/len lengths, then dist lengths at [288..318)
+#define ZZ_L2_LDS_METALENS 7232u      // 32
+#define ZZ_L2_LDS_METACODES 7264u     // 80
+#define ZZ_L2_LDS_RLE 7344u           // up to 316+30 records -> 704 bytes
+#define ZZ_L2_LDS_SYMF 8192u          // 1280 counts, 1152 lit/len codes, 128 distance codes, 80 meta frequencies
+#define ZZ_L2_LDS_MISC 11264u         // 256
+__device__ __forceinline__ huff_scratch l2_huff_scratch(uint8_t* lds)
+{
+    huff_scratch S;
+    S.rec_freq = (uint32_t*)(lds);                 // 1152
+    S.rec_id = (uint16_t*)(lds + 1152);            // 576
+    S.t_freq = (uint32_t*)(lds + 1728);            // 2304
+    S.t_left = (uint16_t*)(lds + 4032);            // 1152
+    S.t_right = (uint16_t*)(lds + 5184);           // 1152
+    S.t_bits = (uint8_t*)(lds + 6336);             // 576
+    return S;
+}
+__device__ __forceinline__ pm_scratch l2_pm_scratch(uint8_t* lds)
+{
+    pm_scratch PM;
+    PM.sym = (uint16_t*)(lds);                     // 576
+    PM.w = (uint32_t*)(lds + 576);                 // 1152
+    PM.pk = (uint32_t*)(lds + 1728);               // 1152
+    PM.cur = (uint32_t*)(lds + 2880);              // 2304
+    PM.bm = (uint64_t*)(lds + 5184);               // 1152
+    PM.misc = (uint32_t*)(lds + 6336);             // 128 (.. 6464 < 6912)
+    return PM;
+}
+
 template <uint32_t BIAS, bool XD, bool PP, class MAP>
 __device__ __forceinline__ void l2_encode_run(const zz_l2_params Q, const MAP M)
 {
@@ -1122,12 +1153,12 @@ __device__ __forceinline__ void l2_encode_run(const zz_l2_params Q, const MAP M)
     constexpr uint32_t RING3 = 12288u;                            // PP: the second parser's (the dead hash table has room: 12080 .. 16384)
     __shared__ __attribute__((aligned(16))) uint8_t lds[HB + (ZZ_L2_LDS_BYTES - 16384) + 16];
     uint16_t* T = (uint16_t*)lds;                                 // 16384: hash table during the token pass
-    uint32_t* symF = (uint32_t*)(lds + 8192);                     // 1280: 286 lit/len + pad | 30 dist at [288..318)
+    uint32_t* symF = (uint32_t*)(lds + ZZ_L2_LDS_SYMF);           // 1280: 286 lit/len + pad | 30 dist at [288..318)
     uint32_t* distF = symF + 288;
-    uint32_t* codes = (uint32_t*)(lds + 8192 + 1280);             // 1152: 286 lit/len codes
-    uint32_t* dcodes = (uint32_t*)(lds + 8192 + 1280 + 1152);     // 128: 30 distance codes
-    uint32_t* metaF = (uint32_t*)(lds + 8192 + 1280 + 1152 + 128);            // 80: 19 meta frequencies
-    uint32_t* misc = (uint32_t*)(lds + 11264);                    // 256: lane-0 results [0..3], code-generation work area [16..48)
+    uint32_t* codes = (uint32_t*)(lds + ZZ_L2_LDS_SYMF + 1280);   // 1152: 286 lit/len codes
+    uint32_t* dcodes = (uint32_t*)(lds + ZZ_L2_LDS_SYMF + 1280 + 1152);       // 128: 30 distance codes
+    uint32_t* metaF = (uint32_t*)(lds + ZZ_L2_LDS_SYMF + 1280 + 1152 + 128);  // 80: 19 meta frequencies
+    uint32_t* misc = (uint32_t*)(lds + ZZ_L2_LDS_MISC);           // 256: lane-0 results [0..3], code-generation work area [16..48)
     uint32_t* ring_words = (uint32_t*)(lds + HB);                 // 512 (+48 pad)
     uint32_t* hb = (uint32_t*)(lds + HB);                         // 560: two hand-over slots, same bytes as the ring
     uint64_t* covw = (uint64_t*)(lds + HB + 560);                 // 128: covered bits of the 16 blocks around the probe front
@@ -1135,25 +1166,13 @@ __device__ __forceinline__ void l2_encode_run(const zz_l2_params Q, const MAP M)
     uint32_t* histP = (uint32_t*)(lds + HB + 560 + 2 * ZZ_L2_WIN * 8);        // 640: packed 16-bit counters
     __shared__ uint32_t xb[8];                                    // PP: backRefEnd, the next probe position and the hand-over counters (l2p_sync)
     // Huffman scratch inside the (dead) hash table
-    huff_scratch S;
-    S.rec_freq = (uint32_t*)(lds);                 // 1152
-    S.rec_id = (uint16_t*)(lds + 1152);            // 576
-    S.t_freq = (uint32_t*)(lds + 1728);            // 2304
-    S.t_left = (uint16_t*)(lds + 4032);            // 1152
-    S.t_right = (uint16_t*)(lds + 5184);           // 1152
-    S.t_bits = (uint8_t*)(lds + 6336);             // 576
-    uint8_t* lens = (uint8_t*)(lds + 6912);        // 320: lit/len lengths, then dist lengths at [288..318)
-    uint8_t* metaLens = (uint8_t*)(lds + 7232);    // 32
-    uint32_t* metaCodes = (uint32_t*)(lds + 7264); // 80
-    uint16_t* rle = (uint16_t*)(lds + 7344);       // up to 316+30 records -> 704 bytes
+    huff_scratch S = l2_huff_scratch(lds);
+    uint8_t* lens = (uint8_t*)(lds + ZZ_L2_LDS_LENS);
+    uint8_t* metaLens = (uint8_t*)(lds + ZZ_L2_LDS_METALENS);
+    uint32_t* metaCodes = (uint32_t*)(lds + ZZ_L2_LDS_METACODES);
+    uint16_t* rle = (uint16_t*)(lds + ZZ_L2_LDS_RLE);
     // XD: package-merge scratch in the same (dead) space, in front of `lens`
-    pm_scratch PM;
-    PM.sym = (uint16_t*)(lds);                     // 576
-    PM.w = (uint32_t*)(lds + 576);                 // 1152
-    PM.pk = (uint32_t*)(lds + 1728);               // 1152
-    PM.cur = (uint32_t*)(lds + 2880);              // 2304
-    PM.bm = (uint64_t*)(lds + 5184);               // 1152
-    PM.misc = (uint32_t*)(lds + 6336);             // 128 (.. 6464 < 6912)
+    pm_scratch PM = l2_pm_scratch(lds);
 
     const int lane = lane_id();
     const uint32_t wave = uniform(threadIdx.x >> 6);
@@ -1561,6 +1580,74 @@ template <uint32_t BIAS, bool XD = false, bool PP = false>
 __global__ __launch_bounds__(PP ? ZZ_L2P_THREADS : ZZ_L2_THREADS, PP ? ZZ_L2P_WPE : (XD ? 6 : 5)) void k_encode_l2_t(zz_l2_params Q)
 {
     l2_encode_run<BIAS, XD, PP>(Q, zz_no_batch());
+}
+
+// ---- diagnostic: the code construction alone, on histograms the caller supplies (zz_debug_code_lengths, zz_api.hip) ----------------
+// The packet kernels reach calc_lengths_w's retry loop and a biting 15-bit limit only through the histograms their inputs happen to
+// produce; this kernel runs the same routines, instantiated with the same constants on the same LDS layout, on any histogram: one
+// wavefront per case, case = workgroup. Per case: desc[4c] = mode (0 calc_lengths_w, 1 pm_lengths_w), desc[4c + 1] = n (286 / 30 /
+// 19: the host checks), freqs[288c ..]; out: lens[288c ..], codes[288c ..] as generate_codes_w packs them, and for n = 286 / 30
+// what rle_lengths_w makes of the lengths: recs[320c ..], meta[20c .. 20c + 19) the meta frequencies, meta[20c + 19] the record count.
+struct zz_dbg_cl_params {
+    const uint32_t* desc;
+    const uint32_t* freqs;
+    uint8_t* lens;
+    uint32_t* codes;
+    uint16_t* recs;
+    uint32_t* meta;
+};
+__global__ __launch_bounds__(ZZ_WAVE) void k_debug_code_lengths(zz_dbg_cl_params Q)
+{
+    __shared__ __attribute__((aligned(16))) uint8_t lds[ZZ_L2_LDS_MISC + 256];
+    uint32_t* symF = (uint32_t*)(lds + ZZ_L2_LDS_SYMF);
+    uint32_t* distF = symF + 288;
+    uint32_t* codes = (uint32_t*)(lds + ZZ_L2_LDS_SYMF + 1280);
+    uint32_t* dcodes = (uint32_t*)(lds + ZZ_L2_LDS_SYMF + 1280 + 1152);
+    uint32_t* metaF = (uint32_t*)(lds + ZZ_L2_LDS_SYMF + 1280 + 1152 + 128);
+    uint32_t* misc = (uint32_t*)(lds + ZZ_L2_LDS_MISC);
+    huff_scratch S = l2_huff_scratch(lds);
+    pm_scratch PM = l2_pm_scratch(lds);
+    uint8_t* lens = (uint8_t*)(lds + ZZ_L2_LDS_LENS);
+    uint8_t* metaLens = (uint8_t*)(lds + ZZ_L2_LDS_METALENS);
+    uint32_t* metaCodes = (uint32_t*)(lds + ZZ_L2_LDS_METACODES);
+    uint16_t* rle = (uint16_t*)(lds + ZZ_L2_LDS_RLE);
+
+    const int lane = lane_id();
+    const uint32_t c = blockIdx.x;
+    const bool pm = uniform(Q.desc[4 * c]) != 0;
+    const int n = (int)uniform(Q.desc[4 * c + 1]);      // (desc[4c + 2], maxlen, is not read: the host admits only 286 / 15, 30 / 15, 19 / 7)
+    uint32_t* const F = n == 286 ? symF : n == 30 ? distF : metaF;
+    for (int i = lane; i < 20; i += ZZ_WAVE) metaF[i] = 0;
+    ZZ_WAVE_SYNC();
+    for (int i = lane; i < n; i += ZZ_WAVE) F[i] = Q.freqs[288u * c + (uint32_t)i];
+    ZZ_WAVE_SYNC();
+    const uint8_t* L;
+    const uint32_t* C;
+    int nr = 0;
+    if (n == 286) {         // the calls as l2_encode_run makes them
+        if (pm) pm_lengths_w(PM, symF, 286, 15, lens); else calc_lengths_w(S, symF, 286, 15, lens);
+        ZZ_WAVE_SYNC();
+        nr = rle_lengths_w<286>(lens, rle, 0, metaF);
+        generate_codes_w(lens, 286, codes, misc + 16);
+        L = lens; C = codes;
+    } else if (n == 30) {
+        if (pm) pm_lengths_w(PM, distF, 30, 15, lens + 288); else calc_lengths_w(S, distF, 30, 15, lens + 288);
+        ZZ_WAVE_SYNC();
+        nr = rle_lengths_w<30>(lens + 288, rle, 0, metaF);
+        generate_codes_w(lens + 288, 30, dcodes, misc + 16);
+        L = lens + 288; C = dcodes;
+    } else {
+        if (pm) pm_lengths_w(PM, metaF, 19, 7, metaLens); else calc_lengths_w(S, metaF, 19, 7, metaLens);
+        generate_codes_w(metaLens, 19, metaCodes, misc + 16);
+        L = metaLens; C = metaCodes;
+    }
+    ZZ_WAVE_SYNC();
+    for (int i = lane; i < n; i += ZZ_WAVE) { Q.lens[288u * c + (uint32_t)i] = L[i]; Q.codes[288u * c + (uint32_t)i] = C[i]; }
+    if (n != 19) {
+        for (int i = lane; i < nr; i += ZZ_WAVE) Q.recs[320u * c + (uint32_t)i] = rle[i];
+        if (lane < 19) Q.meta[20u * c + (uint32_t)lane] = metaF[lane];
+        if (lane == 19) Q.meta[20u * c + 19u] = (uint32_t)nr;
+    }
 }
 
 // xdepth: 0 = levels 2,3; 2 / 4 / 8 = the extended levels 4 / 5 / 6 (chain depth)
