@@ -327,6 +327,39 @@ int zz_decode_ranges_device(zz_ctx* ctx, const void* d_src, uint64_t src_len, in
 int zz_ctx_last_decode_ranges_stats(const zz_ctx* ctx, uint64_t* packets, uint32_t* attempts,
                                     uint64_t* retried_ranges, uint32_t* waves);
 
+/* A file of gzip members back to back (RFC 1952 2.2): what `cat a.gz b.gz`, an append-mode gzip writer and bgzip / BAM / tabix
+ * (BGZF) write, and what gzip(1), zlib's gzread and Python's gzip.decompress read. d_src[0, src_len) holds one or more members;
+ * each is judged exactly as zz_decode_batch_device judges a single gzip item, the first byte behind a member's trailer is the
+ * next member's 1f or the end of the file, and d_dst[0, *out_len) receives the members' bytes one after the other. Zero
+ * padding between or behind members is NOT accepted (zlib's verdict, not gzip(1)'s leniency), nor is an empty file.
+ * Paths (zz_ctx_last_decode_members_stats):
+ *   1  blocked: every member announces its length in a `BC` extra subfield (anywhere among its subfields), the headers found
+ *      by a pass over the source form one chain from offset 0 to src_len, checked in parallel; the members are then decoded as a
+ *      batch, one wavefront each, at zz_decode_batch_device's rate -- fast from a few thousand members on
+ *   2  blocked, but a member holds bytes that look like such a header (a blocked file stored inside a blocked file): the chain
+ *      is walked from offset 0 by one lane, one dependent load per member, then decoded as in path 1
+ *   3  serial: members without `BC`, a chain that cannot be walked, and every file in which a member fails: ONE wavefront
+ *      decodes member after member at a few MB/s, like packet_size 0 of zz_decode_device
+ * The paths decide speed, never the result: the serial path is the definition, and the blocked paths answer only what it
+ * would. Verdict: members are judged in file order and the first one that fails decides -- ZZ_E_DATA if it is invalid (header,
+ * blocks, truncation, CRC-32, ISIZE, a byte that is not a header behind a trailer, src_len == 0), ZZ_E_NOSPACE if its bytes
+ * pass `cap` before it is found invalid; nothing is written outside d_dst[0, cap). *out_len = ~0 on failure.
+ * Cost of errors: a blocked file that is merely too large for `cap` is refused at the parallel rate plus ONE member at the
+ * serial rate (the member that ran out of room is judged again as the serial path reads it); any other failure is
+ * decided by the serial path, so a damaged multi-GiB file takes minutes to be refused.
+ * ZZ_E_ARG, before anything is launched: a null context, a null d_src with src_len > 0, a null d_dst with cap > 0, a null
+ * out_len, an unfinished zz_encode_device_async on the context.
+ * Workspace: 12 bytes per 4 KiB of source and 52 bytes per header-like offset found (members or not). Limits: the blocked paths
+ * take at most 2^31 - 1 members (a file with more header-like offsets goes to the serial path). Synchronous; the host reads
+ * a fixed handful of numbers, whatever the member count. Leaves the context's "last call" and "last decode" state alone, as
+ * zz_decode_batch_device does. */
+int zz_decode_members_device(zz_ctx* ctx, const void* d_src, uint64_t src_len, void* d_dst, uint64_t cap,
+                             uint64_t* out_len, void* hip_stream);
+/* what the last zz_decode_members_device did: the members it decoded (on failure: those in front of the deciding one when the
+ * serial path decided, else those dealt), the header-like offsets the blocked path found (candidates), and the path:
+ * 1 blocked, chain verified in parallel; 2 blocked, chain walked; 3 serial (0: no call yet, or refused before a path was taken) */
+int zz_ctx_last_decode_members_stats(const zz_ctx* ctx, uint64_t* members, uint64_t* candidates, int* path);
+
 enum { ZZ_DECODE_INDEXED = 1, ZZ_DECODE_DISCOVERED = 2, ZZ_DECODE_SERIAL = 3 };
 /* which path the last zz_decode_device finished on (0: none) */
 int zz_ctx_last_decode_path(const zz_ctx* ctx);

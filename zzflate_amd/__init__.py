@@ -92,6 +92,8 @@ def _load():
         "zz_ctx_last_decode_range_stats": (i32, [vp, pu64, pu64, ctypes.POINTER(u32), pu64]),
         "zz_decode_ranges_device": (i32, [vp, vp, u64, i32, u32, vp, u64, u64, vp, vp, vp, vp, vp, vp, vp]),
         "zz_ctx_last_decode_ranges_stats": (i32, [vp, pu64, ctypes.POINTER(u32), pu64, ctypes.POINTER(u32)]),
+        "zz_decode_members_device": (i32, [vp, vp, u64, vp, u64, pu64, vp]),
+        "zz_ctx_last_decode_members_stats": (i32, [vp, pu64, pu64, ctypes.POINTER(i32)]),
         "zz_ctx_last_decode_path": (i32, [vp]),
         "zz_ctx_last_decode_stats": (i32, [vp, pu64, ctypes.POINTER(u32)]),
         "zz_ctx_last_decode_index_device": (i32, [vp, vp, u64, pu64, vp]),
@@ -222,6 +224,8 @@ def generate_host(kind, seed, first_byte, n):
 GEN_TEXT, GEN_RANDOM, GEN_LOG, GEN_MIX = 0, 1, 2, 3
 # which path a decode finished on (Context.last_decode_path)
 DECODE_INDEXED, DECODE_DISCOVERED, DECODE_SERIAL = 1, 2, 3
+# which path a members decode finished on (Context.last_decode_members_stats)
+MEMBERS_BLOCKED, MEMBERS_WALKED, MEMBERS_SERIAL = 1, 2, 3
 E_NOSPACE, E_ARG, E_UNSUPPORTED, E_DATA = -2, -4, -5, -6
 
 
@@ -542,6 +546,24 @@ class Context:
         npk, retried, tries, waves = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint32(0), ctypes.c_uint32(0)
         _check(lib.zz_ctx_last_decode_ranges_stats(self._h, ctypes.byref(npk), ctypes.byref(tries), ctypes.byref(retried), ctypes.byref(waves)))
         return npk.value, tries.value, retried.value, waves.value
+
+    def decode_members(self, src, src_len, dst, cap, stream=None):
+        """Decode the file of gzip members ``src[:src_len]`` -- one member or many back to back: ``cat a.gz b.gz``, bgzip / BAM
+        (BGZF) -- into ``dst`` (``cap`` bytes); returns the decoded length, the members' bytes one after the other. Members that
+        announce their length (BGZF's ``BC`` subfield) are decoded in parallel, one wavefront each; any other file serially, at
+        a few MB/s. The result is the same either way. Raises ZzFlateError (E_DATA: an invalid member, padding, an empty file;
+        E_NOSPACE: the bytes do not fit ``cap``)."""
+        out = ctypes.c_uint64(0)
+        st = self._stream() if stream is None else stream
+        _check(lib.zz_decode_members_device(self._h, self._ptr(src), src_len, self._ptr(dst), cap, ctypes.byref(out), st))
+        return out.value
+
+    def last_decode_members_stats(self):
+        """(members, header-like offsets found, path) of the last ``decode_members``; path is MEMBERS_BLOCKED (chain verified
+        in parallel), MEMBERS_WALKED (chain walked by one lane) or MEMBERS_SERIAL."""
+        m, cand, path = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_int(0)
+        _check(lib.zz_ctx_last_decode_members_stats(self._h, ctypes.byref(m), ctypes.byref(cand), ctypes.byref(path)))
+        return m.value, cand.value, path.value
 
     def last_decode_path(self):
         """DECODE_INDEXED, DECODE_DISCOVERED or DECODE_SERIAL: the path the last decode finished on (0: none)."""

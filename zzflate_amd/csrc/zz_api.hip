@@ -31,6 +31,7 @@
 #include "zz_verify.h"
 #include "zz_inflate.h"
 #include "zz_inflate_ranges.h"
+#include "zz_inflate_members.h"
 #include "zz_batch.h"
 
 using namespace zz;
@@ -183,6 +184,16 @@ struct zz_ctx {
         zz_buf<zz_rng_totals> rng_tot; zz_pin<zz_rng_totals> rng_host;
         struct { uint64_t packets = 0, retried = 0; uint32_t attempts = 0, waves = 0; } ranges;
         std::vector<uint64_t> last_index;                     // the index discovery recovered (zz_ctx_last_decode_index_device)
+        // zz_decode_members_device: per stretch of the mark pass (count, base), per candidate (offset, length; then the member
+        // list), per member k_inflate_items' descriptors, what the host reads, the serial path's result
+        struct {
+            zz_buf<uint32_t> blk_cnt; zz_buf<uint64_t> blk_base;
+            zz_buf<uint64_t> offs; zz_buf<uint32_t> lens;
+            zz_buf<const uint8_t*> srcs; zz_buf<uint8_t*> dsts; zz_buf<uint64_t> src_lens, caps, out_lens;
+            zz_buf<zz_mem_state> st; zz_pin<zz_mem_state> h_st;
+            zz_buf<zz_inf_members_out> sres; zz_pin<zz_inf_members_out> h_sres;
+            uint64_t members = 0, candidates = 0; int path = 0;
+        } mem;
     } dec;
 };
 // one call per context at a time: every entry point that would use the buffers of an enqueued call refuses
@@ -1872,6 +1883,21 @@ extern "C" int zz_encode_batch_device(zz_ctx* c, uint64_t nitems, const void* co
 // ---- a batch of independent streams back to their bytes (zz_inflate.h, k_inflate_items) ---------------------------------------
 static_assert(ZI_ITEM_OK == ZZ_OK && ZI_ITEM_NOSPACE == ZZ_E_NOSPACE && ZI_ITEM_UNSUPPORTED == ZZ_E_UNSUPPORTED && ZI_ITEM_DATA == ZZ_E_DATA,
               "zi_item reports the C ABI's codes");
+// k_inflate_items over q's items (its counters are the context's): returns when the two failure counters are in c->dec.items_host
+static int dec_items(zz_ctx* c, zz_inf_items_params q, hipStream_t st)
+{
+    // workspace: the dealing counter and the two failure counters (and their pinned mirror)
+    if (int rc = c->dec.items_ctr.grow(4)) return rc;
+    if (int rc = c->dec.items_host.grow(2)) return rc;
+    HIPCHK(hipMemsetAsync(c->dec.items_ctr, 0, 4 * sizeof(unsigned long long), st));
+    q.fails = c->dec.items_ctr; q.next = (unsigned int*)(c->dec.items_ctr + 2);
+    const uint64_t resident = 256ull * ZZ_INF_ITEM_WG_PER_CU;      // persistent wavefronts: what the CUs hold at once
+    hipLaunchKernelGGL(k_inflate_items, dim3((uint32_t)(q.nitems < resident ? q.nitems : resident)), dim3(ZZ_INF_THREADS), 0, st, q);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(c->dec.items_host, c->dec.items_ctr, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return ZZ_OK;
+}
 extern "C" int zz_decode_batch_device(zz_ctx* c, uint64_t nitems, const void* const* d_srcs, const uint64_t* d_src_lens,
                                       void* const* d_dsts, const uint64_t* d_caps, uint64_t* d_out_lens, int32_t* d_status,
                                       int format, void* hip_stream)
@@ -1884,19 +1910,10 @@ extern "C" int zz_decode_batch_device(zz_ctx* c, uint64_t nitems, const void* co
     if (nitems > 0x7FFFFFFFull) { set_err("too many items for one call"); return ZZ_E_ARG; }
     HIPCHK(hipSetDevice(c->device));
     hipStream_t st = (hipStream_t)hip_stream;
-    // workspace: the dealing counter and the two failure counters (and their pinned mirror)
-    if (int rc = c->dec.items_ctr.grow(4)) return rc;
-    if (int rc = c->dec.items_host.grow(2)) return rc;
-    HIPCHK(hipMemsetAsync(c->dec.items_ctr, 0, 4 * sizeof(unsigned long long), st));
     zz_inf_items_params q;
     q.srcs = (const uint8_t* const*)d_srcs; q.src_lens = d_src_lens; q.dsts = (uint8_t* const*)d_dsts; q.caps = d_caps;
     q.out_lens = d_out_lens; q.status = d_status; q.nitems = (uint32_t)nitems; q.format = format;
-    q.fails = c->dec.items_ctr; q.next = (unsigned int*)(c->dec.items_ctr + 2);
-    const uint64_t resident = 256ull * ZZ_INF_ITEM_WG_PER_CU;      // persistent wavefronts: what the CUs hold at once
-    hipLaunchKernelGGL(k_inflate_items, dim3((uint32_t)(nitems < resident ? nitems : resident)), dim3(ZZ_INF_THREADS), 0, st, q);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(c->dec.items_host, c->dec.items_ctr, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
+    if (int rc = dec_items(c, q, st)) return rc;
     const unsigned long long bad = c->dec.items_host[0], nospace = c->dec.items_host[1];
     if (bad) {
         set_err(std::to_string(bad) + " of " + std::to_string(nitems) + " items are not valid streams of the requested format (or need a preset dictionary)" +
@@ -1907,6 +1924,128 @@ extern "C" int zz_decode_batch_device(zz_ctx* c, uint64_t nitems, const void* co
         set_err(std::to_string(nospace) + " of " + std::to_string(nitems) + " items did not fit their destination");
         return ZZ_E_NOSPACE;
     }
+    return ZZ_OK;
+}
+
+// ---- a file of gzip members back to back (zz_inflate_members.h) -----------------------------------------------------------
+// the serial path: zi_members by one wavefront; it decides every verdict the blocked path does not. `members0` proven members
+// and `out0` bytes of theirs stand in front of src (0 and 0: the whole file); `path` is what the call reports if this succeeds
+// or answers "no space"
+static int dec_members_serial(zz_ctx* c, const uint8_t* src, uint64_t n, uint8_t* dst, uint64_t cap, hipStream_t st, uint64_t* out_len,
+                              uint64_t members0, uint64_t out0, int path)
+{
+    auto& M = c->dec.mem;
+    if (int rc = M.sres.grow(1)) return rc;
+    if (int rc = M.h_sres.grow(1)) return rc;
+    hipLaunchKernelGGL(k_inflate_members, dim3(1), dim3(ZZ_INF_THREADS), 0, st, src, n, dst, cap, (zz_inf_members_out*)M.sres);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(M.h_sres, M.sres, sizeof(zz_inf_members_out), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    M.members = members0 + M.h_sres->members;
+    M.path = path;
+    if (M.h_sres->status == ZI_ITEM_OK) { *out_len = out0 + M.h_sres->out; return ZZ_OK; }
+    if (M.h_sres->status == ZI_ITEM_NOSPACE) {
+        set_err("member " + std::to_string(M.members) + " does not fit what is left of the destination");
+        return ZZ_E_NOSPACE;
+    }
+    M.path = 3;
+    set_err("what stands where member " + std::to_string(M.members) + " would begin is not a valid gzip member");
+    return ZZ_E_DATA;
+}
+
+extern "C" int zz_decode_members_device(zz_ctx* c, const void* d_src_v, uint64_t src_len, void* d_dst_v, uint64_t cap, uint64_t* out_len,
+                                        void* hip_stream)
+{
+    if (out_len) *out_len = ~0ull;
+    if (!c) { set_err("null ctx"); return ZZ_E_ARG; }
+    if (!out_len) { set_err("null out_len"); return ZZ_E_ARG; }
+    if (!d_src_v && src_len) { set_err("null source"); return ZZ_E_ARG; }
+    if (!d_dst_v && cap) { set_err("null destination"); return ZZ_E_ARG; }
+    if (call_pending(c)) return ZZ_E_ARG;
+    auto& M = c->dec.mem;
+    M.members = 0; M.candidates = 0; M.path = 0;
+    if (src_len == 0) { set_err("an empty file holds no gzip member"); return ZZ_E_DATA; }
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t st = (hipStream_t)hip_stream;
+    const uint8_t* src = (const uint8_t*)d_src_v;
+    uint8_t* dst = (uint8_t*)d_dst_v;
+    const auto serial = [&]() -> int { return dec_members_serial(c, src, src_len, dst, cap, st, out_len, 0, 0, 3); };     // (writes *out_len on ZZ_OK only)
+
+    // mark: count per stretch, scan, and the one number that sizes the candidates' buffers
+    const uint64_t nblk = (src_len + ZZ_MEM_STRETCH - 1) / ZZ_MEM_STRETCH;
+    if (nblk > 0x7FFFFFFFull) return serial();                           // (8 TiB of source: beyond one launch's grid)
+    if (int rc = M.blk_cnt.grow(nblk)) return rc;
+    if (int rc = M.blk_base.grow(nblk)) return rc;
+    if (int rc = M.st.grow(1)) return rc;
+    if (int rc = M.h_st.grow(1)) return rc;
+    HIPCHK(hipMemsetAsync(M.st, 0, sizeof(zz_mem_state), st));
+    HIPCHK(hipMemsetAsync(&M.st->mstar, 0xFF, sizeof(unsigned long long), st));
+    hipLaunchKernelGGL(k_members_mark<false>, dim3((uint32_t)nblk), dim3(ZZ_MEM_THREADS), 0, st, src, src_len, (uint32_t*)M.blk_cnt,
+                       (const uint64_t*)nullptr, (uint64_t*)nullptr, (uint32_t*)nullptr);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(k_members_scan, dim3(1), dim3(ZZ_MEM_SCAN_THREADS), 0, st, (const uint32_t*)M.blk_cnt, nblk, (uint64_t*)M.blk_base,
+                       (zz_mem_state*)M.st);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(M.h_st, M.st, sizeof(zz_mem_state), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    const uint64_t ncand = M.h_st->candidates;
+    M.candidates = ncand;
+    if (ncand == 0 || ncand > 0x7FFFFFFFull) return serial();
+
+    // fill, check, hop (only if the check failed), slots: one readback for all of them
+    if (int rc = M.offs.grow(ncand)) return rc;
+    if (int rc = M.lens.grow(ncand)) return rc;
+    if (int rc = M.srcs.grow(ncand)) return rc;
+    if (int rc = M.dsts.grow(ncand)) return rc;
+    if (int rc = M.src_lens.grow(ncand)) return rc;
+    if (int rc = M.caps.grow(ncand)) return rc;
+    if (int rc = M.out_lens.grow(ncand)) return rc;
+    hipLaunchKernelGGL(k_members_mark<true>, dim3((uint32_t)nblk), dim3(ZZ_MEM_THREADS), 0, st, src, src_len, (uint32_t*)M.blk_cnt,
+                       (const uint64_t*)M.blk_base, (uint64_t*)M.offs, (uint32_t*)M.lens);
+    HIPCHK(hipGetLastError());
+    const uint64_t cgrid = (ncand + 255) / 256;
+    hipLaunchKernelGGL(k_members_check, dim3((uint32_t)(cgrid < 2048 ? cgrid : 2048)), dim3(256), 0, st, (const uint64_t*)M.offs,
+                       (const uint32_t*)M.lens, ncand, src_len, (zz_mem_state*)M.st);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(k_members_hop, dim3(1), dim3(ZZ_WAVE), 0, st, src, src_len, (uint64_t*)M.offs, (uint32_t*)M.lens, ncand,
+                       (zz_mem_state*)M.st);
+    HIPCHK(hipGetLastError());
+    zz_mem_slots q;
+    q.src = src; q.n = src_len; q.dst = dst; q.cap = cap; q.offs = M.offs; q.lens = M.lens;
+    q.srcs = M.srcs; q.src_lens = M.src_lens; q.dsts = M.dsts; q.caps = M.caps; q.st = M.st;
+    hipLaunchKernelGGL(k_members_slots, dim3(1), dim3(ZZ_MEM_SCAN_THREADS), 0, st, q);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(M.h_st, M.st, sizeof(zz_mem_state), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (!M.h_st->blocked) return serial();
+    const uint64_t members = M.h_st->members, mstar = M.h_st->mstar;
+    const bool have_mstar = mstar != ~0ull;
+    const uint64_t dealt = have_mstar ? mstar + 1 : members;
+
+    // decode: k_inflate_items over the dealt members, as zz_decode_batch_device launches it
+    zz_inf_items_params p;
+    p.srcs = (const uint8_t* const*)M.srcs.p; p.src_lens = M.src_lens; p.dsts = (uint8_t* const*)M.dsts.p; p.caps = M.caps;
+    p.out_lens = M.out_lens; p.status = nullptr; p.nitems = (uint32_t)dealt; p.format = ZZ_GZIP;
+    if (int rc = dec_items(c, p, st)) return rc;
+    const int v = zi_members_verdict(have_mstar, c->dec.items_host[0], c->dec.items_host[1]);
+    if (v == ZI_MEMBERS_SERIAL) return serial();
+    const int path = M.h_st->chain_bad ? 2 : 1;
+    if (v == ZI_MEMBERS_REJUDGE) {
+        // m* alone failed, for want of room -- on its cut-out bytes, which proves nothing about the bits behind them: the serial
+        // rule from m* on gives the verdict (for an honest file: one member's work, and the same answer)
+        const uint64_t at = M.h_st->mstar_src, off = M.h_st->mstar_dst;
+        return dec_members_serial(c, src + at, src_len - at, dst + off, cap - off, st, out_len, mstar, off, path);
+    }
+    M.path = path; M.members = dealt;
+    *out_len = M.h_st->total;
+    return ZZ_OK;
+}
+extern "C" int zz_ctx_last_decode_members_stats(const zz_ctx* c, uint64_t* members, uint64_t* candidates, int* path)
+{
+    if (!c) { set_err("null ctx"); return ZZ_E_ARG; }
+    if (members) *members = c->dec.mem.members;
+    if (candidates) *candidates = c->dec.mem.candidates;
+    if (path) *path = c->dec.mem.path;
     return ZZ_OK;
 }
 

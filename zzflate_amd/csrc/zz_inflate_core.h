@@ -692,4 +692,155 @@ ZZ_HD zi_item_result zi_item(L& w, const uint8_t* src, uint64_t src_len, uint8_t
     return r;
 }
 
+// ---- a member file: gzip members back to back (zz_decode_members_device; tests/cxx/inflate_members_harness.cpp) ----------
+// src[0, src_len) holds one or more gzip members (RFC 1952 2.2). Every member is judged as zi_item(format = gzip) judges a
+// single one; the first byte behind a member's trailer is the next member's 1f or the end of the file -- no padding, and an
+// empty file is no member file. The output is the members' bytes one after the other in dst[0, cap); members are judged in
+// file order and the first one that fails decides: ZI_ITEM_DATA, or ZI_ITEM_NOSPACE if its bytes pass `cap` before it is
+// found invalid. zi_members below IS this definition; the blocked path (zz_inflate_members.h) only reaches it sooner.
+struct zi_member_result {
+    int status;              // ZI_ITEM_*
+    uint64_t out;            // decoded bytes (0 unless status is ZI_ITEM_OK)
+    uint64_t used;           // source bytes the member took, trailer included (0 unless status is ZI_ITEM_OK)
+};
+// zi_item's body for gzip, but bytes may follow the trailer, and the member's length in the source comes back
+template <class L>
+ZZ_HD zi_member_result zi_member(L& w, const uint8_t* src, uint64_t src_len, uint8_t* dst, uint64_t cap, zi_tables& S,
+                                 uint32_t lane, uint32_t nl)
+{
+    zi_member_result r{ ZI_ITEM_DATA, 0, 0 };
+    const int64_t hl = zi_header(1, src, src_len);
+    if (hl < 0) return r;
+    const zi_view<const uint8_t> view{ src + hl, src_len - (uint64_t)hl };     // the blocks, the trailer and what follows
+    typename L::in_t in = w.input(view.p, view.n);
+    zi_out_linear<typename L::fence_t> o{ zi_view<uint8_t>{ dst, cap }, 0, lane, nl, {} };
+    S.kind = 0;
+    const zi_result R = zi_run(in, view, 0, o, S, ZI_RUN_STREAM, 0, lane, nl);
+    if (R.err) { if (R.err == ZI_E_SPACE) r.status = ZI_ITEM_NOSPACE; return r; }
+    if (R.end > view.n || view.n - R.end < 8) return r;                        // truncated trailer
+    const zi_view<const uint8_t> t{ view.p + R.end, 8 };
+    w.sync();
+    const uint32_t c = t[0] | ((uint32_t)t[1] << 8) | ((uint32_t)t[2] << 16) | ((uint32_t)t[3] << 24);
+    const uint32_t l = t[4] | ((uint32_t)t[5] << 8) | ((uint32_t)t[6] << 16) | ((uint32_t)t[7] << 24);
+    if (l != (uint32_t)R.out || zi_crc_lanes(w, zi_view<const uint8_t>{ dst, R.out }, R.out, lane, nl) != c) return r;
+    r.status = ZI_ITEM_OK; r.out = R.out; r.used = (uint64_t)hl + R.end + 8;
+    return r;
+}
+
+struct zi_members_result {
+    int status;              // ZI_ITEM_*
+    uint64_t out;            // decoded bytes of all members (0 unless status is ZI_ITEM_OK)
+    uint64_t members;        // members decoded (all of them when status is ZI_ITEM_OK)
+};
+// the loop over zi_member by one lane group, onto consecutive parts of dst, until the source is used up
+template <class L>
+ZZ_HD zi_members_result zi_members(L& w, const uint8_t* src, uint64_t src_len, uint8_t* dst, uint64_t cap, zi_tables& S,
+                                   uint32_t lane, uint32_t nl)
+{
+    zi_members_result r{ ZI_ITEM_DATA, 0, 0 };
+    while (src_len) {
+        const zi_member_result m = zi_member(w, src, src_len, dst, cap, S, lane, nl);
+        if (m.status != ZI_ITEM_OK) { r.status = m.status; r.out = 0; return r; }
+        src += m.used; src_len -= m.used;                      // (used <= src_len, out <= cap: the member read and wrote inside them)
+        dst += m.out; cap -= m.out;
+        r.out += m.out; ++r.members;
+        w.sync();                                              // every lane has finished with this member's input
+    }
+    if (r.members == 0) return r;                              // an empty file
+    r.status = ZI_ITEM_OK;
+    return r;
+}
+
+// The member length a header announces (BGZF: the extra subfield `BC`, SLEN 2, holds BSIZE = length - 1), or 0: h[0, n) must
+// begin 1f 8b 08 with FEXTRA set and no reserved flag bit, XLEN must lie inside n, and the FIRST subfield B C 2 among the
+// subfields inside XLEN counts -- others may stand in front of it (htslib's fixed offset 12 is not assumed). A subfield
+// that runs past XLEN, or a length that cannot hold this header, two bytes of blocks and the trailer, gives 0. The length
+// is a claim: whoever uses it checks that it stays inside the file, and zi_item judges the member it cuts out.
+ZZ_HD inline uint32_t zi_bc_len(const uint8_t* hp, uint64_t n)
+{
+    if (n < 12) return 0;
+    zi_view<const uint8_t> h{ hp, n };
+    if (h[0] != 0x1f || h[1] != 0x8b || h[2] != 8) return 0;
+    const uint32_t flg = h[3];
+    if (!(flg & 4) || (flg & 0xE0)) return 0;
+    const uint64_t xlen = h[10] | ((uint64_t)h[11] << 8);
+    const uint64_t end = 12 + xlen;
+    if (end > n) return 0;
+    for (uint64_t p = 12; p + 4 <= end;) {
+        const uint32_t slen = h[p + 2] | ((uint32_t)h[p + 3] << 8);
+        if (p + 4 + slen > end) return 0;
+        if (h[p] == 0x42 && h[p + 1] == 0x43 && slen == 2) {
+            const uint32_t len = (h[p + 4] | ((uint32_t)h[p + 5] << 8)) + 1u;
+            return len < end + 2 + 8 ? 0u : len;
+        }
+        p += 4 + slen;
+    }
+    return 0;
+}
+
+// -- the blocked path's rules (the kernels of zz_inflate_members.h and the harness's host restatement run these) --
+// CANDIDATES: every offset i with zi_bc_len(src + i, src_len - i) = len != 0 and i + len <= src_len, ascending.
+ZZ_HD inline uint32_t zi_members_candidate(const uint8_t* src, uint64_t src_len, uint64_t i)
+{
+    const uint32_t len = zi_bc_len(src + i, src_len - i);
+    return len && len <= src_len - i ? len : 0u;
+}
+// CHAIN CHECK, candidate j of m: is its link broken? The file is "blocked and clean" iff no link is: c_0 = 0, c_j + len_j =
+// c_(j+1), c_(m-1) + len_(m-1) = src_len. Then the chain of members from offset 0 (the hop below) is the candidate list itself:
+// by induction its j-th stop is c_j -- c_0 = 0 is the first stop, and from c_j the header there announces len_j (that is what
+// made c_j a candidate), so the next stop is c_j + len_j = c_(j+1), and the last stop's end is src_len.
+ZZ_HD inline bool zi_members_link_broken(uint64_t j, uint64_t m, uint64_t c, uint32_t len, uint64_t next, uint64_t src_len)
+{
+    if (j == 0 && c != 0) return true;
+    return c + len != (j + 1 < m ? next : src_len);
+}
+// HOP: one lane walks the chain from offset 0 with zi_bc_len at each stop and writes the member list (at most `max` members,
+// the number of candidates: every stop is one). Returns the members, or 0 when the file is not blocked: a stop at a non-header,
+// a length that passes the end, or more stops than candidates.
+ZZ_HD inline uint64_t zi_members_hop(const uint8_t* src, uint64_t src_len, uint64_t* offs, uint32_t* lens, uint64_t max)
+{
+    uint64_t pos = 0, m = 0;
+    while (pos < src_len) {
+        const uint32_t len = zi_members_candidate(src, src_len, pos);
+        if (!len || m >= max) return 0;
+        offs[m] = pos; lens[m] = len; ++m;
+        pos += len;
+    }
+    return m;
+}
+// SLOTS: ISIZE is a member's last four bytes; an exclusive scan of it gives the member's offset `off` in dst, and its slot is
+// min(ISIZE, what is left of cap) bytes -- so a lying ISIZE cannot make a member write into its neighbour's slot. m* is the
+// first member with off + ISIZE > cap: members behind it are not dealt, and m* itself, short of room, can only answer
+// ZI_ITEM_NOSPACE or ZI_ITEM_DATA (ZI_ITEM_OK needs ISIZE bytes decoded).
+// (a member of the list lies inside the file with its whole length, and zi_bc_len announces at least 22 bytes)
+ZZ_HD inline uint32_t zi_members_isize(const zi_view<const uint8_t>& src, uint64_t c, uint32_t len)
+{
+    const uint64_t t = c + len - 4;
+    return src[t] | ((uint32_t)src[t + 1] << 8) | ((uint32_t)src[t + 2] << 16) | ((uint32_t)src[t + 3] << 24);
+}
+ZZ_HD inline uint64_t zi_members_slot_cap(uint32_t isize, uint64_t off, uint64_t cap)
+{
+    const uint64_t left = cap - (cap < off ? cap : off);
+    return isize < left ? isize : left;
+}
+ZZ_HD inline bool zi_members_is_mstar(uint32_t isize, uint64_t off, uint64_t cap) { return off + isize > cap; }
+// VERDICT from what k_inflate_items counted over the dealt members: ZI_ITEM_OK (all fine, no m*), ZI_MEMBERS_REJUDGE (one
+// member out of room and nothing else wrong -- with an m* that member is m*, see above), or ZI_MEMBERS_SERIAL: the serial path
+// decides. ZI_ITEM_OK here implies the serial path's ZI_ITEM_OK with the same bytes: a member that zi_item accepts on exactly
+// src[c, c + len) with ISIZE bytes of room is what zi_member reads at c -- the same header, the same bits (a run that ENDS
+// inside its view never used a bit behind it), the trailer at the same place -- so the serial loop's stops are the c_j, its
+// offsets the scan's, and it ends at src_len.
+// A member that is out of room proves less. Its run did not end: zi_run asks for room for a literal before it looks whether
+// the literal's bits were there, so zi_item on the cut-out member may have read the zero bits behind the cut where zi_member
+// reads the next member's bytes -- and those may spell an end of block, a far distance or no code at all. So "no space" from
+// m* is a claim, not the verdict: members 0 .. m* - 1 are proven as above, and zi_members from m* on, over what is left of
+// source and room, gives the verdict (ZI_MEMBERS_REJUDGE). For an honest file that is one member's work.
+enum { ZI_MEMBERS_SERIAL = 1, ZI_MEMBERS_REJUDGE = 2 };
+ZZ_HD inline int zi_members_verdict(bool have_mstar, uint64_t n_data, uint64_t n_nospace)
+{
+    if (n_data == 0 && n_nospace == 0 && !have_mstar) return ZI_ITEM_OK;
+    if (n_data == 0 && n_nospace == 1 && have_mstar) return ZI_MEMBERS_REJUDGE;
+    return ZI_MEMBERS_SERIAL;
+}
+
 }  // namespace zz
