@@ -1,5 +1,6 @@
 """Extended seeded fuzz against the oracle (manual; the pytest suite runs a 120-case version): packet mode (cold, warm
 window, extended levels), the sequential stream into roomy and tight destinations, the callback form's chunks.
+The deterministic sweeps of copies across the encoders' internal boundaries are in the suite: tests/planted_cases.py, tests/test_gpu_planted.py.
 python tools/fuzz_gpu.py [cases] [seed] [--seconds S]     stops by itself after S seconds (exit 0 unless a case was bad), so that a
                                                           run under a time box ends with its own summary line, not with the box's kill
 ZZ_FUZZ_DUMP=<case> python tools/fuzz_gpu.py [cases] [seed]   (no GPU needed) writes that case's input to gpurun_out/fuzz_case_<case>.in"""
