@@ -133,6 +133,48 @@ int zz_encode_batch_device(zz_ctx* ctx, uint64_t nitems, const void* const* d_sr
                            void* const* d_dsts, const uint64_t* d_caps, uint64_t* d_out_lens,
                            int format, int level, uint32_t packet_size, void* hip_stream);
 
+/* One buffer to one blocked gzip (BGZF) file: what bgzip -d, samtools, tabix, gzip(1) and zz_decode_members_device (its
+ * parallel path, no index needed) read, a random-access format (member offset + offset inside the member), and one that
+ * concatenates: pieces written with ZZ_MEMBERS_NO_EOF and joined with `cat` are a file.
+ * The format rule: d_src[0, n) is cut into blocks of block_size bytes (0 = ZZ_MEMBERS_BLOCK, bgzip's; the last block is
+ * shorter; n == 0 gives no blocks). Member i is, in order,
+ *   the 18-byte header 1f 8b 08 04 00 00 00 00 00 ff 06 00 42 43 02 00 <BSIZE lo> <BSIZE hi>, BSIZE = the member's bytes - 1;
+ *   the body: exactly the raw-deflate stream zz_encode_batch_device(ZZ_DEFLATE, level, packet_size) writes for block i alone
+ *     (cold packets, the last one final, no match reaching in front of the block), D bytes -- or, when D > S, the level-0
+ *     stream of the same block at the same packet size, S bytes (the stored fallback), so that a file is never longer than
+ *     its stored form and no member passes 65,536 bytes;
+ *   CRC-32 of the block, then ISIZE, little-endian.
+ * Behind the last member comes bgzip's empty member of 28 bytes, unless ZZ_MEMBERS_NO_EOF is set (n == 0 writes that member
+ * alone, or nothing). *out_len = the file's bytes.
+ * d_member_offsets (optional, device memory, max_offsets entries) receives members + 1 file offsets: each member's first byte,
+ * then the offset where the empty last member starts (= the file's length under ZZ_MEMBERS_NO_EOF); they are written
+ * whenever the call gets as far as its encode, also when the file then does not fit.
+ *   ZZ_E_ARG, before anything is launched: a null context (*out_len = ~0 where there is one), a null d_src with n > 0, a null
+ *     d_dst with cap > 0, a null out_len, an unfinished zz_encode_device_async on the context; block_size above 65,536,
+ *     packet_size above 32,768, or a pair whose full stored member, 18 + S(block_size, packet_size) + 8, passes 65,536 bytes
+ *     (65,280 with packets of 32,768 or 4,096 is accepted, with packets of 1,000 it is not); max_offsets < members + 1; more
+ *     than 2^31 - 1 members or packets.
+ *   ZZ_E_LEVEL: level outside 0..3.   ZZ_E_UNSUPPORTED: the context has a warm window or the extended levels switched on.
+ *   ZZ_E_NOSPACE: the file does not fit cap; *out_len = ~0 and no byte of d_dst is written (decided on the device from the
+ *     scanned sizes before any pass stores).
+ * Synchronous: the host reads one small record, whatever the member count, and device-side consumers of d_dst wait for the
+ * call. Like a batch it is not a "last call" for zz_verify_last_device, zz_packet_extent_device and zz_packet_index_device,
+ * and it leaves the decode state alone. Workspace: a batch's over the same blocks, plus 25 bytes per member. */
+enum { ZZ_MEMBERS_NO_EOF = 1 };
+#define ZZ_MEMBERS_BLOCK 65280u
+int zz_encode_members_device(zz_ctx* ctx, const void* d_src, uint64_t n, void* d_dst, uint64_t cap, uint64_t* out_len,
+                             int level, uint32_t block_size, uint32_t packet_size, int flags,
+                             uint64_t* d_member_offsets, uint64_t max_offsets, void* hip_stream);
+/* (host, no device) the largest file zz_encode_members_device can write for these arguments -- every member stored; ~0 for
+ * sizes the call refuses */
+uint64_t zz_encode_members_bound(uint64_t n, uint32_t block_size, uint32_t packet_size, int flags);
+/* (host, no device) the header of a member of member_bytes bytes (1..65536) in all; returns 18 */
+int zz_members_header(uint32_t member_bytes, uint8_t out[18]);
+/* what the last zz_encode_members_device wrote: its members (the blocks, without the empty last member) and how many of them
+ * took the stored fallback (level 0: none -- every member is its level-0 stream). Both are 0 after a refused call and when
+ * there has been no call. */
+int zz_ctx_last_encode_members_stats(const zz_ctx* ctx, uint64_t* members, uint64_t* stored_members);
+
 /* The same call in two halves: zz_encode_device_async enqueues the whole pipeline on `hip_stream` and returns without
  * waiting; zz_encode_finish waits for it and returns the length (or the error, as zz_encode_device). With two contexts
  * on two streams, call i+1 can be enqueued before call i is finished: its encode kernel fills the CUs call i's last

@@ -17,9 +17,12 @@ from . import build as _build
 __all__ = [
     "Format", "Config", "ZzFlateError", "ZzFlateEncode", "ZzFlateEncodeToCallback", "adler32x", "combine",
     "crc32", "crc32_combine", "bound", "Context", "lib", "DEFAULT_PACKET", "generate_host", "header", "trailer",
+    "MEMBERS_BLOCK", "members_bound", "members_header", "gzi_bytes",
 ]
 
 DEFAULT_PACKET = 32768
+MEMBERS_BLOCK = 65280            # input bytes per member of a blocked gzip file (bgzip's)
+MEMBERS_NO_EOF = 1
 _ERR = (1 << 64) - 1
 
 
@@ -75,6 +78,10 @@ def _load():
         "zz_encode_device": (i32, [vp, vp, u64, vp, u64, pu64, i32, i32, u32, vp]),
         "zz_encode_device_async": (i32, [vp, vp, u64, vp, u64, i32, i32, u32, vp]),
         "zz_encode_batch_device": (i32, [vp, u64, vp, vp, vp, vp, vp, i32, i32, u32, vp]),
+        "zz_encode_members_device": (i32, [vp, vp, u64, vp, u64, pu64, i32, u32, u32, i32, vp, u64, vp]),
+        "zz_encode_members_bound": (u64, [u64, u32, u32, i32]),
+        "zz_members_header": (i32, [u32, vp]),
+        "zz_ctx_last_encode_members_stats": (i32, [vp, pu64, pu64]),
         "zz_encode_finish": (i32, [vp, pu64]),
         "zz_encode_stream_device": (i32, [vp, vp, u64, vp, u64, pu64, i32, i32, vp]),
         "zz_encode_ranges_device": (i32, [vp, vp, u64, vp, u64, pu64, i32, i32, u32, vp]),
@@ -213,6 +220,38 @@ def trailer(format, cks_total, n):
     buf = ctypes.create_string_buffer(8)
     k = lib.zz_trailer(int(format), cks_total, n, buf)
     return buf.raw[:k]
+
+
+def members_bound(n, block_size=MEMBERS_BLOCK, packet_size=DEFAULT_PACKET, eof=True):
+    """The largest file ``Context.encode_members`` can write for ``n`` input bytes (every member stored)."""
+    b = lib.zz_encode_members_bound(n, block_size, packet_size, 0 if eof else MEMBERS_NO_EOF)
+    if b == _ERR:
+        raise ZzFlateError(E_ARG, "block size and packet size: a block's stored member must fit 65536 bytes")
+    return b
+
+
+def members_header(member_bytes):
+    """The 18-byte header of a blocked member of ``member_bytes`` bytes in all (header, body, CRC-32, ISIZE)."""
+    buf = ctypes.create_string_buffer(18)
+    k = lib.zz_members_header(member_bytes, buf)
+    if k < 0:
+        _check(k)
+    return buf.raw[:k]
+
+
+def gzi_bytes(offsets, n, block_size=MEMBERS_BLOCK):
+    """bgzip's ``.gzi`` index of a file ``Context.encode_members`` wrote from ``n`` input bytes: a little-endian u64 count, then
+    the pairs (compressed offset, uncompressed offset) of every member but the first. ``offsets`` is the host copy of the
+    call's offsets array (members + 1 entries)."""
+    import struct
+    offsets = [int(v) for v in offsets]
+    members = len(offsets) - 1
+    if members < 0 or members != -(-n // block_size):
+        raise ValueError(f"{len(offsets)} offsets do not describe {n} bytes in blocks of {block_size}")
+    out = [struct.pack("<Q", max(members - 1, 0))]
+    for i in range(1, members):
+        out.append(struct.pack("<QQ", offsets[i], i * block_size))
+    return b"".join(out)
 
 
 def generate_host(kind, seed, first_byte, n):
@@ -357,6 +396,34 @@ class Context:
         if rc not in (0, E_NOSPACE, E_DATA):
             _check(rc)
         return [None if v == -1 else v for v in out.cpu().tolist()], status.cpu().tolist()
+
+    def encode_members(self, src, n, dst, cap, level=1, block_size=MEMBERS_BLOCK, packet_size=DEFAULT_PACKET, eof=True, offsets=None,
+                       stream=None):
+        """One blocked gzip (BGZF) file from ``src[:n]``: members of ``block_size`` input bytes back to back, each announcing its
+        length, then bgzip's empty last member (``eof=False`` omits it: pieces that ``cat`` will join). bgzip, samtools, tabix,
+        ``gzip.decompress`` and ``decode_members`` (in parallel) read it. A member is the raw-deflate stream ``encode_batch``
+        writes for its block, or the block's level-0 stream where that is shorter. ``offsets``: an int64 tensor on this
+        context's device that receives members + 1 file offsets (``gzi_bytes`` turns its host copy into a ``.gzi`` index).
+        Returns the file's length; raises ZzFlateError (E_NOSPACE: it does not fit ``cap``, nothing is written). Levels 0..3."""
+        out = ctypes.c_uint64(0)
+        st = self._stream() if stream is None else stream
+        op, on = None, 0
+        if offsets is not None:
+            import torch
+            if not isinstance(offsets, torch.Tensor) or offsets.dtype != torch.int64 or offsets.dim() != 1 or not offsets.is_contiguous():
+                raise TypeError("offsets must be a contiguous one-dimensional int64 tensor")
+            if offsets.device.type != "cuda" or offsets.device.index != self.device:
+                raise ValueError(f"offsets must live on this context's device (cuda:{self.device}), not {offsets.device}")
+            op, on = offsets.data_ptr(), offsets.numel()
+        _check(lib.zz_encode_members_device(self._h, self._ptr(src), n, self._ptr(dst), cap, ctypes.byref(out), int(level), block_size,
+                                            packet_size, 0 if eof else MEMBERS_NO_EOF, op, on, st))
+        return out.value
+
+    def last_encode_members_stats(self):
+        """(members, members that took the stored fallback) of the last ``encode_members``; (0, 0) after a refused call."""
+        m, stored = ctypes.c_uint64(0), ctypes.c_uint64(0)
+        _check(lib.zz_ctx_last_encode_members_stats(self._h, ctypes.byref(m), ctypes.byref(stored)))
+        return m.value, stored.value
 
     def encode_async(self, src, n, dst, cap, format=Format.Zlib, level=1, packet_size=DEFAULT_PACKET, stream=None):
         """Enqueue ``encode`` on ``stream`` without waiting; ``finish()`` returns the byte count. One call per context at a

@@ -33,6 +33,7 @@
 #include "zz_inflate_ranges.h"
 #include "zz_inflate_members.h"
 #include "zz_batch.h"
+#include "zz_members_write.h"
 
 using namespace zz;
 
@@ -147,6 +148,12 @@ struct zz_ctx {
         zz_buf<zz_batch_desc> desc;
         zz_buf<zz_batch_totals> d_tot; zz_pin<zz_batch_totals> h_tot;
     } bat;
+    // zz_encode_members_device: per member (source, length; file offset (+1 entry), stored flag), what the host reads, the last call's stats
+    struct {
+        zz_buf<const uint8_t*> srcs; zz_buf<uint64_t> ns, moff; zz_buf<uint8_t> stored;
+        zz_buf<zz_mw_state> d_st; zz_pin<zz_mw_state> h_st;
+        uint64_t members = 0, stored_members = 0;
+    } mw;
     zz_buf<uint32_t> d_work;             // level 2: packet counter of the persistent workgroups
     zz_buf<uint64_t> d_log;              // sequential stream, callback form: EnsureOutputLength log, two words per entry
     // a call that has been enqueued but not waited for (zz_encode_device_async .. zz_encode_finish)
@@ -292,7 +299,8 @@ extern "C" uint64_t zz_ctx_workspace_bytes(const zz_ctx* c)
 {
     if (!c) return 0;
     return c->slots.bytes() + c->sizes.bytes() + c->offsets.bytes() + c->cks.bytes() + c->l2_scratch.bytes() + c->stage_in.bytes() +
-           c->stage_out.bytes() + c->bat.first.bytes() + c->bat.slotbase.bytes() + c->bat.tails.bytes() + c->bat.desc.bytes();
+           c->stage_out.bytes() + c->bat.first.bytes() + c->bat.slotbase.bytes() + c->bat.tails.bytes() + c->bat.desc.bytes() +
+           c->mw.srcs.bytes() + c->mw.ns.bytes() + c->mw.moff.bytes() + c->mw.stored.bytes();
 }
 // diagnostic (not part of the public header): workgroups of the level's encode kernel the runtime places on one CU
 extern "C" int zz_debug_occupancy(int level)
@@ -1878,6 +1886,164 @@ extern "C" int zz_encode_batch_device(zz_ctx* c, uint64_t nitems, const void* co
     HIPCHK(hipSetDevice(c->device));
     return encode_batch(c, (uint32_t)nitems, (const uint8_t* const*)d_srcs, d_ns, (uint8_t* const*)d_dsts, d_caps, d_out_lens, format,
                         level, P, (hipStream_t)hip_stream, false);
+}
+
+// ---- one buffer to a blocked gzip (BGZF) file (zz_members_write.h) ----------------------------------------------------------
+// bytes of the file when every member takes its stored form: the bound, and what mw_geometry_ok keeps below 65,536 per member
+static uint64_t members_stored_bytes(uint64_t n, uint32_t B, uint32_t P)
+{
+    if (n == 0) return 0;
+    const uint64_t m = (n + B - 1) / B;
+    return (m - 1) * (ZZ_MW_HEADER + l0_item_bytes(B, P) + ZZ_MW_TRAILER) + ZZ_MW_HEADER + l0_item_bytes(n - (m - 1) * B, P) + ZZ_MW_TRAILER;
+}
+static bool members_sizes(uint32_t& B, uint32_t& P)
+{
+    if (B == 0) B = ZZ_MEMBERS_BLOCK;
+    if (P == 0) P = ZZ_DEFAULT_PACKET;
+    return P <= ZZ_MAX_PACKET_SIZE && mw_geometry_ok(B, P);
+}
+extern "C" uint64_t zz_encode_members_bound(uint64_t n, uint32_t B, uint32_t P, int flags)
+{
+    if (!members_sizes(B, P)) return ~0ull;
+    return members_stored_bytes(n, B, P) + ((flags & ZZ_MEMBERS_NO_EOF) ? 0 : ZZ_MW_EOF);
+}
+extern "C" int zz_members_header(uint32_t member_bytes, uint8_t out[18])
+{
+    if (!out || member_bytes == 0 || member_bytes > ZZ_MW_MAX_MEMBER) { set_err("a member has 1..65536 bytes"); return ZZ_E_ARG; }
+    mw_header(member_bytes, out);
+    return ZZ_MW_HEADER;
+}
+
+static int encode_members(zz_ctx* c, const uint8_t* d_src, uint64_t n, uint8_t* d_dst, uint64_t cap, uint64_t* out_len, int level,
+                          uint32_t B, uint32_t P, int flags, uint64_t* d_member_offsets, hipStream_t st, bool one_parser)
+{
+    auto& W = c->mw;
+    c->have_time = false;
+    c->have_last = false;            // verify / extent / index describe single calls only
+    c->idx_empty = false;
+    // members, packets and slot bytes in closed form: the host reads nothing back before the launches
+    const uint32_t m = (uint32_t)((n + B - 1) / B), ppm = (B + P - 1) / P;
+    const uint32_t last = m ? (uint32_t)(n - (uint64_t)(m - 1) * B) : 0;
+    const uint32_t npk = m ? (m - 1) * ppm + (last + P - 1) / P : 0;
+    const auto block_slots = [&](uint32_t len) -> uint64_t {
+        const uint32_t k = (len + P - 1) / P;
+        return level ? (uint64_t)(k - 1) * zz_slot_stride(level, P) + zz_slot_stride(level, len - (k - 1) * P) : 0;
+    };
+    const uint64_t full_slots = block_slots(B);
+    const uint64_t slot_bytes = m ? (uint64_t)(m - 1) * full_slots + block_slots(last) + 256 : 0;     // (+ room behind the last slot)
+    const uint64_t mm = (uint64_t)m + 1;
+    if (mm * 128 > c->bat.tails.cap) {   // (the last of the three, as in encode_batch)
+        c->bat.first.release(); c->bat.slotbase.release(); c->bat.tails.release();
+        if (int rc = c->bat.first.grow(mm)) return rc;
+        if (int rc = c->bat.slotbase.grow(mm)) return rc;
+        if (int rc = c->bat.tails.grow(mm * 128)) return rc;
+    }
+    if (int rc = W.srcs.grow(mm)) return rc;
+    if (int rc = W.ns.grow(mm)) return rc;
+    if (int rc = W.moff.grow(mm)) return rc;
+    if (int rc = W.stored.grow(mm)) return rc;
+    if (int rc = W.d_st.grow(1)) return rc;
+    if (int rc = W.h_st.grow(1)) return rc;
+    if (npk) {
+        int rc = ensure_workspace(c, 0, npk, 0);                                  // sizes, offsets, checksum partials
+        if (rc) return rc;
+        if (level != 0 && (rc = c->slots.grow(slot_bytes))) return rc;
+        if (level >= 2 && (rc = c->l2_scratch.grow(l2_scratch_bytes(npk, 0, P)))) return rc;
+        if ((rc = c->bat.desc.grow(npk))) return rc;
+    }
+    HIPCHK(hipMemsetAsync(c->d_err, 0, sizeof(uint32_t), st));
+    const launch_plan plan = plan_launch(c, level, 0, 0, one_parser);
+    zz_mw_params Q;
+    Q.src = d_src; Q.n = n; Q.dst = d_dst; Q.cap = cap; Q.B = B; Q.P = P; Q.members = m; Q.ppm = ppm;
+    Q.eof = (flags & ZZ_MEMBERS_NO_EOF) ? 0 : ZZ_MW_EOF; Q.level = level; Q.full_slots = full_slots;
+    Q.srcs = W.srcs; Q.ns = W.ns; Q.first = c->bat.first; Q.desc = c->bat.desc;
+    Q.sizes = c->sizes; Q.offsets = c->offsets; Q.cks = c->cks; Q.slots = c->slots;
+    Q.moff = W.moff; Q.stored = W.stored; Q.st = W.d_st; Q.user_offsets = d_member_offsets;
+    if (npk) {
+        hipLaunchKernelGGL(k_mw_items, dim3((m + 1 + 255) / 256), dim3(256), 0, st, Q);
+        hipLaunchKernelGGL(k_mw_desc, dim3((npk + 255) / 256), dim3(256), 0, st, Q, npk);
+        zz_batch_map M;
+        M.desc = c->bat.desc; M.srcs = W.srcs; M.ns = W.ns; M.first = c->bat.first; M.tails = c->bat.tails; M.npk = npk; M.level = level;
+        if (level >= 1)
+            hipLaunchKernelGGL(k_batch_tails, dim3(m < 65536 ? m : 65536), dim3(128), 0, st, (const uint8_t* const*)W.srcs.p, (const uint64_t*)W.ns, m,
+                               (uint8_t*)c->bat.tails);
+        zz_packet_params pp = {};
+        pp.packet_size = P; pp.cks_kind = ZZ_CKS_CRC; pp.slots = c->slots; pp.sizes = c->sizes; pp.cks = c->cks; pp.err = c->d_err;
+        pp.prof = c->d_prof; pp.warm = 0; pp.last_is_final = 1;
+        pp.npk = npk;
+        pp.dbg_viol = plan.order_checked && take_forced_violation() ? 1 : 0;
+        if (c->timing) HIPCHK(hipEventRecord(c->ev0, st));
+        hipLaunchKernelGGL(k_crc32_packets_batch, dim3(npk < 2048 ? npk : 2048), dim3(ZZ_CRC_THREADS), 0, st, pp, M);
+        pp.cks_kind = ZZ_CKS_NONE;           // the encode kernels must not overwrite the CRC partials
+        if (level == 1) {
+            if (plan.l1p) hipLaunchKernelGGL(k_encode_l1p_batch, dim3(npk), dim3(ZZ_L1P_THREADS), 0, st, pp, M);
+            else hipLaunchKernelGGL(k_encode_l1_batch, dim3(npk), dim3(ZZ_L1_THREADS), 0, st, pp, M);
+        } else if (level >= 2) {
+            launch_level2(pp, c->l2_scratch, c->d_work, st, 0, plan.l2p, &M);
+        }
+        if (c->timing) { HIPCHK(hipEventRecord(c->ev1, st)); c->have_time = true; }
+        if (level != 0) hipLaunchKernelGGL(k_scan_sizes, dim3(1), dim3(ZZ_SCAN_THREADS), 0, st, c->sizes, npk, c->offsets, c->d_res);
+    }
+    // the members' sizes and places, and the room check: nothing below stores a byte unless the file fits
+    hipLaunchKernelGGL(k_mw_sizes, dim3(1), dim3(ZZ_SCAN_THREADS), 0, st, Q);
+    const uint32_t per_fin = ZZ_MW_FIN_THREADS / ZZ_WAVE, gf = (m + per_fin - 1) / per_fin;
+    hipLaunchKernelGGL(k_mw_finalize, dim3(gf < 65536 ? (gf ? gf : 1) : 65536), dim3(ZZ_MW_FIN_THREADS), 0, st, Q);
+    if (npk && level != 0) {
+        const uint32_t per_cp = ZZ_MW_COMPACT_THREADS / ZZ_WAVE, gc = (npk + per_cp - 1) / per_cp;
+        hipLaunchKernelGGL(k_mw_compact, dim3(gc < 65536 ? gc : 65536), dim3(ZZ_MW_COMPACT_THREADS), 0, st, Q, npk);
+    }
+    if (npk) hipLaunchKernelGGL(k_mw_stored, dim3(npk < 16384 ? npk : 16384), dim3(256), 0, st, Q, npk);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(W.h_st, W.d_st, sizeof(zz_mw_state), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(c->h_err, c->d_err, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    const int ew = read_err_word(c, plan.order_checked);
+    if (ew == ERR_RERUN)                 // as encode_batch: the whole call runs again on the one-parser kernels
+        return encode_members(c, d_src, n, d_dst, cap, out_len, level, B, P, flags, d_member_offsets, st, true);
+    if (ew) return ew;
+    if (!W.h_st->fits) {
+        set_err("the file (" + std::to_string(W.h_st->total + Q.eof) + " bytes) does not fit the destination");
+        return ZZ_E_NOSPACE;
+    }
+    W.members = m; W.stored_members = W.h_st->stored;
+    *out_len = W.h_st->total + Q.eof;
+    return ZZ_OK;
+}
+
+extern "C" int zz_encode_members_device(zz_ctx* c, const void* d_src, uint64_t n, void* d_dst, uint64_t cap, uint64_t* out_len,
+                                        int level, uint32_t block_size, uint32_t packet_size, int flags,
+                                        uint64_t* d_member_offsets, uint64_t max_offsets, void* hip_stream)
+{
+    if (out_len) *out_len = ~0ull;
+    if (!c) { set_err("null ctx"); return ZZ_E_ARG; }
+    c->mw.members = 0; c->mw.stored_members = 0;
+    if (!out_len) { set_err("null out_len"); return ZZ_E_ARG; }
+    if (!d_src && n) { set_err("null source"); return ZZ_E_ARG; }
+    if (!d_dst && cap) { set_err("null destination"); return ZZ_E_ARG; }
+    if (call_pending(c)) return ZZ_E_ARG;
+    if (c->warm || c->extended) {
+        set_err("members take cold packets of levels 0..3: switch the warm window and the extended levels off on this context");
+        return ZZ_E_UNSUPPORTED;
+    }
+    if (level < 0 || level > 3) { set_err("level must be 0..3 (zzflate.cpp:201,230)"); return ZZ_E_LEVEL; }
+    uint32_t B = block_size, P = packet_size;
+    if (!members_sizes(B, P)) {
+        set_err("block size must be 1..65536, packet size 1..32768, and a block's stored member (26 bytes + its level-0 stream) at most 65536 bytes");
+        return ZZ_E_ARG;
+    }
+    const uint64_t m = (n + B - 1) / B;
+    if (m > 0x7FFFFFFFull || m * ((B + P - 1) / P) > 0x7FFFFFFFull) { set_err("too many members or packets for one call"); return ZZ_E_ARG; }
+    if (d_member_offsets && max_offsets < m + 1) { set_err("the offsets array takes members + 1 entries"); return ZZ_E_ARG; }
+    HIPCHK(hipSetDevice(c->device));
+    return encode_members(c, (const uint8_t*)d_src, n, (uint8_t*)d_dst, cap, out_len, level, B, P, flags, d_member_offsets,
+                          (hipStream_t)hip_stream, false);
+}
+extern "C" int zz_ctx_last_encode_members_stats(const zz_ctx* c, uint64_t* members, uint64_t* stored_members)
+{
+    if (!c) { set_err("null ctx"); return ZZ_E_ARG; }
+    if (members) *members = c->mw.members;
+    if (stored_members) *stored_members = c->mw.stored_members;
+    return ZZ_OK;
 }
 
 // ---- a batch of independent streams back to their bytes (zz_inflate.h, k_inflate_items) ---------------------------------------

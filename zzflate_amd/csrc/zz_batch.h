@@ -122,7 +122,7 @@ struct zz_l0_batch_params {
     const uint64_t* caps;    // per item: its capacity
     int format;
 };
-__device__ __forceinline__ uint64_t l0_item_bytes(uint64_t n, uint32_t P)
+__host__ __device__ inline uint64_t l0_item_bytes(uint64_t n, uint32_t P)
 {
     if (n == 0) return 5;                                  // one empty stored final block
     const uint64_t npk = (n + P - 1) / P;
@@ -192,6 +192,29 @@ struct zz_batch_join {
     int format, cks_kind, level;
 };
 
+// The CRC-32 of an item from its packets' partials (cks[k].a: packet k with start value 0), by one wavefront: every lane folds a
+// run of packets, then shifts it by the bytes behind the run; the runs XOR together. xp = gf2_xpow8(P).
+__device__ __forceinline__ uint32_t batch_crc_fold(const zz_cks* cks, uint32_t npk, uint64_t n, uint32_t P, uint32_t xp, uint32_t lane)
+{
+    const uint32_t per = (npk + ZZ_WAVE - 1) / ZZ_WAVE;
+    uint32_t k0 = lane * per, k1 = k0 + per;
+    if (k0 > npk) k0 = npk;
+    if (k1 > npk) k1 = npk;
+    uint32_t a = 0;
+    for (uint32_t k = k0; k < k1; ++k) {
+        const uint64_t off = (uint64_t)k * P;
+        const uint64_t l = (n - off) < P ? (n - off) : P;
+        a = gf2_mulmod(a, l == P ? xp : gf2_xpow8(l)) ^ cks[k].a;
+    }
+    if (k0 < k1) {
+        const uint64_t e = (uint64_t)k1 * P;
+        a = gf2_mulmod(a, gf2_xpow8(n - (e < n ? e : n)));
+    }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) a ^= __shfl_xor(a, o);
+    return a;
+}
+
 // one wavefront per item: what k_cks_reduce and k_finalize do for one stream
 #define ZZ_BATCH_FIN_THREADS 256
 __global__ __launch_bounds__(ZZ_BATCH_FIN_THREADS) void k_batch_finalize(zz_batch_join J)
@@ -225,24 +248,7 @@ __global__ __launch_bounds__(ZZ_BATCH_FIN_THREADS) void k_batch_finalize(zz_batc
             const uint32_t part = ((uint32_t)(sB % ZZ_ADLER_MOD) << 16) | (uint32_t)(sA % ZZ_ADLER_MOD);
             cks = adler_combine(1u, part, n);
         } else if (J.cks_kind == ZZ_CKS_CRC) {
-            // every lane folds a run of packets, then shifts it by the bytes behind the run; the runs XOR together
-            const uint32_t per = (npk + ZZ_WAVE - 1) / ZZ_WAVE;
-            uint32_t k0 = lane * per, k1 = k0 + per;
-            if (k0 > npk) k0 = npk;
-            if (k1 > npk) k1 = npk;
-            uint32_t a = 0;
-            for (uint32_t k = k0; k < k1; ++k) {
-                const uint64_t off = (uint64_t)k * P;
-                const uint64_t l = (n - off) < P ? (n - off) : P;
-                a = gf2_mulmod(a, l == P ? xp : gf2_xpow8(l)) ^ J.cks[f + k].a;
-            }
-            if (k0 < k1) {
-                const uint64_t e = (uint64_t)k1 * P;
-                a = gf2_mulmod(a, gf2_xpow8(n - (e < n ? e : n)));
-            }
-#pragma unroll
-            for (int o = 32; o >= 1; o >>= 1) a ^= __shfl_xor(a, o);
-            cks = a;
+            cks = batch_crc_fold(J.cks + f, npk, n, P, xp, lane);
         }
         if (lane == 0) {
             if (total > J.caps[i]) {
