@@ -41,5 +41,16 @@ for kind in ["random", "zeros", "words", "ab", "runs", "period"]:
                 bad += 1
                 i = next((i for i in range(min(len(got), len(want))) if got[i] != want[i]), None)
                 print("MISMATCH", kind, n, lvl, len(got), len(want), i)
+for kind in ["ff", "impulse"]:       # the largest checksum sums, and one position's weight (tests/join_cases.py)
+    for n in (1, 5, 300, 70000):
+        d = b"\xFF" * n if kind == "ff" else bytes(n - 1 - n // 3) + b"\xFF" + bytes(n // 3)
+        for lvl in levels:
+            for fmt in (0, 1):
+                got = enc(d, fmt, lvl); want = o.encode_packets(d, fmt, lvl, 32768, warm if lvl else 0)
+                tail = zlib.adler32(d).to_bytes(4, "big") if fmt == 0 else zlib.crc32(d).to_bytes(4, "little") + n.to_bytes(4, "little")
+                if got != want or not got.endswith(tail):
+                    bad += 1
+                    i = next((i for i in range(min(len(got), len(want))) if got[i] != want[i]), None)
+                    print("MISMATCH", kind, n, lvl, fmt, len(got), len(want), i)
 print("bad", bad)
 sys.exit(1 if bad else 0)
