@@ -180,3 +180,24 @@ def test_stream_level2_one_position_at_a_time_everywhere(oracle, corpus, tmp_pat
         assert rc == 0
         assert h_(dst[:out.value].cpu().numpy().tobytes()) == G["files"][fname]["whole"]["0"]["2"], fname
     L.zz_ctx_destroy(h)
+
+
+def test_packet_index_after_a_sequential_call_refuses():
+    """The packet index is the last PACKET-MODE call's: after an empty packet-mode call (whose index has two entries) and then a
+    sequential stream or a ranges call on the same context there is none, as after a non-empty packet-mode call."""
+    import ctypes
+    import torch
+    d = synth("words", 1000, 3)
+    ctx = zz.Context(0)
+    src = torch.frombuffer(bytearray(d), dtype=torch.uint8).cuda()
+    cap = 2 * len(d) + 1024
+    dst = torch.zeros(cap, dtype=torch.uint8, device="cuda")
+    entries = ctypes.c_uint64(0)
+    for call in (lambda: ctx.encode_stream(src, len(d), dst, cap, zz.Format.Zlib, 1),
+                 lambda: ctx.encode_ranges(src, len(d), dst, cap, 2, zz.Format.Zlib, 2)):
+        ctx.encode(src, 0, dst, cap, zz.Format.Zlib, 1)
+        assert ctx.packet_index().numel() == 2
+        w = call()
+        assert zlib.decompress(dst[:w].cpu().numpy().tobytes()) == d
+        assert zz.lib.zz_packet_index_device(ctx._h, None, 0, ctypes.byref(entries), None) == -4
+    ctx.close()

@@ -58,6 +58,13 @@ def encode_ranges(torch, ctx, d, lvl, count):
     return dst[:w].cpu().numpy().tobytes()
 
 
+def encode_members(torch, ctx, d, lvl):
+    cap = zz.members_bound(len(d))
+    dst = torch.zeros(cap, dtype=torch.uint8, device="cuda")
+    w = ctx.encode_members(dev(torch, d), len(d), dst, cap, level=lvl)
+    return dst[:w].cpu().numpy().tobytes()
+
+
 def decode(torch, ctx, s, n):
     dst = torch.zeros(n + 1, dtype=torch.uint8, device="cuda")
     w = ctx.decode(dev(torch, s), len(s), dst, n + 1, ZLIB)
@@ -79,6 +86,8 @@ def steps(torch, text):
     return [
         ("encode_l2", lambda c, o: encode(torch, c, text[:300000], ZLIB, 2, 4096)),
         ("batch_l1", lambda c, o: encode_batch(torch, c, items, ZLIB, 1)),
+        ("members_l1", lambda c, o: encode_members(torch, c, text[:200000], 1)),   # on item buffers the larger batch has grown
+        ("batch_l2_gzip", lambda c, o: encode_batch(torch, c, items, GZIP, 2)),     # and a batch on what members left there
         ("stream_l2", lambda c, o: encode_stream(torch, c, text[:100000], 2)),
         ("ranges_l2", lambda c, o: encode_ranges(torch, c, text[:200000], 2, 3)),
         ("encode_l1_gzip", lambda c, o: encode(torch, c, text[:1000], GZIP, 1)),

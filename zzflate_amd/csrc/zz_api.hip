@@ -142,7 +142,7 @@ struct zz_ctx {
     zz_verify_params last = {};  bool have_last = false;
     bool idx_empty = false; uint64_t idx_empty_bytes = 0;   // the last packet-mode call had an empty input (zz_packet_index_device)
     zz_buf<unsigned long long> d_verify;
-    // zz_encode_batch_device: per item (first packet, slot base, tail: grown together), per packet (descriptor), the plan's totals
+    // zz_encode_batch_device: per item (first packet, slot base, tail: ensure_items), per packet (descriptor), the plan's totals
     struct {
         zz_buf<uint32_t> first; zz_buf<uint64_t> slotbase; zz_buf<uint8_t> tails;     // (tails: 128 bytes per item)
         zz_buf<zz_batch_desc> desc;
@@ -591,6 +591,24 @@ static int ensure_workspace(zz_ctx* c, int level, uint64_t npk, uint32_t stride,
     if (level >= 2) if (int rc = c->l2_scratch.grow(l2_scratch_bytes((uint32_t)npk, xdepth, P))) return rc;
     return ZZ_OK;
 }
+// batches and members, per item: first packet and slot base (`items_plus_one` entries), tail (128 bytes each) -- grown together
+static int ensure_items(zz_ctx* c, uint64_t items_plus_one)
+{
+    if (items_plus_one * 128 <= c->bat.tails.cap) return ZZ_OK;    // (the last of the three, as in ensure_workspace)
+    c->bat.first.release(); c->bat.slotbase.release(); c->bat.tails.release();
+    if (int rc = c->bat.first.grow(items_plus_one)) return rc;
+    if (int rc = c->bat.slotbase.grow(items_plus_one)) return rc;
+    return c->bat.tails.grow(items_plus_one * 128);
+}
+// batches and members, per packet: sizes, offsets and checksum partials, the items' slots end to end (slot_bytes == 0: none),
+// level 2's scratch, the descriptors
+static int ensure_batch_workspace(zz_ctx* c, int level, uint32_t npk, uint64_t slot_bytes, uint32_t P)
+{
+    if (int rc = ensure_workspace(c, 0, npk, 0)) return rc;
+    if (int rc = c->slots.grow(slot_bytes)) return rc;
+    if (level >= 2) if (int rc = c->l2_scratch.grow(l2_scratch_bytes(npk, 0, P))) return rc;
+    return c->bat.desc.grow(npk);
+}
 // staging of the host-buffer entry points and of zz_encode_multi_device's pulls (64 bytes of room behind what was asked for)
 static int ensure_stage(zz_ctx* c, uint64_t in_bytes, uint64_t out_bytes)
 {
@@ -659,6 +677,83 @@ static int read_err_word(zz_ctx* c, bool order_checked)
 extern "C" int zz_debug_l1_kernel(const zz_ctx* c) { return (c && plan_launch(c, 1, 0, 0, false).l1p) ? 2 : 1; }
 // (the same for levels 2,3: 2 = k_encode_l2p, 1 = the two-wavefront k_encode_l2_t<0, false>)
 extern "C" int zz_debug_l2_kernel(const zz_ctx* c) { return (c && plan_launch(c, 2, 0, 0, false).l2p) ? 2 : 1; }
+
+// ---- what the encode drivers share ----------------------------------------------------------------------------------------
+// Every encode call starts here: whatever zz_ctx_last_kernel_ms, zz_verify_last_device / zz_packet_extent_device and
+// zz_packet_index_device could look at is about to change (they describe single packet-mode calls only).
+static void begin_encode_call(zz_ctx* c) { c->have_time = false; c->have_last = false; c->idx_empty = false; }
+
+// Checksum partials of pp's packets by pp.cks_kind (none: nothing), and their fold into d_cks_total. CRC: persistent workgroups (the table
+// and the shift constants are built once per block); Adler: the grid's cap is the caller's (the packet kernels make their own Adler partials).
+static void launch_cks_partials(const zz_packet_params& pp, uint32_t adler_cap, hipStream_t st)
+{
+    if (pp.cks_kind == ZZ_CKS_CRC) hipLaunchKernelGGL(k_crc32_packets, dim3(pp.npk < 2048 ? pp.npk : 2048), dim3(ZZ_CRC_THREADS), 0, st, pp);
+    else if (pp.cks_kind == ZZ_CKS_ADLER) hipLaunchKernelGGL(k_adler_packets, dim3(pp.npk < adler_cap ? pp.npk : adler_cap), dim3(ZZ_WAVE), 0, st, pp);
+}
+static void launch_cks_fold(zz_ctx* c, const zz_packet_params& pp, int cks_kind, hipStream_t st)      // (pp.cks_kind may have been cleared)
+{
+    if (cks_kind != ZZ_CKS_NONE)
+        hipLaunchKernelGGL(k_cks_reduce, dim3(1), dim3(ZZ_RED_THREADS), 0, st, pp.cks, pp.npk, pp.packet_size, pp.n, cks_kind, c->d_cks_total);
+}
+
+// What every packet-mode launch is given, as a batch's or a member file's packets take it (final, cold, slots end to end; a packet's own
+// view counts its item's: zz_packet_view); a single stream adds its own. One forced violation is consumed per order-checked launch.
+static zz_packet_params packet_params(zz_ctx* c, uint32_t npk, uint32_t P, int cks_kind, const launch_plan& plan)
+{
+    zz_packet_params pp = {};
+    pp.packet_size = P; pp.npk = npk; pp.cks_kind = cks_kind; pp.last_is_final = 1;
+    pp.slots = c->slots; pp.sizes = c->sizes; pp.cks = c->cks; pp.err = c->d_err; pp.prof = c->d_prof;
+    pp.dbg_viol = plan.order_checked && take_forced_violation() ? 1 : 0;
+    return pp;
+}
+// The one place that launches the packet encoders, for a single stream (M == nullptr) and for the items of a batch map. The timed work
+// begins here: the CRC-32 pass of a gzip container (after it the encode kernels must not overwrite the CRC partials), then level 1's or
+// levels 2..6's kernel by the plan. The level-0 forms differ between the callers and follow this call; end_packet_encoders closes it.
+// (Round 3 ran the CRC pass BESIDE the encode kernel on a second stream, in front of it or behind it, with 256..2048 workgroups:
+// 96.3-96.7 GB/s against 95.9 on 1 GiB of log lines at level 1, and slower at level 2 -- its LDS table lookups and VALU work come out
+// of what the encode kernel's waiting parsers leave each other. Not worth a second stream: profiles/README.md.)
+static int launch_packet_encoders(zz_ctx* c, zz_packet_params& pp, const zz_batch_map* M, int level, int xdepth, launch_plan plan, hipStream_t st)
+{
+    if (c->timing) HIPCHK(hipEventRecord(c->ev0, st));
+    if (pp.cks_kind == ZZ_CKS_CRC) {
+        if (M) hipLaunchKernelGGL(k_crc32_packets_batch, dim3(pp.npk < 2048 ? pp.npk : 2048), dim3(ZZ_CRC_THREADS), 0, st, pp, *M);
+        else launch_cks_partials(pp, 0, st);
+        pp.cks_kind = ZZ_CKS_NONE;
+    }
+    if (level == 0) return ZZ_OK;
+    if (!M) hipLaunchKernelGGL(k_fill_tail, dim3(1), dim3(128), 0, st, pp.src, pp.n, c->d_tail);   // (what reads past the shard's end reads this)
+    if (level >= 2) {
+        launch_level2(pp, c->l2_scratch, c->d_work, st, xdepth, plan.l2p, M);
+    } else if (M) {
+        if (plan.l1p) hipLaunchKernelGGL(k_encode_l1p_batch, dim3(pp.npk), dim3(ZZ_L1P_THREADS), 0, st, pp, *M);
+        else hipLaunchKernelGGL(k_encode_l1_batch, dim3(pp.npk), dim3(ZZ_L1_THREADS), 0, st, pp, *M);
+    } else {
+        // ZZFLATE_L1_PAD_LDS (diagnostic): extra dynamic LDS per workgroup, to measure throughput vs. resident waves
+        static const unsigned pad_lds = [] { const char* e = getenv("ZZFLATE_L1_PAD_LDS"); return e ? (unsigned)atoi(e) : 0u; }();
+        // (a warm window exists only where the LDS-order verdict is positive: zz_ctx_set_warm_window; k_encode_l1w = the one-parser form, A/B)
+        if (pp.warm && !l1_classic()) hipLaunchKernelGGL(k_encode_l1pw, dim3(pp.npk), dim3(ZZ_L1P_THREADS), pad_lds, st, pp);
+        else if (pp.warm) hipLaunchKernelGGL(k_encode_l1w, dim3(pp.npk), dim3(ZZ_L1_THREADS), pad_lds, st, pp);
+        else if (!plan.l1p) hipLaunchKernelGGL(k_encode_l1, dim3(pp.npk), dim3(ZZ_L1_THREADS), pad_lds, st, pp);
+        else hipLaunchKernelGGL(k_encode_l1p, dim3(pp.npk), dim3(ZZ_L1P_THREADS), pad_lds, st, pp);
+    }
+    return ZZ_OK;
+}
+// the end of the timed work, and where every packet starts in the joined stream (level 0: every packet has its known place)
+static int end_packet_encoders(zz_ctx* c, int level, uint32_t npk, hipStream_t st)
+{
+    if (c->timing) { HIPCHK(hipEventRecord(c->ev1, st)); c->have_time = true; }
+    if (level != 0) hipLaunchKernelGGL(k_scan_sizes, dim3(1), dim3(ZZ_SCAN_THREADS), 0, st, c->sizes, npk, c->offsets, c->d_res);
+    return ZZ_OK;
+}
+// batches and members: the sticky error word behind the call's last kernel, the wait, the word's verdict (read_err_word).
+// (encode_finish waits on its own: zz_encode_device_async only enqueues.)
+static int finish_err_word(zz_ctx* c, bool order_checked, hipStream_t st)
+{
+    HIPCHK(hipMemcpyAsync(c->h_err, c->d_err, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return read_err_word(c, order_checked);
+}
+
 // The common pipeline. with_container: write header/trailer (whole stream) or not (shard).
 static int encode_finish(zz_ctx* c, zz_result* host_res);
 // `host_res` == nullptr: enqueue only (zz_encode_device_async); the caller collects with encode_finish.
@@ -690,9 +785,7 @@ static int encode_common(zz_ctx* c, const uint8_t* d_src, uint64_t n, uint64_t h
     const uint32_t npk = (uint32_t)npk64;
     const uint32_t stride = slot_stride_for(level, P);
     const launch_plan plan = plan_launch(c, level, warm, xdepth, one_parser);
-    c->have_time = false;
-    c->have_last = false;            // whatever zz_verify_last_device could look at is about to change
-    c->idx_empty = false;
+    begin_encode_call(c);
 
     HIPCHK(hipMemsetAsync(c->d_res, 0, sizeof(zz_result), st));
     HIPCHK(hipMemsetAsync(c->d_cks_total, 0, sizeof(zz_cks_total), st));
@@ -710,24 +803,10 @@ static int encode_common(zz_ctx* c, const uint8_t* d_src, uint64_t n, uint64_t h
         for (uint32_t i = 0; i < bl; ++i) packed |= (uint64_t)blk[i] << (8 * i);
         hipLaunchKernelGGL(k_put_small, dim3(1), dim3(1), 0, st, d_dst + hl, packed, bl, c->d_res, (uint64_t)bl);
     } else {
-        int rc = ensure_workspace(c, level, npk, stride, xdepth, P);
-        if (rc) return rc;
-        zz_packet_params pp;
-        pp.src = d_src; pp.n = n; pp.halo = halo; pp.packet_size = P; pp.npk = npk;
-        pp.last_is_final = last_is_final ? 1 : 0; pp.cks_kind = cks_kind; pp.warm = warm;
-        pp.slots = c->slots; pp.slot_stride = stride; pp.sizes = c->sizes; pp.cks = c->cks; pp.err = c->d_err; pp.prof = c->d_prof; pp.tail = c->d_tail;
-        pp.dbg_viol = plan.order_checked && take_forced_violation() ? 1 : 0;
-
-        if (c->timing) HIPCHK(hipEventRecord(c->ev0, st));   // the CRC-32 pass of the gzip container is part of the timed work
-        if (cks_kind == ZZ_CKS_CRC) {
-            // (Round 3 ran this pass BESIDE the encode kernel on a second stream, in front of it or behind it, with 256..2048
-            // workgroups: 96.3-96.7 GB/s against 95.9 on 1 GiB of log lines at level 1, and slower at level 2 -- its LDS table
-            // lookups and VALU work come out of what the encode kernel's waiting parsers leave each other. Not worth a
-            // second stream: profiles/README.md.)
-            uint32_t g = npk < 2048 ? npk : 2048;   // persistent: table + shift constants are built once per block
-            hipLaunchKernelGGL(k_crc32_packets, dim3(g), dim3(ZZ_CRC_THREADS), 0, st, pp);
-            pp.cks_kind = ZZ_CKS_NONE;   // the encode kernel must not overwrite the CRC partials
-        }
+        if (int rc = ensure_workspace(c, level, npk, stride, xdepth, P)) return rc;
+        zz_packet_params pp = packet_params(c, npk, P, cks_kind, plan);
+        pp.src = d_src; pp.n = n; pp.halo = halo; pp.last_is_final = last_is_final ? 1 : 0; pp.warm = warm; pp.slot_stride = stride; pp.tail = c->d_tail;
+        if (int rc = launch_packet_encoders(c, pp, nullptr, level, xdepth, plan, st)) return rc;
         if (level == 0) {
             const uint64_t total = (uint64_t)(npk - 1) * l0_packet_bytes(P, false) +
                                    l0_packet_bytes((uint32_t)(n - (uint64_t)(npk - 1) * P), last_is_final);
@@ -736,28 +815,14 @@ static int encode_common(zz_ctx* c, const uint8_t* d_src, uint64_t n, uint64_t h
             uint32_t g = npk < 16384 ? npk : 16384;
             hipLaunchKernelGGL(k_encode_l0, dim3(g), dim3(256), 0, st, q);
             hipLaunchKernelGGL(k_put_small, dim3(1), dim3(1), 0, st, (uint8_t*)nullptr, 0ull, 0u, c->d_res, total);
-        } else if (level == 1) {
-            hipLaunchKernelGGL(k_fill_tail, dim3(1), dim3(128), 0, st, pp.src, pp.n, c->d_tail);      // (what reads past the shard's end reads this)
-            // ZZFLATE_L1_PAD_LDS (diagnostic): extra dynamic LDS per workgroup, to measure throughput vs. resident waves
-            static const unsigned pad_lds = [] { const char* e = getenv("ZZFLATE_L1_PAD_LDS"); return e ? (unsigned)atoi(e) : 0u; }();
-            // (a warm window exists only where the LDS-order verdict is positive: zz_ctx_set_warm_window; k_encode_l1w = the one-parser form, A/B)
-            if (pp.warm && !l1_classic()) hipLaunchKernelGGL(k_encode_l1pw, dim3(npk), dim3(ZZ_L1P_THREADS), pad_lds, st, pp);
-            else if (pp.warm) hipLaunchKernelGGL(k_encode_l1w, dim3(npk), dim3(ZZ_L1_THREADS), pad_lds, st, pp);
-            else if (!plan.l1p) hipLaunchKernelGGL(k_encode_l1, dim3(npk), dim3(ZZ_L1_THREADS), pad_lds, st, pp);
-            else hipLaunchKernelGGL(k_encode_l1p, dim3(npk), dim3(ZZ_L1P_THREADS), pad_lds, st, pp);
-        } else {
-            hipLaunchKernelGGL(k_fill_tail, dim3(1), dim3(128), 0, st, pp.src, pp.n, c->d_tail);
-            launch_level2(pp, c->l2_scratch, c->d_work, st, xdepth, plan.l2p);
         }
-        if (c->timing) { HIPCHK(hipEventRecord(c->ev1, st)); c->have_time = true; }
+        if (int rc = end_packet_encoders(c, level, npk, st)) return rc;
         if (level != 0) {
-            hipLaunchKernelGGL(k_scan_sizes, dim3(1), dim3(ZZ_SCAN_THREADS), 0, st, c->sizes, npk, c->offsets, c->d_res);
             uint32_t g = npk < 65536 ? npk : 65536;
             hipLaunchKernelGGL(k_compact, dim3(g), dim3(256), 0, st, c->slots, stride, c->sizes, c->offsets, npk,
                                d_dst + hl, cap >= (uint64_t)(hl + tl) ? cap - hl - tl : 0, c->d_res);
         }
-        if (cks_kind != ZZ_CKS_NONE)
-            hipLaunchKernelGGL(k_cks_reduce, dim3(1), dim3(ZZ_RED_THREADS), 0, st, c->cks, npk, P, n, cks_kind, c->d_cks_total);
+        launch_cks_fold(c, pp, cks_kind, st);
     }
     hipLaunchKernelGGL(k_finalize, dim3(1), dim3(1), 0, st, d_dst, cap, with_container ? format : (int)ZZ_FMT_DEFLATE,
                        c->d_cks_total, n, c->d_res);
@@ -1069,9 +1134,8 @@ static int dec_check_trailer(zz_ctx* c, const uint8_t* trailer, int format, cons
         if (int rc = D.cks.grow(npk)) return rc;
         zz_packet_params pp = {};
         pp.src = dst; pp.n = n; pp.packet_size = CP; pp.npk = (uint32_t)npk; pp.cks_kind = kind; pp.cks = D.cks;
-        if (kind == ZZ_CKS_ADLER) hipLaunchKernelGGL(k_adler_packets, dim3(npk < 16384 ? (uint32_t)npk : 16384), dim3(ZZ_WAVE), 0, st, pp);
-        else hipLaunchKernelGGL(k_crc32_packets, dim3(npk < 2048 ? (uint32_t)npk : 2048), dim3(ZZ_CRC_THREADS), 0, st, pp);
-        hipLaunchKernelGGL(k_cks_reduce, dim3(1), dim3(ZZ_RED_THREADS), 0, st, D.cks, (uint32_t)npk, CP, n, kind, c->d_cks_total);
+        launch_cks_partials(pp, 16384, st);
+        launch_cks_fold(c, pp, kind, st);
     }
     hipLaunchKernelGGL(k_inflate_trailer, dim3(1), dim3(1), 0, st, trailer, format, c->d_cks_total, n, D.ok);
     HIPCHK(hipGetLastError());
@@ -1457,8 +1521,7 @@ static int encode_stream(zz_ctx* c, const uint8_t* d_src, uint64_t n, uint8_t* d
     const int hl = header_len(format), tl = trailer_len(format);
     if (cap < (uint64_t)hl) { set_err("destination smaller than the container header"); return ZZ_E_NOSPACE; }
     const int cks_kind = cks_kind_for(format);
-    c->have_time = false;
-    c->have_last = false;
+    begin_encode_call(c);
     HIPCHK(hipMemsetAsync(c->d_res, 0, sizeof(zz_result), st));
     HIPCHK(hipMemsetAsync(c->d_cks_total, 0, sizeof(zz_cks_total), st));
     HIPCHK(hipMemsetAsync(c->d_err, 0, 4 * sizeof(uint32_t), st));
@@ -1475,15 +1538,13 @@ static int encode_stream(zz_ctx* c, const uint8_t* d_src, uint64_t n, uint8_t* d
         const uint64_t total = (uint64_t)(npk - 1) * (B + 5) + 5 + (n - (uint64_t)(npk - 1) * B);
         if ((uint64_t)hl + total + tl > cap) { set_err("destination too small"); return ZZ_E_NOSPACE; }
         pp.packet_size = B; pp.npk = npk; pp.cks_kind = cks_kind; pp.sizes = c->sizes; pp.cks = c->cks;
-        if (cks_kind == ZZ_CKS_CRC) {
-            hipLaunchKernelGGL(k_crc32_packets, dim3(npk < 2048 ? npk : 2048), dim3(ZZ_CRC_THREADS), 0, st, pp);
+        if (cks_kind == ZZ_CKS_CRC) {                                  // (Adler partials are k_encode_l0's own)
+            launch_cks_partials(pp, 0, st);
             pp.cks_kind = ZZ_CKS_NONE;
         }
         zz_l0_params q; q.pk = pp; q.dst = d_dst + hl; q.stream_mode = 1;
         hipLaunchKernelGGL(k_encode_l0, dim3(npk < 16384 ? npk : 16384), dim3(256), 0, st, q);
         hipLaunchKernelGGL(k_put_small, dim3(1), dim3(1), 0, st, (uint8_t*)nullptr, 0ull, 0u, c->d_res, total);
-        if (cks_kind != ZZ_CKS_NONE)
-            hipLaunchKernelGGL(k_cks_reduce, dim3(1), dim3(ZZ_RED_THREADS), 0, st, c->cks, npk, B, n, cks_kind, c->d_cks_total);
         if (chunked && chunk_sizes)                                     // WriteUncompressedBlock asks for 6 + length (encoder.cpp:488)
             for (uint32_t k = 0; k < npk; ++k) {
                 log.push_back((uint64_t)k * (B + 5));
@@ -1509,8 +1570,7 @@ static int encode_stream(zz_ctx* c, const uint8_t* d_src, uint64_t n, uint8_t* d
             ctl.log = c->d_log; ctl.log_cap = log_cap;
         }
         pp.packet_size = P; pp.npk = npk_c; pp.cks_kind = cks_kind; pp.cks = c->cks; pp.sizes = c->sizes;
-        if (cks_kind == ZZ_CKS_CRC) hipLaunchKernelGGL(k_crc32_packets, dim3(npk_c < 2048 ? npk_c : 2048), dim3(ZZ_CRC_THREADS), 0, st, pp);
-        else if (cks_kind == ZZ_CKS_ADLER) hipLaunchKernelGGL(k_adler_packets, dim3(npk_c < 4096 ? npk_c : 4096), dim3(ZZ_WAVE), 0, st, pp);
+        launch_cks_partials(pp, 4096, st);
         zz_packet_params ps = pp;
         ps.npk = 1; ps.slots = c->slots; ps.slot_stride = (uint32_t)(bound > 0xFFFFFFF0ull ? 0xFFFFFFF0ull : bound); ps.cks_kind = ZZ_CKS_NONE;
         if (level >= 2 && (rc = c->l2_scratch.grow(ZZ_ST_SCRATCH_BYTES))) return rc;
@@ -1520,9 +1580,8 @@ static int encode_stream(zz_ctx* c, const uint8_t* d_src, uint64_t n, uint8_t* d
         if (c->timing) { HIPCHK(hipEventRecord(c->ev1, st)); c->have_time = true; }
         hipLaunchKernelGGL(k_copy_stream, dim3(1024), dim3(256), 0, st, c->slots, c->sizes, d_dst + hl,
                            cap >= (uint64_t)(hl + tl) ? cap - hl - tl : 0, c->d_res);
-        if (cks_kind != ZZ_CKS_NONE)
-            hipLaunchKernelGGL(k_cks_reduce, dim3(1), dim3(ZZ_RED_THREADS), 0, st, c->cks, npk_c, P, n, cks_kind, c->d_cks_total);
     }
+    launch_cks_fold(c, pp, cks_kind, st);
     hipLaunchKernelGGL(k_finalize, dim3(1), dim3(1), 0, st, d_dst, cap, format, c->d_cks_total, n, c->d_res);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(c->h_res, c->d_res, sizeof(zz_result), hipMemcpyDeviceToHost, st));
@@ -1604,8 +1663,7 @@ static int encode_ranges(zz_ctx* c, const uint8_t* d_src, uint64_t n, uint8_t* d
         set_err("ranges: count too large for this input: (count - 1) * ceil(n / count) must be < n (zzflate.cpp:67-78 would cut ranges past the input's end)");
         return ZZ_E_ARG;
     }
-    c->have_time = false;
-    c->have_last = false;
+    begin_encode_call(c);
     HIPCHK(hipMemsetAsync(c->d_res, 0, sizeof(zz_result), st));
     HIPCHK(hipMemsetAsync(c->d_cks_total, 0, sizeof(zz_cks_total), st));
     HIPCHK(hipMemsetAsync(c->d_err, 0, 4 * sizeof(uint32_t), st));
@@ -1616,8 +1674,7 @@ static int encode_ranges(zz_ctx* c, const uint8_t* d_src, uint64_t n, uint8_t* d
     memset(&pp, 0, sizeof pp);
     pp.src = d_src; pp.n = n; pp.halo = 0; pp.last_is_final = 1; pp.err = c->d_err; pp.prof = c->d_prof; pp.tail = c->d_tail;
     pp.packet_size = P; pp.npk = npk_c; pp.cks_kind = cks_kind; pp.cks = c->cks; pp.sizes = c->sizes;
-    if (cks_kind == ZZ_CKS_CRC) hipLaunchKernelGGL(k_crc32_packets, dim3(npk_c < 2048 ? npk_c : 2048), dim3(ZZ_CRC_THREADS), 0, st, pp);
-    else if (cks_kind == ZZ_CKS_ADLER) hipLaunchKernelGGL(k_adler_packets, dim3(npk_c < 4096 ? npk_c : 4096), dim3(ZZ_WAVE), 0, st, pp);
+    launch_cks_partials(pp, 4096, st);
     if (level == 0) {
         const uint64_t total = (uint64_t)(count - 1) * l0_range_bytes(step, false) + l0_range_bytes(n - (uint64_t)(count - 1) * step, true);
         if ((uint64_t)hl + total + tl > cap) { set_err("destination too small"); return ZZ_E_NOSPACE; }
@@ -1641,8 +1698,7 @@ static int encode_ranges(zz_ctx* c, const uint8_t* d_src, uint64_t n, uint8_t* d
         hipLaunchKernelGGL(k_compact, dim3(count), dim3(256), 0, st, c->slots, (uint32_t)bound, c->sizes, c->offsets, count,
                            d_dst + hl, cap >= (uint64_t)(hl + tl) ? cap - hl - tl : 0, c->d_res);
     }
-    if (cks_kind != ZZ_CKS_NONE)
-        hipLaunchKernelGGL(k_cks_reduce, dim3(1), dim3(ZZ_RED_THREADS), 0, st, c->cks, npk_c, P, n, cks_kind, c->d_cks_total);
+    launch_cks_fold(c, pp, cks_kind, st);
     hipLaunchKernelGGL(k_finalize, dim3(1), dim3(1), 0, st, d_dst, cap, format, c->d_cks_total, n, c->d_res);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(c->h_res, c->d_res, sizeof(zz_result), hipMemcpyDeviceToHost, st));
@@ -1782,17 +1838,8 @@ static int encode_batch(zz_ctx* c, uint32_t nitems, const uint8_t* const* d_srcs
                         const uint64_t* d_caps, uint64_t* d_out_lens, int format, int level, uint32_t P, hipStream_t st, bool one_parser)
 {
     const int cks_kind = cks_kind_for(format);
-    c->have_time = false;
-    c->have_last = false;            // verify / extent / index describe single calls only
-    c->idx_empty = false;
-    // per-item workspace: first packet (+1 entry), slot base, tail
-    const uint64_t m = (uint64_t)nitems + 1;
-    if (m * 128 > c->bat.tails.cap) {    // (the last of the three, as in ensure_workspace)
-        c->bat.first.release(); c->bat.slotbase.release(); c->bat.tails.release();
-        if (int rc = c->bat.first.grow(m)) return rc;
-        if (int rc = c->bat.slotbase.grow(m)) return rc;
-        if (int rc = c->bat.tails.grow(m * 128)) return rc;
-    }
+    begin_encode_call(c);
+    if (int rc = ensure_items(c, (uint64_t)nitems + 1)) return rc;
     if (int rc = c->bat.d_tot.grow(1)) return rc;
     if (int rc = c->bat.h_tot.grow(1)) return rc;
     HIPCHK(hipMemsetAsync(c->d_err, 0, sizeof(uint32_t), st));
@@ -1806,40 +1853,20 @@ static int encode_batch(zz_ctx* c, uint32_t nitems, const uint8_t* const* d_srcs
     const uint32_t npk = (uint32_t)npk64;
     // the same kernel choice as a single call, and the same run-time check behind the LDS-order verdict
     const launch_plan plan = plan_launch(c, level, 0, 0, one_parser);
-    if (npk) {
-        int rc = ensure_workspace(c, 0, npk, 0);                                  // sizes, offsets, checksum partials
-        if (rc) return rc;
-        if ((rc = c->slots.grow(slot_bytes))) return rc;
-        if (level >= 2 && (rc = c->l2_scratch.grow(l2_scratch_bytes(npk, 0, P)))) return rc;
-        if ((rc = c->bat.desc.grow(npk))) return rc;
-    }
+    if (npk) if (int rc = ensure_batch_workspace(c, level, npk, slot_bytes, P)) return rc;
     zz_batch_map M;
     M.desc = c->bat.desc; M.srcs = d_srcs; M.ns = d_ns; M.first = c->bat.first; M.tails = c->bat.tails; M.npk = npk; M.level = level;
     if (npk) {
         hipLaunchKernelGGL(k_batch_desc, dim3((npk + 255) / 256), dim3(256), 0, st, c->bat.first, nitems, npk, P, level, c->bat.slotbase, c->bat.desc);
         if (level >= 1)
             hipLaunchKernelGGL(k_batch_tails, dim3(nitems < 65536 ? nitems : 65536), dim3(128), 0, st, d_srcs, d_ns, nitems, c->bat.tails);
-        zz_packet_params pp = {};
-        pp.packet_size = P; pp.cks_kind = cks_kind; pp.slots = c->slots; pp.sizes = c->sizes; pp.cks = c->cks; pp.err = c->d_err;
-        pp.prof = c->d_prof; pp.warm = 0; pp.last_is_final = 1;
-        pp.npk = npk;                        // (the launch's packets; a packet's own view counts its item's: zz_packet_view)
-        pp.dbg_viol = plan.order_checked && take_forced_violation() ? 1 : 0;
-        if (c->timing) HIPCHK(hipEventRecord(c->ev0, st));
-        if (cks_kind == ZZ_CKS_CRC) {
-            hipLaunchKernelGGL(k_crc32_packets_batch, dim3(npk < 2048 ? npk : 2048), dim3(ZZ_CRC_THREADS), 0, st, pp, M);
-            pp.cks_kind = ZZ_CKS_NONE;
-        }
+        zz_packet_params pp = packet_params(c, npk, P, cks_kind, plan);
+        if (int rc = launch_packet_encoders(c, pp, &M, level, 0, plan, st)) return rc;
         if (level == 0) {
             zz_l0_batch_params q; q.pk = pp; q.dsts = d_dsts; q.caps = d_caps; q.format = format;
             hipLaunchKernelGGL(k_encode_l0_batch, dim3(npk < 16384 ? npk : 16384), dim3(256), 0, st, q, M);
-        } else if (level == 1) {
-            if (plan.l1p) hipLaunchKernelGGL(k_encode_l1p_batch, dim3(npk), dim3(ZZ_L1P_THREADS), 0, st, pp, M);
-            else hipLaunchKernelGGL(k_encode_l1_batch, dim3(npk), dim3(ZZ_L1_THREADS), 0, st, pp, M);
-        } else {
-            launch_level2(pp, c->l2_scratch, c->d_work, st, 0, plan.l2p, &M);
         }
-        if (c->timing) { HIPCHK(hipEventRecord(c->ev1, st)); c->have_time = true; }
-        if (level != 0) hipLaunchKernelGGL(k_scan_sizes, dim3(1), dim3(ZZ_SCAN_THREADS), 0, st, c->sizes, npk, c->offsets, c->d_res);
+        if (int rc = end_packet_encoders(c, level, npk, st)) return rc;
     }
     zz_batch_join J;
     J.map = M; J.sizes = c->sizes; J.offsets = c->offsets; J.cks = c->cks; J.slots = c->slots; J.dsts = d_dsts; J.caps = d_caps;
@@ -1853,9 +1880,7 @@ static int encode_batch(zz_ctx* c, uint32_t nitems, const uint8_t* const* d_srcs
     }
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(c->bat.h_tot, c->bat.d_tot, sizeof(zz_batch_totals), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(c->h_err, c->d_err, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    const int ew = read_err_word(c, plan.order_checked);
+    const int ew = finish_err_word(c, plan.order_checked, st);
     if (ew == ERR_RERUN)                 // as encode_finish: the whole batch runs again on the one-parser kernels
         return encode_batch(c, nitems, d_srcs, d_ns, d_dsts, d_caps, d_out_lens, format, level, P, st, true);
     if (ew) return ew;
@@ -1918,9 +1943,7 @@ static int encode_members(zz_ctx* c, const uint8_t* d_src, uint64_t n, uint8_t* 
                           uint32_t B, uint32_t P, int flags, uint64_t* d_member_offsets, hipStream_t st, bool one_parser)
 {
     auto& W = c->mw;
-    c->have_time = false;
-    c->have_last = false;            // verify / extent / index describe single calls only
-    c->idx_empty = false;
+    begin_encode_call(c);
     // members, packets and slot bytes in closed form: the host reads nothing back before the launches
     const uint32_t m = (uint32_t)((n + B - 1) / B), ppm = (B + P - 1) / P;
     const uint32_t last = m ? (uint32_t)(n - (uint64_t)(m - 1) * B) : 0;
@@ -1932,25 +1955,14 @@ static int encode_members(zz_ctx* c, const uint8_t* d_src, uint64_t n, uint8_t* 
     const uint64_t full_slots = block_slots(B);
     const uint64_t slot_bytes = m ? (uint64_t)(m - 1) * full_slots + block_slots(last) + 256 : 0;     // (+ room behind the last slot)
     const uint64_t mm = (uint64_t)m + 1;
-    if (mm * 128 > c->bat.tails.cap) {   // (the last of the three, as in encode_batch)
-        c->bat.first.release(); c->bat.slotbase.release(); c->bat.tails.release();
-        if (int rc = c->bat.first.grow(mm)) return rc;
-        if (int rc = c->bat.slotbase.grow(mm)) return rc;
-        if (int rc = c->bat.tails.grow(mm * 128)) return rc;
-    }
+    if (int rc = ensure_items(c, mm)) return rc;
     if (int rc = W.srcs.grow(mm)) return rc;
     if (int rc = W.ns.grow(mm)) return rc;
     if (int rc = W.moff.grow(mm)) return rc;
     if (int rc = W.stored.grow(mm)) return rc;
     if (int rc = W.d_st.grow(1)) return rc;
     if (int rc = W.h_st.grow(1)) return rc;
-    if (npk) {
-        int rc = ensure_workspace(c, 0, npk, 0);                                  // sizes, offsets, checksum partials
-        if (rc) return rc;
-        if (level != 0 && (rc = c->slots.grow(slot_bytes))) return rc;
-        if (level >= 2 && (rc = c->l2_scratch.grow(l2_scratch_bytes(npk, 0, P)))) return rc;
-        if ((rc = c->bat.desc.grow(npk))) return rc;
-    }
+    if (npk) if (int rc = ensure_batch_workspace(c, level, npk, level ? slot_bytes : 0, P)) return rc;      // (level 0 has no slots)
     HIPCHK(hipMemsetAsync(c->d_err, 0, sizeof(uint32_t), st));
     const launch_plan plan = plan_launch(c, level, 0, 0, one_parser);
     zz_mw_params Q;
@@ -1967,22 +1979,9 @@ static int encode_members(zz_ctx* c, const uint8_t* d_src, uint64_t n, uint8_t* 
         if (level >= 1)
             hipLaunchKernelGGL(k_batch_tails, dim3(m < 65536 ? m : 65536), dim3(128), 0, st, (const uint8_t* const*)W.srcs.p, (const uint64_t*)W.ns, m,
                                (uint8_t*)c->bat.tails);
-        zz_packet_params pp = {};
-        pp.packet_size = P; pp.cks_kind = ZZ_CKS_CRC; pp.slots = c->slots; pp.sizes = c->sizes; pp.cks = c->cks; pp.err = c->d_err;
-        pp.prof = c->d_prof; pp.warm = 0; pp.last_is_final = 1;
-        pp.npk = npk;
-        pp.dbg_viol = plan.order_checked && take_forced_violation() ? 1 : 0;
-        if (c->timing) HIPCHK(hipEventRecord(c->ev0, st));
-        hipLaunchKernelGGL(k_crc32_packets_batch, dim3(npk < 2048 ? npk : 2048), dim3(ZZ_CRC_THREADS), 0, st, pp, M);
-        pp.cks_kind = ZZ_CKS_NONE;           // the encode kernels must not overwrite the CRC partials
-        if (level == 1) {
-            if (plan.l1p) hipLaunchKernelGGL(k_encode_l1p_batch, dim3(npk), dim3(ZZ_L1P_THREADS), 0, st, pp, M);
-            else hipLaunchKernelGGL(k_encode_l1_batch, dim3(npk), dim3(ZZ_L1_THREADS), 0, st, pp, M);
-        } else if (level >= 2) {
-            launch_level2(pp, c->l2_scratch, c->d_work, st, 0, plan.l2p, &M);
-        }
-        if (c->timing) { HIPCHK(hipEventRecord(c->ev1, st)); c->have_time = true; }
-        if (level != 0) hipLaunchKernelGGL(k_scan_sizes, dim3(1), dim3(ZZ_SCAN_THREADS), 0, st, c->sizes, npk, c->offsets, c->d_res);
+        zz_packet_params pp = packet_params(c, npk, P, ZZ_CKS_CRC, plan);
+        if (int rc = launch_packet_encoders(c, pp, &M, level, 0, plan, st)) return rc;      // (level 0: the CRC pass alone; k_mw_stored writes the blocks)
+        if (int rc = end_packet_encoders(c, level, npk, st)) return rc;
     }
     // the members' sizes and places, and the room check: nothing below stores a byte unless the file fits
     hipLaunchKernelGGL(k_mw_sizes, dim3(1), dim3(ZZ_SCAN_THREADS), 0, st, Q);
@@ -1995,9 +1994,7 @@ static int encode_members(zz_ctx* c, const uint8_t* d_src, uint64_t n, uint8_t* 
     if (npk) hipLaunchKernelGGL(k_mw_stored, dim3(npk < 16384 ? npk : 16384), dim3(256), 0, st, Q, npk);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(W.h_st, W.d_st, sizeof(zz_mw_state), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(c->h_err, c->d_err, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    const int ew = read_err_word(c, plan.order_checked);
+    const int ew = finish_err_word(c, plan.order_checked, st);
     if (ew == ERR_RERUN)                 // as encode_batch: the whole call runs again on the one-parser kernels
         return encode_members(c, d_src, n, d_dst, cap, out_len, level, B, P, flags, d_member_offsets, st, true);
     if (ew) return ew;

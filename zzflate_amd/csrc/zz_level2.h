@@ -1680,8 +1680,8 @@ template <bool PP> __global__ __launch_bounds__(PP ? ZZ_L2P_THREADS : ZZ_L2_THRE
 // two_parser: levels 2,3 with cold packets on k_encode_l2p (the caller decides: not behind ZZFLATE_L2_KERNEL=classic, and -- its insert
 // is an ordered LDS exchange -- only where the device's LDS-order verdict is positive)
 // M: a batch -- the batch forms of the two cold kernels over its pp.npk packets (no window, no extended levels)
-static inline void launch_level2(const zz_packet_params& pp, uint8_t* scratch, uint32_t* work, hipStream_t st, int xdepth = 0, bool two_parser = true,
-                                 const zz_batch_map* M = nullptr)
+static inline void launch_level2(const zz_packet_params& pp, uint8_t* scratch, uint32_t* work, hipStream_t st, int xdepth, bool two_parser,
+                                 const zz_batch_map* M)
 {
     zz_l2_params q; q.pk = pp; q.scratch = scratch; q.work = work; q.m = nullptr; q.k0 = 0; q.k1 = pp.npk;
     const dim3 g1(l2_grid(pp.npk)), b1(ZZ_L2_THREADS), g2(l2_grid(pp.npk, false, ZZ_L2P_WPE >= 7 ? 9 : 8)), b2(ZZ_L2P_THREADS);   // one parser, two
