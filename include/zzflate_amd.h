@@ -113,7 +113,13 @@ int zz_set_packet_size(uint32_t packet_size);
 uint32_t zz_get_packet_size(void);
 
 /* ---- device-resident entry points ---------------------------------------------------------------- */
-/* Whole stream: d_src[0,n) -> d_dst (container header, packets, trailer). *out_len = bytes or ~0. */
+/* Whole stream: d_src[0,n) -> d_dst (container header, packets, trailer). *out_len = bytes or ~0.
+ * Every single-stream encode entry point below (this one, its two halves, the shard calls, zz_encode_multi_device, the
+ * sequential stream and its chunked form, zz_encode_ranges_device) and zz_encode: nothing is written outside d_dst[0, cap),
+ * whatever the result. A stream of exactly `cap` bytes fits; one byte less gives ZZ_E_NOSPACE, also where only the trailer
+ * does not fit. What lies in d_dst[0, cap) after ZZ_E_NOSPACE is unspecified. A call that is refused, for whatever reason, is
+ * still the context's last call: zz_verify_last_device, zz_packet_extent_device and zz_packet_index_device answer ZZ_E_ARG
+ * after it, they never describe the call in front of it. */
 int zz_encode_device(zz_ctx* ctx, const void* d_src, uint64_t n, void* d_dst, uint64_t cap, uint64_t* out_len,
                      int format, int level, uint32_t packet_size, void* hip_stream);
 

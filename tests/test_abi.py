@@ -50,6 +50,16 @@ def test_bound_covers_worst_case():
     for n in (0, 1, 32767, 32768, 32769, 1 << 20):
         for lvl in range(4):
             assert zz.bound(n, zz.Format.Gzip, lvl) >= n + 18
+    # the per-packet term against the worst packets in closed form (tests/expansion_cases.py; the oracle's own packets are held to it
+    # in tests/test_expansion_cases_cpu.py): nine bits a byte at level 1, the stored fallback above, level 0's len + 10
+    import expansion_cases as ec
+    for L in ec.LENGTHS:
+        assert ec.per_packet(0, L) >= (L + 10 if L > 1 else 6)
+        assert ec.per_packet(1, L) >= max(ec.level1_packet_bytes(L, True), ec.level1_packet_bytes(L, False))
+        for lvl in range(2, 7):
+            assert ec.per_packet(lvl, L) >= ec.stored_packet_bytes(L, False)
+        for fmt in zz.Format:
+            assert zz.bound(3 * L + 1, fmt, 1, L) >= ec.HEADER[fmt] + 3 * ec.level1_packet_bytes(L, False) + 3 + ec.TRAILER[fmt]
 
 
 def test_generators_are_deterministic_and_blockwise():

@@ -763,6 +763,7 @@ static int encode_common(zz_ctx* c, const uint8_t* d_src, uint64_t n, uint64_t h
 {
     const int level_asked = level;
     if (call_pending(c)) return ZZ_E_ARG;
+    begin_encode_call(c);              // a call that is refused below is still the context's last call: there is then none to look at
     // Levels 4..6 are beyond the reference (which rejects them, zzflate.cpp:201,230) and only exist when switched on:
     // hash chains of depth 2 / 4 / 8 over a window of 8 / 32 / 32 KiB in front of every packet, lazy matching, package-merge
     // code lengths (zz_level6.h), in the level-2 kernel's frame (dynamic blocks, stored fallback).
@@ -785,7 +786,6 @@ static int encode_common(zz_ctx* c, const uint8_t* d_src, uint64_t n, uint64_t h
     const uint32_t npk = (uint32_t)npk64;
     const uint32_t stride = slot_stride_for(level, P);
     const launch_plan plan = plan_launch(c, level, warm, xdepth, one_parser);
-    begin_encode_call(c);
 
     HIPCHK(hipMemsetAsync(c->d_res, 0, sizeof(zz_result), st));
     HIPCHK(hipMemsetAsync(c->d_cks_total, 0, sizeof(zz_cks_total), st));
@@ -1508,6 +1508,7 @@ static int encode_stream(zz_ctx* c, const uint8_t* d_src, uint64_t n, uint8_t* d
                          bool chunked, std::vector<uint64_t>* chunk_sizes, hipStream_t st, zz_result* host_res)
 {
     if (call_pending(c)) return ZZ_E_ARG;
+    begin_encode_call(c);
     if (level < 0 || level > 3) { set_err("level must be 0..3 (zzflate.cpp:201,230)"); return ZZ_E_LEVEL; }
     if (!d_dst || (!d_src && n)) { set_err("null buffer"); return ZZ_E_ARG; }
     if (chunk_sizes) chunk_sizes->clear();
@@ -1521,14 +1522,13 @@ static int encode_stream(zz_ctx* c, const uint8_t* d_src, uint64_t n, uint8_t* d
     const int hl = header_len(format), tl = trailer_len(format);
     if (cap < (uint64_t)hl) { set_err("destination smaller than the container header"); return ZZ_E_NOSPACE; }
     const int cks_kind = cks_kind_for(format);
-    begin_encode_call(c);
     HIPCHK(hipMemsetAsync(c->d_res, 0, sizeof(zz_result), st));
     HIPCHK(hipMemsetAsync(c->d_cks_total, 0, sizeof(zz_cks_total), st));
     HIPCHK(hipMemsetAsync(c->d_err, 0, 4 * sizeof(uint32_t), st));
     zz_packet_params pp;
     memset(&pp, 0, sizeof pp);
     pp.src = d_src; pp.n = n; pp.halo = 0; pp.last_is_final = 1; pp.err = c->d_err; pp.prof = c->d_prof; pp.tail = c->d_tail;
-    std::vector<uint64_t> log;           // (bytes stored, length asked for) per EnsureOutputLength call, chunked form
+    std::vector<uint64_t> log;          // (bytes stored, length asked for) per EnsureOutputLength call, chunked form
     uint32_t log_cap = 0;
     if (level == 0) {
         const uint32_t B = 0xFFFF;                                     // encoder.cpp:484
@@ -1643,11 +1643,12 @@ static bool ranges_split_ok(uint64_t n, uint32_t count)
 static int encode_ranges(zz_ctx* c, const uint8_t* d_src, uint64_t n, uint8_t* d_dst, uint64_t cap, int format, int level,
                          uint32_t count, hipStream_t st, zz_result* host_res)
 {
+    if (call_pending(c)) return ZZ_E_ARG;
+    begin_encode_call(c);
     if (count == 0 || count > 4096) { set_err("ranges: count must be 1..4096"); return ZZ_E_ARG; }
     if (level == 1) { set_err("ranges: the reference's threaded level-1 stream is invalid (block lengths follow from destLen / count); use packet mode"); return ZZ_E_LEVEL; }
     if (n < 100ull * count)                                               // zzflate.cpp:84: the single encoder
         return encode_stream(c, d_src, n, d_dst, cap, format, level, false, nullptr, st, host_res);
-    if (call_pending(c)) return ZZ_E_ARG;
     if (level < 0 || level > 3) { set_err("level must be 0..3 (zzflate.cpp:201,230)"); return ZZ_E_LEVEL; }
     if (!d_dst || !d_src) { set_err("null buffer"); return ZZ_E_ARG; }
     if (n >= (1ull << 31)) { set_err("ranges: input must be < 2 GiB (the reference funnels lengths through int)"); return ZZ_E_ARG; }
@@ -1663,7 +1664,6 @@ static int encode_ranges(zz_ctx* c, const uint8_t* d_src, uint64_t n, uint8_t* d
         set_err("ranges: count too large for this input: (count - 1) * ceil(n / count) must be < n (zzflate.cpp:67-78 would cut ranges past the input's end)");
         return ZZ_E_ARG;
     }
-    begin_encode_call(c);
     HIPCHK(hipMemsetAsync(c->d_res, 0, sizeof(zz_result), st));
     HIPCHK(hipMemsetAsync(c->d_cks_total, 0, sizeof(zz_cks_total), st));
     HIPCHK(hipMemsetAsync(c->d_err, 0, 4 * sizeof(uint32_t), st));
