@@ -408,6 +408,70 @@ int zz_decode_members_device(zz_ctx* ctx, const void* d_src, uint64_t src_len, v
  * 1 blocked, chain verified in parallel; 2 blocked, chain walked; 3 serial (0: no call yet, or refused before a path was taken) */
 int zz_ctx_last_decode_members_stats(const zz_ctx* ctx, uint64_t* members, uint64_t* candidates, int* path);
 
+/* The index of a blocked gzip (BGZF) file, made on the device from the file alone. An index is `entries` = members + 1 pairs of
+ * uint64 in DEVICE memory, one array of 2 * entries words: d_index[2j] is the file offset of member j's first byte,
+ * d_index[2j + 1] the decoded offset of its first byte; the last pair is (the offset behind the last member, the decoded length
+ * L). This is bgzip's .gzi content with its omitted first and last pairs put back; an empty member (bgzip's 28-byte last one,
+ * or one in the middle of a file) is a member like any other, with two equal decoded offsets.
+ * How: mark, scan, fill, check and hop exactly as zz_decode_members_device makes them (its paths 1 and 2), then a scan of the
+ * members' ISIZE. NOTHING IS DECODED: the decoded offsets are the members' own claims, and a read through the index
+ * (zz_decode_members_ranges_device) is what checks them.
+ *   *entries = members + 1 is set even when max_entries is too small; the call then returns ZZ_E_NOSPACE and writes nothing
+ *     (as zz_packet_index_device: call with max_entries 0 for the size).
+ *   ZZ_E_UNSUPPORTED: the file is not blocked -- no member announces its length, or the chain from offset 0 cannot be walked
+ *     (members without `BC`, `cat a.gz b.gz`). Indexing such a file means decoding it, which zz_decode_members_device does.
+ *   ZZ_E_DATA: src_len == 0.
+ *   ZZ_E_ARG, before anything is launched: a null context, a null d_src with src_len > 0, a null d_index with max_entries > 0,
+ *     null entries, an unfinished zz_encode_device_async on the context.
+ * Workspace: zz_decode_members_device's mark pass, 12 bytes per 4 KiB of source and 12 bytes per header-like offset. Synchronous.
+ * Leaves the context's "last call", "last decode" and zz_ctx_last_decode_members_stats state alone. */
+int zz_members_index_device(zz_ctx* ctx, const void* d_src, uint64_t src_len,
+                            uint64_t* d_index, uint64_t max_entries,
+                            uint64_t* entries, void* hip_stream);
+
+/* Many reads of one blocked gzip (BGZF) file through its index in one call: read r receives the decoded bytes
+ * [d_firsts[r], d_firsts[r] + d_nbytes[r]) of the file d_src[0, src_len). d_index / entries are an index as above (from
+ * zz_members_index_device, from zz_encode_members_device's offsets, or from a .gzi file); the six arrays of nranges entries live
+ * in DEVICE memory (d_status may be NULL). With c_j, u_j the index's pairs and L = u_(entries - 1): d_out_lens[r] = m =
+ * min(nbytes, L - first), 0 with ZZ_OK for first == L or nbytes == 0; nothing is written outside d_dsts[r][0, min(m, cap)).
+ * A read whose status is not ZZ_OK has d_out_lens[r] = ~0 and the first min(m, cap) bytes of its destination are unspecified;
+ * it leaves every other read complete.
+ * CHECKED COMPLETELY: every byte a read returns comes from a member that was decoded whole and accepted exactly as
+ * zz_decode_batch_device accepts a gzip item -- header, blocks, CRC-32 and ISIZE, no byte behind the trailer -- and that holds
+ * exactly the u_(j+1) - u_j bytes (its ROOM) the index gives it. The index is never trusted: it proposes the cuts.
+ *   A member is TOUCHED by a read when it holds at least one byte of [first, first + m); empty members are never touched, and
+ *     reads with ZZ_E_ARG or ZZ_E_NOSPACE touch nothing. A touched member is decoded whole and judged whole -- the price of the
+ *     checksum -- and once per call, however many reads touch it.
+ *   d_status[r]: ZZ_OK; ZZ_E_ARG: first > L, or first + nbytes overflows; ZZ_E_NOSPACE: m > cap; ZZ_E_DATA: a member the read
+ *     touches is not what the index says -- decoding d_src[c_j, c_(j+1)) as one gzip member into u_(j+1) - u_j bytes of room
+ *     does not succeed with exactly that many bytes (header, blocks, truncation, CRC-32, ISIZE, bytes behind the trailer, a room
+ *     too small or too large); ZZ_E_UNSUPPORTED: no touched member is like that, but one has a room above 64 MiB (the stage).
+ *   Returns ZZ_OK when every read is ZZ_OK; otherwise ZZ_E_DATA if any read is, else ZZ_E_UNSUPPORTED, else ZZ_E_ARG, else
+ *     ZZ_E_NOSPACE (zz_decode_ranges_device's precedence).
+ *   ZZ_E_ARG, before anything is launched: a null context, source, index, d_firsts, d_nbytes, d_dsts, d_caps or d_out_lens;
+ *     entries < 2; entries - 1 or nranges above 2^31 - 1; an unfinished zz_encode_device_async on the context. nranges == 0 with
+ *     arguments that pass returns ZZ_OK at once.
+ *   Failure of the call as a whole, decided on the device: the index is not an index unless u_0 == 0, c ascends strictly, u
+ *     ascends and the last file offset is at most src_len. Then every d_status[r] = ZZ_E_DATA, every d_out_lens[r] = ~0, no
+ *     destination byte is written and the call returns ZZ_E_DATA.
+ * Reads may overlap each other; destinations that overlap are the caller's error.
+ * How: one thread per entry checks the index; one thread per read plans it (two binary searches, a +1 / -1 pair in
+ * a difference array over the members); a scan over the members gives the touched members, their slots on a stage and their
+ * waves (64 MiB of rooms each); per wave zz_decode_batch_device's kernel decodes the touched members into the stage, and the part
+ * of each read that lies in the wave -- one interval of the stage -- is copied out in 64 KiB chunks dealt over the workgroups.
+ * The host reads a fixed number of words for the plan, two per wave once, and two per wave's decode, whatever nranges and the
+ * member count are. A single small read costs one member's decode by ONE wavefront.
+ * Workspace: the stage, sized by the call's largest wave (below 128 MiB); 28 bytes per member; 44 bytes per touched member of the
+ * largest wave; 32 bytes per read; 16 bytes per wave. Synchronous. Leaves the context's "last call", "last decode",
+ * zz_ctx_last_decode_ranges_stats and zz_ctx_last_decode_members_stats state alone. */
+int zz_decode_members_ranges_device(zz_ctx* ctx, const void* d_src, uint64_t src_len,
+                                    const uint64_t* d_index, uint64_t entries,
+                                    uint64_t nranges, const uint64_t* d_firsts, const uint64_t* d_nbytes,
+                                    void* const* d_dsts, const uint64_t* d_caps,
+                                    uint64_t* d_out_lens, int32_t* d_status, void* hip_stream);
+/* what the last zz_decode_members_ranges_device did: the members it decoded (each once), and the waves */
+int zz_ctx_last_decode_members_ranges_stats(const zz_ctx* ctx, uint64_t* members_decoded, uint32_t* waves);
+
 enum { ZZ_DECODE_INDEXED = 1, ZZ_DECODE_DISCOVERED = 2, ZZ_DECODE_SERIAL = 3 };
 /* which path the last zz_decode_device finished on (0: none) */
 int zz_ctx_last_decode_path(const zz_ctx* ctx);

@@ -101,6 +101,9 @@ def _load():
         "zz_ctx_last_decode_ranges_stats": (i32, [vp, pu64, ctypes.POINTER(u32), pu64, ctypes.POINTER(u32)]),
         "zz_decode_members_device": (i32, [vp, vp, u64, vp, u64, pu64, vp]),
         "zz_ctx_last_decode_members_stats": (i32, [vp, pu64, pu64, ctypes.POINTER(i32)]),
+        "zz_members_index_device": (i32, [vp, vp, u64, vp, u64, pu64, vp]),
+        "zz_decode_members_ranges_device": (i32, [vp, vp, u64, vp, u64, u64, vp, vp, vp, vp, vp, vp, vp]),
+        "zz_ctx_last_decode_members_ranges_stats": (i32, [vp, pu64, ctypes.POINTER(u32)]),
         "zz_ctx_last_decode_path": (i32, [vp]),
         "zz_ctx_last_decode_stats": (i32, [vp, pu64, ctypes.POINTER(u32)]),
         "zz_ctx_last_decode_index_device": (i32, [vp, vp, u64, pu64, vp]),
@@ -252,6 +255,21 @@ def gzi_bytes(offsets, n, block_size=MEMBERS_BLOCK):
     for i in range(1, members):
         out.append(struct.pack("<QQ", offsets[i], i * block_size))
     return b"".join(out)
+
+
+def members_index_from_offsets(offsets, n, block_size=MEMBERS_BLOCK, eof=True):
+    """The index ``Context.decode_members_ranges`` takes, by arithmetic, for a file ``Context.encode_members`` wrote from ``n``
+    input bytes: a list of (file offset, decoded offset) pairs, one per member and one behind the last. ``offsets`` is the host
+    copy of the call's offsets array (data members + 1 entries); member i begins at decoded offset ``min(i * block_size, n)``;
+    with ``eof`` one more pair follows for the 28-byte empty last member."""
+    offsets = [int(v) for v in offsets]
+    members = len(offsets) - 1
+    if members < 0 or members != -(-n // block_size):
+        raise ValueError(f"{len(offsets)} offsets do not describe {n} bytes in blocks of {block_size}")
+    pairs = [(offsets[i], min(i * block_size, n)) for i in range(members + 1)]
+    if eof:
+        pairs.append((offsets[members] + 28, n))
+    return pairs
 
 
 def generate_host(kind, seed, first_byte, n):
@@ -631,6 +649,70 @@ class Context:
         m, cand, path = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_int(0)
         _check(lib.zz_ctx_last_decode_members_stats(self._h, ctypes.byref(m), ctypes.byref(cand), ctypes.byref(path)))
         return m.value, cand.value, path.value
+
+    def members_index(self, src, src_len, stream=None):
+        """The index of the blocked gzip (BGZF) file ``src[:src_len]``, made on the device from the file alone: an int64 tensor of
+        shape ``[members + 1, 2]`` on this context's device -- (file offset, decoded offset) of every member's first byte, then
+        (the offset behind the last member, the decoded length). Nothing is decoded: the decoded offsets are the members' own
+        claims, which ``decode_members_ranges`` checks. Raises ZzFlateError (E_UNSUPPORTED: the file is not blocked --
+        ``decode_members`` decodes it; E_DATA: an empty file)."""
+        import torch
+        entries = ctypes.c_uint64(0)
+        st = self._stream() if stream is None else stream
+        rc = lib.zz_members_index_device(self._h, self._ptr(src), src_len, None, 0, ctypes.byref(entries), st)
+        if rc != E_NOSPACE:
+            _check(rc)
+        idx = torch.empty((entries.value, 2), dtype=torch.int64, device=f"cuda:{self.device}")
+        _check(lib.zz_members_index_device(self._h, self._ptr(src), src_len, idx.data_ptr(), entries.value, ctypes.byref(entries), st))
+        return idx
+
+    def decode_members_ranges(self, src, src_len, index, firsts, nbytes, dsts, caps=None, stream=None):
+        """Many reads of one blocked gzip (BGZF) file in one call: read r = decoded bytes ``[firsts[r], firsts[r] + nbytes[r])``
+        of the file ``src[:src_len]`` into ``dsts[r]``. ``index`` is an int64 tensor of shape ``[members + 1, 2]`` on this
+        context's device (``members_index``, or ``members_index_from_offsets`` moved there); ``dsts`` are items as
+        ``decode_batch`` takes them; ``caps`` defaults to ``min(nbytes[r], destination size)``. Returns ``(lens, status)``:
+        ``lens[r]`` the bytes read (clipped at the file's decoded length) or ``None``, ``status[r]`` 0, E_ARG, E_NOSPACE, E_DATA
+        or E_UNSUPPORTED -- a read's own failure does not raise and leaves the others complete; an index that is not an index
+        gives every read E_DATA; only a refused call (arguments) raises. Every member a read touches is decoded whole and
+        checked completely: CRC-32, ISIZE and the length the index gives it."""
+        import torch
+        if not isinstance(index, torch.Tensor) or index.dtype != torch.int64 or index.dim() != 2 or index.shape[1] != 2 or not index.is_contiguous():
+            raise TypeError("index must be a contiguous int64 tensor of shape [members + 1, 2] (as members_index() returns)")
+        if index.device.type != "cuda" or index.device.index != self.device:
+            raise ValueError(f"index must live on this context's device (cuda:{self.device}), not {index.device}")
+        k = len(firsts)
+        if len(nbytes) != k or len(dsts) != k:
+            raise ValueError(f"{k} starts but {len(nbytes)} lengths and {len(dsts)} destinations")
+        if caps is not None and len(caps) != k:
+            raise ValueError(f"{len(caps)} capacities for {k} reads")
+        if k == 0:
+            return [], []
+        d = [self._item(t) for t in dsts]
+        cp = [min(int(n), nb) for n, (_, nb) in zip(nbytes, d)] if caps is None else [int(c) for c in caps]
+        dev = f"cuda:{self.device}"
+        mask = (1 << 64) - 1
+
+        def i64(v):                                    # uint64 values travel as the int64 of the same bits
+            v = int(v) & mask
+            return v - (1 << 64) if v >> 63 else v
+        table = torch.tensor([[i64(v) for v in firsts], [i64(v) for v in nbytes], [i64(p) for p, _ in d], [i64(v) for v in cp]],
+                             dtype=torch.int64).to(dev)
+        out = torch.empty(k, dtype=torch.int64, device=dev)
+        status = torch.empty(k, dtype=torch.int32, device=dev)
+        st = self._stream() if stream is None else stream
+        rc = lib.zz_decode_members_ranges_device(self._h, self._ptr(src), src_len, index.data_ptr(), index.shape[0],
+                                                 k, table[0].data_ptr(), table[1].data_ptr(), table[2].data_ptr(), table[3].data_ptr(),
+                                                 out.data_ptr(), status.data_ptr(), st)
+        if rc != 0 and not lib.zz_last_error().startswith(b"reads: "):
+            _check(rc)                                 # the call itself was refused (the library words a read's own failure "reads: ...")
+        status = status.cpu().tolist()
+        return [None if sv != 0 else v for v, sv in zip(out.cpu().tolist(), status)], status
+
+    def last_decode_members_ranges_stats(self):
+        """(members decoded, each once; waves) of the last ``decode_members_ranges``."""
+        m, waves = ctypes.c_uint64(0), ctypes.c_uint32(0)
+        _check(lib.zz_ctx_last_decode_members_ranges_stats(self._h, ctypes.byref(m), ctypes.byref(waves)))
+        return m.value, waves.value
 
     def last_decode_path(self):
         """DECODE_INDEXED, DECODE_DISCOVERED or DECODE_SERIAL: the path the last decode finished on (0: none)."""

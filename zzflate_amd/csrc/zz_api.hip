@@ -32,6 +32,7 @@
 #include "zz_inflate.h"
 #include "zz_inflate_ranges.h"
 #include "zz_inflate_members.h"
+#include "zz_inflate_members_ranges.h"
 #include "zz_batch.h"
 #include "zz_members_write.h"
 
@@ -201,6 +202,18 @@ struct zz_ctx {
             zz_buf<zz_inf_members_out> sres; zz_pin<zz_inf_members_out> h_sres;
             uint64_t members = 0, candidates = 0; int path = 0;
         } mem;
+        // zz_decode_members_ranges_device (zz_inflate_members_ranges.h): the stage, per read (record, chunk scan), per member
+        // (differences, counts), per touched member (list, S, F, G), per item of a wave its status, per wave two words, what the
+        // host reads; k_inflate_items' descriptors are mem's
+        struct {
+            zz_buf<uint8_t> stage;
+            zz_buf<zi_mr_read> reads; zz_buf<uint64_t> chunk0;
+            zz_buf<int32_t> diff; zz_buf<uint32_t> cnt, tlist, F, G; zz_buf<uint64_t> S;
+            zz_buf<int32_t> status;
+            zz_buf<uint64_t> waves; zz_pin<uint64_t> h_waves;
+            zz_buf<zz_mr_state> st; zz_pin<zz_mr_state> h_st;
+            uint64_t members_decoded = 0; uint32_t waves_run = 0;
+        } mr;
     } dec;
 };
 // one call per context at a time: every entry point that would use the buffers of an enqueued call refuses
@@ -2116,6 +2129,49 @@ static int dec_members_serial(zz_ctx* c, const uint8_t* src, uint64_t n, uint8_t
     return ZZ_E_DATA;
 }
 
+// The front of the blocked path, for zz_decode_members_device and zz_members_index_device: mark (count per stretch, scan, and
+// the one number that sizes the candidates' buffers: one readback), fill, check and hop (only if the check failed), enqueued
+// and not waited for. *ncand: the candidates; *listed: the member list is being made in mem.offs / mem.lens and mem.st will say
+// whether it stands (false: no candidates, or more than one launch's grid holds).
+static int members_front(zz_ctx* c, const uint8_t* src, uint64_t src_len, hipStream_t st, uint64_t* ncand_out, bool* listed)
+{
+    auto& M = c->dec.mem;
+    *ncand_out = 0; *listed = false;
+    const uint64_t nblk = (src_len + ZZ_MEM_STRETCH - 1) / ZZ_MEM_STRETCH;
+    if (nblk > 0x7FFFFFFFull) return ZZ_OK;                              // (8 TiB of source: beyond one launch's grid)
+    if (int rc = M.blk_cnt.grow(nblk)) return rc;
+    if (int rc = M.blk_base.grow(nblk)) return rc;
+    if (int rc = M.st.grow(1)) return rc;
+    if (int rc = M.h_st.grow(1)) return rc;
+    HIPCHK(hipMemsetAsync(M.st, 0, sizeof(zz_mem_state), st));
+    HIPCHK(hipMemsetAsync(&M.st->mstar, 0xFF, sizeof(unsigned long long), st));
+    hipLaunchKernelGGL(k_members_mark<false>, dim3((uint32_t)nblk), dim3(ZZ_MEM_THREADS), 0, st, src, src_len, (uint32_t*)M.blk_cnt,
+                       (const uint64_t*)nullptr, (uint64_t*)nullptr, (uint32_t*)nullptr);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(k_members_scan, dim3(1), dim3(ZZ_MEM_SCAN_THREADS), 0, st, (const uint32_t*)M.blk_cnt, nblk, (uint64_t*)M.blk_base,
+                       (zz_mem_state*)M.st);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(M.h_st, M.st, sizeof(zz_mem_state), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    const uint64_t ncand = M.h_st->candidates;
+    *ncand_out = ncand;
+    if (ncand == 0 || ncand > 0x7FFFFFFFull) return ZZ_OK;
+    if (int rc = M.offs.grow(ncand)) return rc;
+    if (int rc = M.lens.grow(ncand)) return rc;
+    hipLaunchKernelGGL(k_members_mark<true>, dim3((uint32_t)nblk), dim3(ZZ_MEM_THREADS), 0, st, src, src_len, (uint32_t*)M.blk_cnt,
+                       (const uint64_t*)M.blk_base, (uint64_t*)M.offs, (uint32_t*)M.lens);
+    HIPCHK(hipGetLastError());
+    const uint64_t cgrid = (ncand + 255) / 256;
+    hipLaunchKernelGGL(k_members_check, dim3((uint32_t)(cgrid < 2048 ? cgrid : 2048)), dim3(256), 0, st, (const uint64_t*)M.offs,
+                       (const uint32_t*)M.lens, ncand, src_len, (zz_mem_state*)M.st);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(k_members_hop, dim3(1), dim3(ZZ_WAVE), 0, st, src, src_len, (uint64_t*)M.offs, (uint32_t*)M.lens, ncand,
+                       (zz_mem_state*)M.st);
+    HIPCHK(hipGetLastError());
+    *listed = true;
+    return ZZ_OK;
+}
+
 extern "C" int zz_decode_members_device(zz_ctx* c, const void* d_src_v, uint64_t src_len, void* d_dst_v, uint64_t cap, uint64_t* out_len,
                                         void* hip_stream)
 {
@@ -2134,45 +2190,17 @@ extern "C" int zz_decode_members_device(zz_ctx* c, const void* d_src_v, uint64_t
     uint8_t* dst = (uint8_t*)d_dst_v;
     const auto serial = [&]() -> int { return dec_members_serial(c, src, src_len, dst, cap, st, out_len, 0, 0, 3); };     // (writes *out_len on ZZ_OK only)
 
-    // mark: count per stretch, scan, and the one number that sizes the candidates' buffers
-    const uint64_t nblk = (src_len + ZZ_MEM_STRETCH - 1) / ZZ_MEM_STRETCH;
-    if (nblk > 0x7FFFFFFFull) return serial();                           // (8 TiB of source: beyond one launch's grid)
-    if (int rc = M.blk_cnt.grow(nblk)) return rc;
-    if (int rc = M.blk_base.grow(nblk)) return rc;
-    if (int rc = M.st.grow(1)) return rc;
-    if (int rc = M.h_st.grow(1)) return rc;
-    HIPCHK(hipMemsetAsync(M.st, 0, sizeof(zz_mem_state), st));
-    HIPCHK(hipMemsetAsync(&M.st->mstar, 0xFF, sizeof(unsigned long long), st));
-    hipLaunchKernelGGL(k_members_mark<false>, dim3((uint32_t)nblk), dim3(ZZ_MEM_THREADS), 0, st, src, src_len, (uint32_t*)M.blk_cnt,
-                       (const uint64_t*)nullptr, (uint64_t*)nullptr, (uint32_t*)nullptr);
-    HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(k_members_scan, dim3(1), dim3(ZZ_MEM_SCAN_THREADS), 0, st, (const uint32_t*)M.blk_cnt, nblk, (uint64_t*)M.blk_base,
-                       (zz_mem_state*)M.st);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(M.h_st, M.st, sizeof(zz_mem_state), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    const uint64_t ncand = M.h_st->candidates;
+    uint64_t ncand = 0; bool listed = false;
+    if (int rc = members_front(c, src, src_len, st, &ncand, &listed)) return rc;
     M.candidates = ncand;
-    if (ncand == 0 || ncand > 0x7FFFFFFFull) return serial();
+    if (!listed) return serial();
 
-    // fill, check, hop (only if the check failed), slots: one readback for all of them
-    if (int rc = M.offs.grow(ncand)) return rc;
-    if (int rc = M.lens.grow(ncand)) return rc;
+    // slots: one readback for fill, check, hop (only if the check failed) and slots
     if (int rc = M.srcs.grow(ncand)) return rc;
     if (int rc = M.dsts.grow(ncand)) return rc;
     if (int rc = M.src_lens.grow(ncand)) return rc;
     if (int rc = M.caps.grow(ncand)) return rc;
     if (int rc = M.out_lens.grow(ncand)) return rc;
-    hipLaunchKernelGGL(k_members_mark<true>, dim3((uint32_t)nblk), dim3(ZZ_MEM_THREADS), 0, st, src, src_len, (uint32_t*)M.blk_cnt,
-                       (const uint64_t*)M.blk_base, (uint64_t*)M.offs, (uint32_t*)M.lens);
-    HIPCHK(hipGetLastError());
-    const uint64_t cgrid = (ncand + 255) / 256;
-    hipLaunchKernelGGL(k_members_check, dim3((uint32_t)(cgrid < 2048 ? cgrid : 2048)), dim3(256), 0, st, (const uint64_t*)M.offs,
-                       (const uint32_t*)M.lens, ncand, src_len, (zz_mem_state*)M.st);
-    HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(k_members_hop, dim3(1), dim3(ZZ_WAVE), 0, st, src, src_len, (uint64_t*)M.offs, (uint32_t*)M.lens, ncand,
-                       (zz_mem_state*)M.st);
-    HIPCHK(hipGetLastError());
     zz_mem_slots q;
     q.src = src; q.n = src_len; q.dst = dst; q.cap = cap; q.offs = M.offs; q.lens = M.lens;
     q.srcs = M.srcs; q.src_lens = M.src_lens; q.dsts = M.dsts; q.caps = M.caps; q.st = M.st;
@@ -2209,6 +2237,151 @@ extern "C" int zz_ctx_last_decode_members_stats(const zz_ctx* c, uint64_t* membe
     if (members) *members = c->dec.mem.members;
     if (candidates) *candidates = c->dec.mem.candidates;
     if (path) *path = c->dec.mem.path;
+    return ZZ_OK;
+}
+
+// ---- a blocked file's index, and reads through it (zz_inflate_members_ranges.h) -----------------------------------------------
+extern "C" int zz_members_index_device(zz_ctx* c, const void* d_src_v, uint64_t src_len, uint64_t* d_index, uint64_t max_entries,
+                                       uint64_t* entries, void* hip_stream)
+{
+    if (entries) *entries = 0;
+    if (!c) { set_err("null ctx"); return ZZ_E_ARG; }
+    if (!entries) { set_err("null entries"); return ZZ_E_ARG; }
+    if (!d_src_v && src_len) { set_err("null source"); return ZZ_E_ARG; }
+    if (!d_index && max_entries) { set_err("null index"); return ZZ_E_ARG; }
+    if (call_pending(c)) return ZZ_E_ARG;
+    if (src_len == 0) { set_err("an empty file holds no gzip member"); return ZZ_E_DATA; }
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t st = (hipStream_t)hip_stream;
+    const uint8_t* src = (const uint8_t*)d_src_v;
+    auto& M = c->dec.mem;
+    uint64_t ncand = 0; bool listed = false;
+    if (int rc = members_front(c, src, src_len, st, &ncand, &listed)) return rc;
+    if (listed) {
+        HIPCHK(hipMemcpyAsync(M.h_st, M.st, sizeof(zz_mem_state), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+    }
+    if (!listed || !M.h_st->blocked) {
+        set_err("not a blocked file: its members do not announce their lengths (BC) one after the other; zz_decode_members_device decodes it");
+        return ZZ_E_UNSUPPORTED;
+    }
+    const uint64_t members = M.h_st->members;
+    *entries = members + 1;
+    if (max_entries < members + 1) { set_err("the index has " + std::to_string(members + 1) + " entries"); return ZZ_E_NOSPACE; }
+    hipLaunchKernelGGL(k_members_pairs, dim3(1), dim3(ZZ_MR_SCAN_THREADS), 0, st, src, src_len, (const uint64_t*)M.offs, (const uint32_t*)M.lens,
+                       members, d_index);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(st));
+    return ZZ_OK;
+}
+
+extern "C" int zz_decode_members_ranges_device(zz_ctx* c, const void* d_src_v, uint64_t src_len, const uint64_t* d_index, uint64_t entries,
+                                               uint64_t nranges, const uint64_t* d_firsts, const uint64_t* d_nbytes,
+                                               void* const* d_dsts, const uint64_t* d_caps,
+                                               uint64_t* d_out_lens, int32_t* d_status, void* hip_stream)
+{
+    if (!c || !d_src_v || !d_index || !d_firsts || !d_nbytes || !d_dsts || !d_caps || !d_out_lens) { set_err("null argument"); return ZZ_E_ARG; }
+    if (entries < 2) { set_err("the index needs at least two entries (members + 1)"); return ZZ_E_ARG; }
+    if (entries - 1 > 0x7fffffffull) { set_err("at most 2^31 - 1 members per index"); return ZZ_E_ARG; }
+    if (nranges > 0x7fffffffull) { set_err("at most 2^31 - 1 reads per call"); return ZZ_E_ARG; }
+    if (nranges == 0) return ZZ_OK;                                 // nothing to do: the context is not looked at
+    if (call_pending(c)) return ZZ_E_ARG;
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t st = (hipStream_t)hip_stream;
+    auto& R = c->dec.mr;
+    auto& M = c->dec.mem;
+    R.members_decoded = 0; R.waves_run = 0;
+    const uint64_t members = entries - 1;
+    if (int rc = R.st.grow(1)) return rc;
+    if (int rc = R.h_st.grow(1)) return rc;
+    if (int rc = R.reads.grow(nranges)) return rc;
+    if (int rc = R.chunk0.grow(nranges + 1)) return rc;
+    if (int rc = R.diff.grow(entries)) return rc;
+    if (int rc = R.cnt.grow(entries)) return rc;
+    if (int rc = R.tlist.grow(entries)) return rc;
+    if (int rc = R.S.grow(entries)) return rc;
+    if (int rc = R.F.grow(entries)) return rc;
+    if (int rc = R.G.grow(entries)) return rc;
+    zz_mr_params Q;
+    Q.src = (const uint8_t*)d_src_v; Q.src_len = src_len; Q.idx = d_index; Q.entries = entries;
+    Q.nranges = nranges; Q.firsts = d_firsts; Q.nbytes = d_nbytes; Q.dsts = (uint8_t* const*)d_dsts; Q.caps = d_caps;
+    Q.out_lens = d_out_lens; Q.status = d_status;
+    Q.reads = R.reads; Q.chunk0 = R.chunk0; Q.diff = R.diff; Q.cnt = R.cnt; Q.tlist = R.tlist; Q.S = R.S; Q.F = R.F; Q.G = R.G;
+    Q.stage = nullptr; Q.st = R.st;
+    const auto grid = [](uint64_t n) { return dim3((uint32_t)std::min<uint64_t>((n + 255) / 256, 4096)); };
+
+    // check, plan, touched: one readback
+    HIPCHK(hipMemsetAsync(R.st, 0, sizeof(zz_mr_state), st));
+    HIPCHK(hipMemsetAsync(R.diff, 0, entries * sizeof(int32_t), st));
+    hipLaunchKernelGGL(k_mr_check, grid(entries), dim3(256), 0, st, Q);
+    hipLaunchKernelGGL(k_mr_plan, grid(nranges), dim3(256), 0, st, Q);
+    hipLaunchKernelGGL(k_mr_touched, dim3(1), dim3(ZZ_MR_SCAN_THREADS), 0, st, Q);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(R.h_st, R.st, sizeof(zz_mr_state), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (R.h_st->index_bad) {
+        set_err("reads: all fail, the index is not an index of this file (decoded offsets from 0 ascending, file offsets strictly ascending and inside the source)");
+        return ZZ_E_DATA;
+    }
+    const uint64_t touched = R.h_st->touched, nwaves = R.h_st->nwaves;
+    if (touched) {
+        // the waves' first ranks and S there: one readback
+        if (int rc = R.waves.grow(2 * (nwaves + 1))) return rc;
+        if (int rc = R.h_waves.grow(2 * (nwaves + 1))) return rc;
+        hipLaunchKernelGGL(k_mr_waves, grid(nwaves + 1), dim3(256), 0, st, Q, nwaves, (uint64_t*)R.waves);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(R.h_waves, R.waves, 2 * (nwaves + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        const uint64_t* W = R.h_waves.p;
+        uint64_t big_items = 0, big_bytes = 0;
+        for (uint64_t w = 0; w < nwaves; ++w) {
+            big_items = std::max(big_items, W[2 * w + 2] - W[2 * w]);
+            big_bytes = std::max(big_bytes, W[2 * w + 3] - W[2 * w + 1]);
+        }
+        if (int rc = R.stage.grow(big_bytes + 16)) return rc;
+        if (int rc = M.srcs.grow(big_items)) return rc;
+        if (int rc = M.dsts.grow(big_items)) return rc;
+        if (int rc = M.src_lens.grow(big_items)) return rc;
+        if (int rc = M.caps.grow(big_items)) return rc;
+        if (int rc = M.out_lens.grow(big_items)) return rc;
+        if (int rc = R.status.grow(big_items)) return rc;
+        Q.stage = R.stage;
+        for (uint64_t w = 0; w < nwaves; ++w) {
+            const uint64_t t0 = W[2 * w], t1 = W[2 * w + 2];
+            if (t1 <= t0) continue;                                     // (cannot happen: a room is at most one wave's)
+            ++R.waves_run;
+            hipLaunchKernelGGL(k_mr_desc, grid(t1 - t0), dim3(256), 0, st, Q, t0, t1, (const uint8_t**)M.srcs.p, (uint64_t*)M.src_lens,
+                               (uint8_t**)M.dsts.p, (uint64_t*)M.caps);
+            HIPCHK(hipGetLastError());
+            zz_inf_items_params p;
+            p.srcs = (const uint8_t* const*)M.srcs.p; p.src_lens = M.src_lens; p.dsts = (uint8_t* const*)M.dsts.p; p.caps = M.caps;
+            p.out_lens = M.out_lens; p.status = R.status; p.nitems = (uint32_t)(t1 - t0); p.format = ZZ_GZIP;
+            if (int rc = dec_items(c, p, st)) return rc;
+            hipLaunchKernelGGL(k_mr_judge, dim3(1), dim3(ZZ_MR_SCAN_THREADS), 0, st, Q, t0, t1, (const uint64_t*)M.caps, (const uint64_t*)M.out_lens,
+                               (const int32_t*)R.status);
+            hipLaunchKernelGGL(k_mr_cut, dim3(1), dim3(ZZ_MR_SCAN_THREADS), 0, st, Q, t0, t1);
+            hipLaunchKernelGGL(k_mr_copy, dim3(ZZ_MR_COPY_GRID), dim3(256), 0, st, Q, t0, t1);
+            HIPCHK(hipGetLastError());
+        }
+        R.members_decoded = touched - R.h_st->big;
+    }
+    hipLaunchKernelGGL(k_mr_verdict, grid(nranges), dim3(256), 0, st, Q);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(R.h_st, R.st, sizeof(zz_mr_state), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    const zz_mr_state& T = *R.h_st.p;
+    if (T.n_data) { set_err("reads: " + std::to_string(T.n_data) + " touch a member that is not what the index says"); return ZZ_E_DATA; }
+    if (T.n_unsupported) { set_err("reads: " + std::to_string(T.n_unsupported) + " touch a member whose room exceeds the stage (64 MiB)"); return ZZ_E_UNSUPPORTED; }
+    if (T.n_arg) { set_err("reads: " + std::to_string(T.n_arg) + " start behind the decoded length or overflow"); return ZZ_E_ARG; }
+    if (T.n_nospace) { set_err("reads: " + std::to_string(T.n_nospace) + " do not fit their destinations"); return ZZ_E_NOSPACE; }
+    return ZZ_OK;
+}
+
+extern "C" int zz_ctx_last_decode_members_ranges_stats(const zz_ctx* c, uint64_t* members_decoded, uint32_t* waves)
+{
+    if (!c) { set_err("null context"); return ZZ_E_ARG; }
+    if (members_decoded) *members_decoded = c->dec.mr.members_decoded;
+    if (waves) *waves = c->dec.mr.waves_run;
     return ZZ_OK;
 }
 

@@ -843,4 +843,136 @@ ZZ_HD inline int zi_members_verdict(bool have_mstar, uint64_t n_data, uint64_t n
     return ZI_MEMBERS_SERIAL;
 }
 
+// ---- reads of a member file through an index (zz_decode_members_ranges_device; tests/cxx/inflate_members_ranges_harness.cpp) ----
+// The INDEX is `entries` = members + 1 pairs (c_j, u_j): member j is claimed to be src[c_j, c_(j+1)) and to hold the decoded
+// bytes [u_j, u_(j+1)) -- its ROOM u_(j+1) - u_j; L = u_(members) is the decoded length. It is an index iff u_0 = 0, c ascends
+// strictly, u ascends and c_(members) <= src_len (zi_mr_entry_bad: one entry, one answer); otherwise the call fails as a whole.
+// Nothing else of it is trusted: it proposes the cuts, and zi_item judges every member it cuts out -- a member is what the index
+// says iff zi_item(gzip) on its bytes, given its room, answers ZI_ITEM_OK with exactly `room` bytes (zi_mr_member_bad).
+//
+// A READ (first, nbytes, cap) returns m = min(nbytes, L - first) bytes. The plan settles ZI_RV_ARG (first > L, or first + nbytes
+// overflows) and ZI_RV_NOSPACE (m > cap); such a read touches nothing, and neither does one with m = 0. Any other read TOUCHES
+// the members that hold a byte of [first, first + m): the non-empty members of [j0, j1], j0 = upper_bound(u, first) - 1 (the
+// members in front of it that begin at `first` too are empty) and j1 = upper_bound(u, first + m - 1) - 1. Coverage is a
+// difference array over the members, +1 at j0 and -1 at j1 + 1, so a read costs two searches whatever it spans.
+//
+// TOUCHED members, in file order, have ranks t = 0, 1, ..; S_t is the exclusive sum of their rooms and their stage slots follow
+// one another: a member with a room above ZZ_MR_STAGE is BIG, takes no room on the stage and is not decoded, and the reads that
+// touch it are ZI_RV_UNSUPPORTED. WAVE w holds the ranks with floor(S_t / ZZ_MR_STAGE) = w: less than ZZ_MR_STAGE plus one room
+// of stage. The members a read touches have consecutive ranks [a, b), so what a wave holds of a read is ONE interval of its
+// stage (zi_mr_cut). F is the exclusive count of members that are not what the index says, G that of big ones, both over the
+// ranks: a read is ZI_RV_DATA iff F_b != F_a, else ZI_RV_UNSUPPORTED iff G_b != G_a, else ZI_RV_OK (zi_mr_verdict).
+#ifndef ZZ_MR_STAGE
+#define ZZ_MR_STAGE (64ull << 20)
+#endif
+#define ZZ_MR_CHUNK 65536u               // bytes of a read's interval that one workgroup copies at a time
+#define ZI_MR_BIG 0x80000000u            // in the touched list: the member is big
+struct zi_mr_read {
+    uint64_t m;            // bytes the read returns (valid unless status is ZI_RV_ARG)
+    uint32_t j0, j1;       // first and last member it touches (valid when `any`)
+    int32_t status;        // the plan's: ZI_RV_OK, ZI_RV_ARG, ZI_RV_NOSPACE
+    uint32_t any;          // it touches members
+};
+struct zi_mr_tables {
+    zi_view<const uint64_t> idx;       // 2 * entries words
+    zi_view<const uint32_t> cnt;       // entries: touched members in front of member j; cnt[members] = their number T
+    zi_view<const uint32_t> tlist;     // T: the member of rank t (| ZI_MR_BIG)
+    zi_view<const uint64_t> S;         // T + 1
+    zi_view<const uint32_t> F, G;      // T + 1 each
+};
+ZZ_HD inline uint64_t zi_mr_c(const zi_view<const uint64_t>& idx, uint64_t j) { return idx[2 * j]; }
+ZZ_HD inline uint64_t zi_mr_u(const zi_view<const uint64_t>& idx, uint64_t j) { return idx[2 * j + 1]; }
+ZZ_HD inline uint64_t zi_mr_room(const zi_view<const uint64_t>& idx, uint64_t j) { return zi_mr_u(idx, j + 1) - zi_mr_u(idx, j); }
+ZZ_HD inline bool zi_mr_entry_bad(const zi_view<const uint64_t>& idx, uint64_t entries, uint64_t j, uint64_t src_len)
+{
+    if (j == 0 && zi_mr_u(idx, 0) != 0) return true;
+    if (j + 1 == entries) return zi_mr_c(idx, j) > src_len;
+    return zi_mr_c(idx, j) >= zi_mr_c(idx, j + 1) || zi_mr_u(idx, j) > zi_mr_u(idx, j + 1);
+}
+// the first entry whose decoded offset lies behind x (entries: none)
+ZZ_HD inline uint64_t zi_mr_upper(const zi_view<const uint64_t>& idx, uint64_t entries, uint64_t x)
+{
+    uint64_t lo = 0, hi = entries;
+    while (lo < hi) {
+        const uint64_t mid = lo + (hi - lo) / 2;
+        if (zi_mr_u(idx, mid) <= x) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo;
+}
+// PLAN of one read over an index that passed the check (so 1 <= upper_bound(x) <= members for every x < L)
+ZZ_HD inline zi_mr_read zi_mr_plan(const zi_view<const uint64_t>& idx, uint64_t entries, uint64_t first, uint64_t nbytes, uint64_t cap)
+{
+    zi_mr_read R{ 0, 0, 0, ZI_RV_OK, 0 };
+    const uint64_t L = zi_mr_u(idx, entries - 1);
+    if (first > L || first + nbytes < first) { R.status = ZI_RV_ARG; return R; }
+    R.m = nbytes < L - first ? nbytes : L - first;
+    if (R.m > cap) { R.status = ZI_RV_NOSPACE; return R; }
+    if (R.m == 0) return R;
+    const uint64_t members = entries - 1;
+    uint64_t a = zi_mr_upper(idx, entries, first), b = zi_mr_upper(idx, entries, first + R.m - 1);
+    a = a ? a - 1 : 0; b = b ? b - 1 : 0;
+    if (a >= members) a = members - 1;
+    if (b >= members) b = members - 1;
+    R.j0 = (uint32_t)a; R.j1 = (uint32_t)b; R.any = 1;
+    return R;
+}
+// TOUCHED: what member j is, from its room and the reads that cover it: 0 untouched, 1 touched, 2 touched and big
+ZZ_HD inline uint32_t zi_mr_touch(uint64_t room, int32_t cover) { return cover > 0 && room ? (room > ZZ_MR_STAGE ? 2u : 1u) : 0u; }
+ZZ_HD inline uint64_t zi_mr_wave(uint64_t S) { return S / ZZ_MR_STAGE; }
+// the first rank of [0, T) whose S is at or behind x (T: none): where wave x / ZZ_MR_STAGE begins
+ZZ_HD inline uint64_t zi_mr_wave_first(const zi_view<const uint64_t>& S, uint64_t T, uint64_t x)
+{
+    uint64_t lo = 0, hi = T;
+    while (lo < hi) {
+        const uint64_t mid = lo + (hi - lo) / 2;
+        if (S[mid] < x) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo;
+}
+// DESCRIPTOR of the member of rank t in the wave that begins at rank t0: its bytes in the source and its slot on the stage. A big
+// member, and one the index puts outside the source, gets no bytes: zi_item refuses it without reading or writing anything.
+struct zi_mr_slot { uint64_t src_off, src_len, stage_off, room; };
+ZZ_HD inline zi_mr_slot zi_mr_desc(const zi_mr_tables& T, uint64_t t, uint64_t t0, uint64_t src_len)
+{
+    const uint32_t e = T.tlist[t];
+    const uint64_t j = e & ~ZI_MR_BIG, c0 = zi_mr_c(T.idx, j), c1 = zi_mr_c(T.idx, j + 1);
+    if ((e & ZI_MR_BIG) || c1 > src_len || c1 < c0) return zi_mr_slot{ 0, 0, 0, 0 };
+    return zi_mr_slot{ c0, c1 - c0, T.S[t] - T.S[t0], zi_mr_room(T.idx, j) };
+}
+ZZ_HD inline bool zi_mr_member_bad(uint32_t entry, int32_t status, uint64_t out, uint64_t room)
+{
+    return !(entry & ZI_MR_BIG) && !(status == ZI_ITEM_OK && out == room);
+}
+// CUT: what the wave of ranks [t0, t1) holds of a read -- `len` bytes at `stage_off` of its stage, for dst + dst_off. Nothing
+// for a read the plan settled, one that touches a big member, one whose ranks miss the wave, and one that touches a member of
+// this wave that is not what the index says (F is known up to t1 when this is asked). dst_off + len <= m <= cap.
+struct zi_mr_piece { uint64_t stage_off, dst_off, len; };
+ZZ_HD inline zi_mr_piece zi_mr_cut(const zi_mr_read& R, uint64_t first, const zi_mr_tables& T, uint64_t t0, uint64_t t1)
+{
+    zi_mr_piece p{ 0, 0, 0 };
+    if (R.status != ZI_RV_OK || !R.any) return p;
+    const uint64_t a = T.cnt[R.j0], b = T.cnt[(uint64_t)R.j1 + 1];
+    if (T.G[b] != T.G[a]) return p;
+    const uint64_t ta = a > t0 ? a : t0, tb = b < t1 ? b : t1;
+    if (ta >= tb || T.F[tb] != T.F[ta]) return p;
+    const uint64_t ja = T.tlist[ta] & ~ZI_MR_BIG, jb = T.tlist[tb - 1] & ~ZI_MR_BIG;
+    const uint64_t ua = zi_mr_u(T.idx, ja), ub = zi_mr_u(T.idx, jb);
+    const uint64_t d0 = ta == a ? first : ua;                              // decoded offsets of the piece: [d0, d1)
+    const uint64_t d1 = tb == b ? first + R.m : zi_mr_u(T.idx, jb + 1);
+    const uint64_t s0 = T.S[ta] - T.S[t0] + (d0 - ua), s1 = T.S[tb - 1] - T.S[t0] + (d1 - ub);
+    p.stage_off = s0; p.dst_off = d0 - first; p.len = s1 - s0;
+    return p;
+}
+ZZ_HD inline uint64_t zi_mr_chunks(uint64_t len) { return (len + ZZ_MR_CHUNK - 1) / ZZ_MR_CHUNK; }
+ZZ_HD inline int zi_mr_verdict(const zi_mr_read& R, const zi_mr_tables& T)
+{
+    if (R.status != ZI_RV_OK || !R.any) return R.status;
+    const uint64_t a = T.cnt[R.j0], b = T.cnt[(uint64_t)R.j1 + 1];
+    if (T.F[b] != T.F[a]) return ZI_RV_DATA;
+    if (T.G[b] != T.G[a]) return ZI_RV_UNSUPPORTED;
+    return ZI_RV_OK;
+}
+
 }  // namespace zz
