@@ -324,7 +324,8 @@ int zz_decode_batch_device(zz_ctx* ctx, uint64_t nitems, const void* const* d_sr
  * refused at the parallel rate -- and a call never takes less than one wavefront needs for one packet.
  * NOT CHECKED: the trailer's checksum (Adler-32, CRC-32, ISIZE). It covers bytes this call never decodes, so a corrupt byte
  * that leaves a packet's structure intact (a changed literal, a changed stored byte) comes back as a wrong byte; packets
- * outside the decoded ones are not looked at at all. zz_decode_device checks the whole stream.
+ * outside the decoded ones are not looked at at all. zz_decode_device checks the whole stream; zz_decode_range_checked_device
+ * checks every packet this read returns bytes from, against a sidecar that it first holds to the trailer.
  * Workspace: as zz_decode_device's batch plus one byte per output byte of a batch (64 MiB). Synchronous. Leaves the
  * context's "last call" and "last decode" state alone, as zz_decode_batch_device does. */
 int zz_decode_range_device(zz_ctx* ctx, const void* d_src, uint64_t src_len, int format, uint32_t packet_size,
@@ -357,7 +358,7 @@ int zz_ctx_last_decode_range_stats(const zz_ctx* ctx, uint64_t* first_packet, ui
  *     is then that code and every d_out_lens[r] = ~0.
  * Reads may overlap each other (each decodes its own copy of the packets); destinations that overlap are the caller's error.
  * NOT CHECKED: the trailer's checksum (Adler-32, CRC-32, ISIZE), for zz_decode_range_device's reason: it covers bytes this call
- * never decodes.
+ * never decodes. zz_decode_ranges_checked_device is the same call with every returned packet checked against a sidecar.
  * How: every read's packets and look-back form a segment on a stage; the segments of many reads go through phase 1 and the
  * rounds together, a wave of at most two batches of packets at a time; a read that still points in front of its segment comes
  * back in the next attempt with four times the look-back, the others are finished. Per attempt the host
@@ -374,6 +375,59 @@ int zz_decode_ranges_device(zz_ctx* ctx, const void* d_src, uint64_t src_len, in
  * needed more than one attempt; the waves, summed over its attempts */
 int zz_ctx_last_decode_ranges_stats(const zz_ctx* ctx, uint64_t* packets, uint32_t* attempts,
                                     uint64_t* retried_ranges, uint32_t* waves);
+
+/* ---- checked range reads: a per-packet checksum sidecar ---------------------------------------------------------------
+ * The SIDECAR of a stream written with packet size P from L decoded bytes: max(1, ceil(L / P)) little-endian uint32 values in
+ * device memory, entry k = the checksum of decoded bytes [k * P, min((k + 1) * P, L)) as zlib computes it -- adler32 (start
+ * value 1) for ZZ_ZLIB, crc32 for ZZ_GZIP and ZZ_DEFLATE; an empty stream has one entry, 1 or 0. Stored beside the stream and
+ * its index (12 bytes per packet together) it lets a range read verify what it returns.
+ *
+ * zz_packet_checksums_device computes the sidecar of ANY device buffer d_data[0, n): the input before it is encoded, or a
+ * decoded copy. *entries is set even when max_entries is too small (ZZ_E_NOSPACE, nothing written: zz_packet_index_device's
+ * convention). ZZ_E_ARG: a null context, entries or d_cks (or null d_data with n > 0), packet_size outside 1..32768, a format
+ * outside 0..2, more than 2^31 - 1 packets. Stateless: it does not depend on the context's last call and leaves the "last call",
+ * "last decode" and range-stats state alone. Synchronous. Workspace: 8 bytes per packet. */
+int zz_packet_checksums_device(zz_ctx* ctx, const void* d_data, uint64_t n, uint32_t packet_size, int format,
+                               uint32_t* d_cks, uint64_t max_entries, uint64_t* entries, void* hip_stream);
+
+/* zz_decode_range_device with every packet it returns bytes from verified. d_cks is the stream's sidecar (entries - 1 values),
+ * total_len its decoded length L (the caller knows it; gzip also stores it). Arguments, clipping, m, cap, look-back growth,
+ * batches, zz_ctx_last_decode_range_stats and "nothing written outside d_dst[0, min(m, cap))" are zz_decode_range_device's.
+ *   ZZ_E_ARG on top, before anything is launched: d_cks null; entries - 1 != max(1, ceil(total_len / packet_size)); more than
+ *     2^31 - 1 packets.
+ *   The sidecar is never trusted. In every call its entries are folded in packet order on the device (the last packet's length
+ *     from total_len) and the fold is held to the stream's own trailer: Adler-32 for zlib; CRC-32 and ISIZE (against total_len mod
+ *     2^32) for gzip. A mismatch, or an entry no packet can have: ZZ_E_DATA, *out_len = ~0, no destination byte written.
+ *     ZZ_DEFLATE HAS NO TRAILER: there nothing vouches for the sidecar but the caller who stored it -- the call then proves that
+ *     the bytes match the caller's sidecar, not that the sidecar matches what was once encoded.
+ *   Every packet [first / P, ...) the range touches is summed whole on the device after it is decoded -- its length is what the
+ *     decoder produced, not what the host expects -- and compared with its entry; the stream's last packet must also hold
+ *     exactly total_len - (packets - 1) * P bytes. Look-back packets are not summed: none of their bytes is returned. Any
+ *     mismatch: ZZ_E_DATA, *out_len = ~0; earlier batches of a long range may already have been copied, so d_dst[0, min(m, cap))
+ *     is unspecified, as after any failed read.
+ *   A packet with an unresolved byte cannot be summed, so a byte that points in front of the decoded packets sends the call
+ *     back for a longer look-back when it lies anywhere in a touched packet, not only inside [first, first + m): the returned
+ *     bytes are the same, the look-back may grow one step earlier than the unchecked call's.
+ * Cost on top of the unchecked call: one pass over the touched packets on the stage and an O(packets) fold of the sidecar; the
+ * host reads one more word per call. Workspace on top: 8 bytes per packet of the stream and 8 per packet of a batch. */
+int zz_decode_range_checked_device(zz_ctx* ctx, const void* d_src, uint64_t src_len, int format, uint32_t packet_size,
+                                   const uint64_t* d_index, uint64_t entries,
+                                   const uint32_t* d_cks, uint64_t total_len,
+                                   uint64_t first, uint64_t nbytes,
+                                   void* d_dst, uint64_t cap, uint64_t* out_len, void* hip_stream);
+
+/* zz_decode_ranges_device with every returned packet verified; d_cks and total_len as zz_decode_range_checked_device takes them,
+ * and its ZZ_E_ARG cases on top of zz_decode_ranges_device's. The sidecar is held to the trailer once per call: on failure
+ * every d_status[r] = ZZ_E_DATA, every d_out_lens[r] = ~0, nothing is written and the call returns ZZ_E_DATA. Per read: the
+ * widened window, and its touched packets summed after the rounds of its wave; a mismatch is charged to that read alone
+ * (ZZ_E_DATA, ~0, its destination not copied) and leaves the others complete. Status precedence, waves, attempts, stats and the
+ * fixed number of words the host reads per attempt are zz_decode_ranges_device's. For ZZ_DEFLATE see above. */
+int zz_decode_ranges_checked_device(zz_ctx* ctx, const void* d_src, uint64_t src_len, int format, uint32_t packet_size,
+                                    const uint64_t* d_index, uint64_t entries,
+                                    const uint32_t* d_cks, uint64_t total_len,
+                                    uint64_t nranges, const uint64_t* d_firsts, const uint64_t* d_nbytes,
+                                    void* const* d_dsts, const uint64_t* d_caps,
+                                    uint64_t* d_out_lens, int32_t* d_status, void* hip_stream);
 
 /* A file of gzip members back to back (RFC 1952 2.2): what `cat a.gz b.gz`, an append-mode gzip writer and bgzip / BAM / tabix
  * (BGZF) write, and what gzip(1), zlib's gzread and Python's gzip.decompress read. d_src[0, src_len) holds one or more members;

@@ -17,7 +17,7 @@ from . import build as _build
 __all__ = [
     "Format", "Config", "ZzFlateError", "ZzFlateEncode", "ZzFlateEncodeToCallback", "adler32x", "combine",
     "crc32", "crc32_combine", "bound", "Context", "lib", "DEFAULT_PACKET", "generate_host", "header", "trailer",
-    "MEMBERS_BLOCK", "members_bound", "members_header", "gzi_bytes",
+    "MEMBERS_BLOCK", "members_bound", "members_header", "gzi_bytes", "packet_checksums_host",
 ]
 
 DEFAULT_PACKET = 32768
@@ -98,6 +98,9 @@ def _load():
         "zz_decode_range_device": (i32, [vp, vp, u64, i32, u32, vp, u64, u64, u64, vp, u64, pu64, vp]),
         "zz_ctx_last_decode_range_stats": (i32, [vp, pu64, pu64, ctypes.POINTER(u32), pu64]),
         "zz_decode_ranges_device": (i32, [vp, vp, u64, i32, u32, vp, u64, u64, vp, vp, vp, vp, vp, vp, vp]),
+        "zz_packet_checksums_device": (i32, [vp, vp, u64, u32, i32, vp, u64, pu64, vp]),
+        "zz_decode_range_checked_device": (i32, [vp, vp, u64, i32, u32, vp, u64, vp, u64, u64, u64, vp, u64, pu64, vp]),
+        "zz_decode_ranges_checked_device": (i32, [vp, vp, u64, i32, u32, vp, u64, vp, u64, u64, vp, vp, vp, vp, vp, vp, vp]),
         "zz_ctx_last_decode_ranges_stats": (i32, [vp, pu64, ctypes.POINTER(u32), pu64, ctypes.POINTER(u32)]),
         "zz_decode_members_device": (i32, [vp, vp, u64, vp, u64, pu64, vp]),
         "zz_ctx_last_decode_members_stats": (i32, [vp, pu64, pu64, ctypes.POINTER(i32)]),
@@ -223,6 +226,16 @@ def trailer(format, cks_total, n):
     buf = ctypes.create_string_buffer(8)
     k = lib.zz_trailer(int(format), cks_total, n, buf)
     return buf.raw[:k]
+
+
+def packet_checksums_host(data, format=Format.Zlib, packet_size=DEFAULT_PACKET):
+    """The packet checksum sidecar of ``data`` by Python's zlib: one value per packet of ``packet_size`` decoded bytes (one for
+    empty data) -- ``zlib.adler32`` for Format.Zlib, ``zlib.crc32`` for Gzip and Deflate. What ``Context.packet_checksums``
+    computes on the device."""
+    import zlib
+    data = bytes(data)
+    f = zlib.adler32 if int(format) == int(Format.Zlib) else zlib.crc32
+    return [f(data[k: k + packet_size]) for k in range(0, max(len(data), 1), packet_size)]
 
 
 def members_bound(n, block_size=MEMBERS_BLOCK, packet_size=DEFAULT_PACKET, eof=True):
@@ -535,6 +548,31 @@ class Context:
         _check(lib.zz_packet_index_device(self._h, idx.data_ptr(), entries.value, ctypes.byref(entries), st))
         return idx
 
+    def packet_checksums(self, data, n, format=Format.Zlib, packet_size=DEFAULT_PACKET, stream=None):
+        """The packet checksum sidecar of ``data[:n]`` (the input of an encode call, or decoded bytes): an int32 tensor on this
+        context's device holding the 32-bit patterns of ``max(1, ceil(n / packet_size))`` checksums, ``zlib.adler32`` of each
+        packet for Format.Zlib and ``zlib.crc32`` otherwise (``packet_checksums_host``). Store it beside the stream and its
+        packet index; ``decode_range_checked`` and ``decode_ranges_checked`` take it as ``checksums``."""
+        import torch
+        entries = ctypes.c_uint64(0)
+        st = self._stream() if stream is None else stream
+        npk = max(1, (n + packet_size - 1) // packet_size) if packet_size > 0 else 1
+        cks = torch.empty(npk, dtype=torch.int32, device=f"cuda:{self.device}")
+        _check(lib.zz_packet_checksums_device(self._h, self._ptr(data) if n else None, n, packet_size, int(format), cks.data_ptr(), npk,
+                                              ctypes.byref(entries), st))
+        return cks
+
+    def _sidecar(self, checksums, total_len):
+        import torch
+        if total_len is None:
+            raise TypeError("checksums need total_len, the stream's decoded length")
+        if (not isinstance(checksums, torch.Tensor) or checksums.dtype != torch.int32 or checksums.dim() != 1
+                or not checksums.is_contiguous()):
+            raise TypeError("checksums must be a contiguous one-dimensional int32 tensor (as packet_checksums() returns)")
+        if checksums.device.type != "cuda" or checksums.device.index != self.device:
+            raise ValueError(f"checksums must live on this context's device (cuda:{self.device}), not {checksums.device}")
+        return checksums.data_ptr(), int(total_len)
+
     def decode(self, src, src_len, dst, cap, format=Format.Zlib, packet_size=DEFAULT_PACKET, index=None, stream=None):
         """Decode the zlib / gzip / raw stream ``src[:src_len]`` into ``dst`` (``cap`` bytes); returns the decoded length.
         ``packet_size`` 1..32768 with ``index`` (an int64 tensor from ``packet_index``): packets decoded in parallel;
@@ -560,7 +598,20 @@ class Context:
         returns how many there are (the range is clipped at the stream's end). ``index`` is the stream's packet index (an int64
         tensor from ``packet_index`` or ``last_decode_index``) and is required; ``packet_size`` is the one the stream was written
         with. Only the packets the range touches and a look-back in front of them are decoded; the trailer's checksum is NOT
-        checked (it covers bytes this call never decodes). Raises ZzFlateError (E_ARG, E_DATA, E_NOSPACE, E_UNSUPPORTED)."""
+        checked (it covers bytes this call never decodes); ``decode_range_checked`` checks what
+        it returns. Raises ZzFlateError (E_ARG, E_DATA, E_NOSPACE, E_UNSUPPORTED)."""
+        return self._decode_range(src, src_len, dst, cap, first, nbytes, format, packet_size, index, stream, None, None)
+
+    def decode_range_checked(self, src, src_len, dst, cap, first, nbytes, checksums, total_len, format=Format.Zlib,
+                             packet_size=DEFAULT_PACKET, index=None, stream=None):
+        """``decode_range`` with what it returns verified: ``checksums`` is the stream's sidecar (``packet_checksums``, one entry
+        per packet), ``total_len`` its decoded length. The sidecar is first held to the stream's trailer, then every packet the
+        range returns bytes from is summed on the device and compared with its entry: E_DATA on any mismatch."""
+        if checksums is None:
+            raise TypeError("decode_range_checked needs the stream's packet checksums (packet_checksums())")
+        return self._decode_range(src, src_len, dst, cap, first, nbytes, format, packet_size, index, stream, checksums, total_len)
+
+    def _decode_range(self, src, src_len, dst, cap, first, nbytes, format, packet_size, index, stream, checksums, total_len):
         import torch
         if index is None:
             raise TypeError("decode_range needs the stream's packet index (packet_index() or last_decode_index())")
@@ -570,6 +621,13 @@ class Context:
             raise ValueError(f"index must live on this context's device (cuda:{self.device}), not {index.device}")
         out = ctypes.c_uint64(0)
         st = self._stream() if stream is None else stream
+        if checksums is not None:
+            cp, tl = self._sidecar(checksums, total_len)
+            if checksums.numel() != index.numel() - 1:
+                raise ValueError(f"{checksums.numel()} checksums for an index of {index.numel() - 1} packets")
+            _check(lib.zz_decode_range_checked_device(self._h, self._ptr(src), src_len, int(format), packet_size, index.data_ptr(),
+                                                      index.numel(), cp, tl, first, nbytes, self._ptr(dst), cap, ctypes.byref(out), st))
+            return out.value
         _check(lib.zz_decode_range_device(self._h, self._ptr(src), src_len, int(format), packet_size, index.data_ptr(),
                                           index.numel(), first, nbytes, self._ptr(dst), cap, ctypes.byref(out), st))
         return out.value
@@ -589,7 +647,19 @@ class Context:
         ``(lens, status)``: ``lens[r]`` the bytes read (clipped at the stream's end) or ``None``, ``status[r]`` 0, E_ARG,
         E_NOSPACE, E_DATA or E_UNSUPPORTED -- a read's own failure does not raise and leaves the others complete; a failure of
         the call (arguments, container header, an index that is not this stream's) raises. The trailer's checksum is NOT
-        checked."""
+        checked; ``decode_ranges_checked`` checks what it returns."""
+        return self._decode_ranges(src, src_len, firsts, nbytes, dsts, caps, format, packet_size, index, stream, None, None)
+
+    def decode_ranges_checked(self, src, src_len, firsts, nbytes, dsts, checksums, total_len, caps=None, format=Format.Zlib,
+                              packet_size=DEFAULT_PACKET, index=None, stream=None):
+        """``decode_ranges`` with what it returns verified; ``checksums`` and ``total_len`` as ``decode_range_checked`` takes
+        them. A sidecar that does not fold to the trailer raises E_DATA (nothing is written); a packet that does not match its
+        entry fails the reads that return bytes from it (status E_DATA) and leaves the others complete."""
+        if checksums is None:
+            raise TypeError("decode_ranges_checked needs the stream's packet checksums (packet_checksums())")
+        return self._decode_ranges(src, src_len, firsts, nbytes, dsts, caps, format, packet_size, index, stream, checksums, total_len)
+
+    def _decode_ranges(self, src, src_len, firsts, nbytes, dsts, caps, format, packet_size, index, stream, checksums, total_len):
         import torch
         if index is None:
             raise TypeError("decode_ranges needs the stream's packet index (packet_index() or last_decode_index())")
@@ -602,6 +672,11 @@ class Context:
             raise ValueError(f"{k} starts but {len(nbytes)} lengths and {len(dsts)} destinations")
         if caps is not None and len(caps) != k:
             raise ValueError(f"{len(caps)} capacities for {k} reads")
+        side = None
+        if checksums is not None:
+            side = self._sidecar(checksums, total_len)
+            if checksums.numel() != index.numel() - 1:
+                raise ValueError(f"{checksums.numel()} checksums for an index of {index.numel() - 1} packets")
         if k == 0:
             return [], []
         d = [self._item(t) for t in dsts]
@@ -617,9 +692,14 @@ class Context:
         out = torch.empty(k, dtype=torch.int64, device=dev)
         status = torch.empty(k, dtype=torch.int32, device=dev)
         st = self._stream() if stream is None else stream
-        rc = lib.zz_decode_ranges_device(self._h, self._ptr(src), src_len, int(format), packet_size, index.data_ptr(), index.numel(),
-                                         k, table[0].data_ptr(), table[1].data_ptr(), table[2].data_ptr(), table[3].data_ptr(),
-                                         out.data_ptr(), status.data_ptr(), st)
+        if side is not None:
+            rc = lib.zz_decode_ranges_checked_device(self._h, self._ptr(src), src_len, int(format), packet_size, index.data_ptr(),
+                                                     index.numel(), side[0], side[1], k, table[0].data_ptr(), table[1].data_ptr(),
+                                                     table[2].data_ptr(), table[3].data_ptr(), out.data_ptr(), status.data_ptr(), st)
+        else:
+            rc = lib.zz_decode_ranges_device(self._h, self._ptr(src), src_len, int(format), packet_size, index.data_ptr(), index.numel(),
+                                             k, table[0].data_ptr(), table[1].data_ptr(), table[2].data_ptr(), table[3].data_ptr(),
+                                             out.data_ptr(), status.data_ptr(), st)
         if rc != 0 and not lib.zz_last_error().startswith(b"reads: "):
             _check(rc)                                 # the call itself failed (the library words a read's own failure "reads: ...")
         status = status.cpu().tolist()

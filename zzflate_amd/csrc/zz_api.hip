@@ -31,6 +31,7 @@
 #include "zz_verify.h"
 #include "zz_inflate.h"
 #include "zz_inflate_ranges.h"
+#include "zz_inflate_check.h"
 #include "zz_inflate_members.h"
 #include "zz_inflate_members_ranges.h"
 #include "zz_batch.h"
@@ -191,6 +192,9 @@ struct zz_ctx {
         zz_buf<zi_read> rng_reads; zz_buf<zi_read_desc> rng_desc;
         zz_buf<zz_rng_totals> rng_tot; zz_pin<zz_rng_totals> rng_host;
         struct { uint64_t packets = 0, retried = 0; uint32_t attempts = 0, waves = 0; } ranges;
+        // the checked reads and zz_packet_checksums_device (zz_inflate_check.h): per packet of the stream a partial (the sidecar unpacked,
+        // or the producer's sums), per stage packet its sum, the sidecar's fold, the verdict words
+        zz_buf<zz_cks> side, scks; zz_buf<zz_cks_total> side_total; zz_buf<uint32_t> verdict;
         std::vector<uint64_t> last_index;                     // the index discovery recovered (zz_ctx_last_decode_index_device)
         // zz_decode_members_device: per stretch of the mark pass (count, base), per candidate (offset, length; then the member
         // list), per member k_inflate_items' descriptors, what the host reads, the serial path's result
@@ -1249,9 +1253,47 @@ extern "C" int zz_decode_device(zz_ctx* c, const void* d_src_v, uint64_t src_len
 // but the last go to d_dst at once (such a batch holds full packets only), the last batch's after the host has seen the
 // attempt's counters: *ext = external bytes inside the window (then nothing more is copied: the caller tries again),
 // *m = the bytes the range holds.
+// A checked read's sidecar (zz_inflate_check.h); cks == nullptr: the unchecked call.
+struct dec_sidecar { const uint32_t* cks; uint64_t L; int kind; };
+
+// what the checked calls refuse before anything is launched, on top of the unchecked calls' own
+static int dec_sidecar_args(const uint32_t* d_cks, uint64_t total_len, uint64_t entries, uint32_t P)
+{
+    if (!d_cks) { set_err("null argument"); return ZZ_E_ARG; }
+    if (entries - 1 > 0x7fffffffull) { set_err("at most 2^31 - 1 packets"); return ZZ_E_ARG; }
+    if (entries - 1 != zi_sidecar_entries(total_len, P)) { set_err("the index's packets are not total_len's: entries - 1 != max(1, ceil(total_len / packet_size))"); return ZZ_E_ARG; }
+    return ZZ_OK;
+}
+// The sidecar against the stream's trailer, enqueued: unpack, fold, verdict. The caller reads D.verdict[0] (1: it holds) with its
+// next wait. A raw stream has no trailer: nothing is launched, and nothing is read.
+static int dec_sidecar_fold(zz_ctx* c, const dec_sidecar& sc, uint64_t npk, uint32_t P, int format, const uint8_t* trailer, hipStream_t st)
+{
+    auto& D = c->dec;
+    if (format == ZZ_DEFLATE) return ZZ_OK;
+    if (int rc = D.side.grow(npk)) return rc;
+    if (int rc = D.side_total.grow(1)) return rc;
+    if (int rc = D.verdict.grow(2)) return rc;
+    HIPCHK(hipMemsetAsync(D.verdict, 0, 8, st));
+    hipLaunchKernelGGL(k_sidecar_unpack, dim3((uint32_t)((npk + 255) / 256)), dim3(256), 0, st, sc.cks, (uint32_t)npk, P, sc.L, sc.kind, D.side.p, D.verdict.p);
+    hipLaunchKernelGGL(k_cks_reduce, dim3(1), dim3(ZZ_RED_THREADS), 0, st, D.side.p, (uint32_t)npk, P, sc.L, sc.kind, D.side_total.p);
+    hipLaunchKernelGGL(k_sidecar_verdict, dim3(1), dim3(1), 0, st, trailer, format, D.side_total.p, sc.L, D.verdict.p);
+    HIPCHK(hipGetLastError());
+    return ZZ_OK;
+}
+// Stage packets [0, n) at `stage` (phase 1's words at `stat`) summed into D.scks: the MAP forms of zz_checksum.h's bodies.
+static void dec_stage_sums(zz_ctx* c, const dec_sidecar& sc, const uint8_t* stage, const uint32_t* stat, const zi_read_desc* desc, uint32_t n,
+                           uint32_t P, hipStream_t st)
+{
+    zz_packet_params pp = {};
+    pp.src = stage; pp.packet_size = P; pp.npk = n; pp.cks_kind = sc.kind; pp.cks = c->dec.scks;
+    zz_stage_map M{ stat, desc, n };
+    if (sc.kind == ZZ_CKS_CRC) hipLaunchKernelGGL(k_crc32_stage, dim3(n < 2048 ? n : 2048), dim3(ZZ_CRC_THREADS), 0, st, pp, M);
+    else hipLaunchKernelGGL(k_adler_stage, dim3(n < 16384 ? n : 16384), dim3(ZZ_WAVE), 0, st, pp, M);
+}
+
 static int dec_range_attempt(zz_ctx* c, const uint8_t* s, uint64_t sn, const uint64_t* d_index, uint64_t npk, uint32_t P,
                              uint64_t kb, uint64_t k1, uint64_t first, uint64_t nbytes, uint8_t* dst, uint64_t cap, hipStream_t st,
-                             uint64_t* ext, uint64_t* pending, uint64_t* m)
+                             const dec_sidecar& sc, uint64_t* ext, uint64_t* pending, uint64_t* m, uint64_t* bad)
 {
     auto& D = c->dec;
     const uint32_t words = ((P + 31) / 32 + 3) & ~3u;
@@ -1265,11 +1307,15 @@ static int dec_range_attempt(zz_ctx* c, const uint8_t* s, uint64_t sn, const uin
     if (int rc = D.prem.grow(B)) return rc;
     if (int rc = D.ends.grow(B)) return rc;
     if (int rc = D.stat.grow(B)) return rc;
+    if (sc.cks) if (int rc = D.scks.grow(B)) return rc;
     HIPCHK(hipMemsetAsync(D.tot, 0, 64 * sizeof(unsigned long long), st));
     HIPCHK(hipMemsetAsync(D.xcarry, 0xFF, ZI_BIAS / 8, st));   // the first batch: whatever lies below it is external
     const uint32_t rounds = dec_ceil_log2(B) + 2;
     const size_t lds = (size_t)words * 4 + ZZ_INF_IBUF + ((P + 15) & ~15u);
+    const uint64_t k0 = first / P;
     const uint64_t wend = nbytes < k1 * P - first ? first + nbytes : k1 * P;       // the window's end, as far as packets go
+    uint64_t xlo = 0, xhi = 0;                                  // where an external byte sends the call back: the window, or its packets whole
+    zi_checked_window(sc.cks != nullptr, first, nbytes, P, k0, k1, &xlo, &xhi);
     for (uint64_t kf = kb; kf < k1; kf += B) {
         const uint32_t nb = (uint32_t)(k1 - kf < B ? k1 - kf : B);
         const uint64_t base = kf * P;
@@ -1280,8 +1326,14 @@ static int dec_range_attempt(zz_ctx* c, const uint8_t* s, uint64_t sn, const uin
         Q.ebase = kf;
         hipLaunchKernelGGL(k_inflate_packets_range, dim3(nb), dim3(ZZ_INF_THREADS), lds, st, Q);
         zz_res_params R{ D.stage, ZI_BIAS, P, nb, words, D.st, D.pend, D.pcnt, D.prem, D.tot };
-        zz_res_range X{ D.xcarry, (int64_t)first - (int64_t)base, (int64_t)wend - (int64_t)base };
+        zz_res_range X{ D.xcarry, (int64_t)xlo - (int64_t)base, (int64_t)xhi - (int64_t)base };
         for (uint32_t r = 1; r <= rounds; ++r) hipLaunchKernelGGL(k_inflate_resolve_range, dim3(nb), dim3(ZZ_INF_RES_THREADS), 0, st, R, X, r);
+        if (sc.cks && kf + nb > k0) {                               // the batch's touched packets: summed, held to the sidecar (tot[60])
+            const uint32_t g = (uint32_t)(k0 > kf ? k0 - kf : 0), n = nb - g;
+            dec_stage_sums(c, sc, D.stage + ZI_BIAS + (uint64_t)g * P, D.stat + g, nullptr, n, P, st);
+            zz_chk_params C{ sc.cks, npk, sc.L, P, sc.kind, D.scks.p, D.stat + g };
+            hipLaunchKernelGGL(k_stage_check_range, dim3((n + 255) / 256), dim3(256), 0, st, C, kf + g, n, D.tot + 60);
+        }
         // this batch's share of the window: stream bytes [lo, hi)
         const uint64_t lo = first > base ? first : base;
         uint64_t hi = base + (uint64_t)nb * P < wend ? base + (uint64_t)nb * P : wend;
@@ -1295,11 +1347,11 @@ static int dec_range_attempt(zz_ctx* c, const uint8_t* s, uint64_t sn, const uin
             HIPCHK(hipStreamSynchronize(st));
             if (tot[63] != 0) { set_err("not a valid stream of the requested format: " + std::to_string(tot[63]) + " of the range's packets do not decode as the index says"); return ZZ_E_DATA; }
             if (tot[1 + rounds] != 0) { set_err("pending bytes left unresolved"); return ZZ_E_DATA; }   // (cannot happen: the rounds suffice for any chain)
-            *ext = tot[61]; *pending = tot[0];
+            *ext = tot[61]; *pending = tot[0]; *bad = tot[60];
             uint64_t have = nbytes;                                 // bytes of the stream from `first` on, if its end is in sight
             if (k1 == npk) { const uint64_t L = (npk - 1) * (uint64_t)P + (stat >> 3); have = L > first ? L - first : 0; }
             *m = nbytes < have ? nbytes : have;
-            if (*ext != 0) return ZZ_OK;
+            if (*ext != 0 || *bad != 0) return ZZ_OK;             // nothing more is copied: the caller tries again, or refuses
             if (hi > first + *m) hi = first + *m;
         }
         if (hi > first && hi - first > cap) hi = first + cap;                     // nothing past cap, whatever the call's result will be
@@ -1318,9 +1370,10 @@ static int dec_range_attempt(zz_ctx* c, const uint8_t* s, uint64_t sn, const uin
     return ZZ_OK;
 }
 
-extern "C" int zz_decode_range_device(zz_ctx* c, const void* d_src_v, uint64_t src_len, int format, uint32_t P,
-                                      const uint64_t* d_index, uint64_t entries, uint64_t first, uint64_t nbytes,
-                                      void* d_dst_v, uint64_t cap, uint64_t* out_len, void* hip_stream)
+// zz_decode_range_device (checked == false: d_cks and total_len are not looked at) and zz_decode_range_checked_device: one body
+static int dec_range(zz_ctx* c, const void* d_src_v, uint64_t src_len, int format, uint32_t P,
+                     const uint64_t* d_index, uint64_t entries, bool checked, const uint32_t* d_cks, uint64_t total_len,
+                     uint64_t first, uint64_t nbytes, void* d_dst_v, uint64_t cap, uint64_t* out_len, void* hip_stream)
 {
     if (!c || !d_src_v || !d_index || !out_len) { set_err("null argument"); return ZZ_E_ARG; }
     *out_len = 0;
@@ -1331,6 +1384,8 @@ extern "C" int zz_decode_range_device(zz_ctx* c, const void* d_src_v, uint64_t s
     if (first / P >= npk) { set_err("the range starts behind the index's last packet"); return ZZ_E_ARG; }
     if (first + nbytes < first) { set_err("first + nbytes overflows"); return ZZ_E_ARG; }
     if (!d_dst_v && cap) { set_err("null buffer"); return ZZ_E_ARG; }
+    if (checked) if (int rc = dec_sidecar_args(d_cks, total_len, entries, P)) return rc;
+    const dec_sidecar sc{ checked ? d_cks : nullptr, total_len, zi_sidecar_kind(format) };
     if (nbytes == 0) return ZZ_OK;                                  // nothing to do: the context is not looked at
     if (call_pending(c)) return ZZ_E_ARG;
     const uint8_t* d_src = (const uint8_t*)d_src_v;
@@ -1345,22 +1400,38 @@ extern "C" int zz_decode_range_device(zz_ctx* c, const void* d_src_v, uint64_t s
     const uint8_t* s = d_src + hl;
     const uint64_t sn = src_len - hl - (uint64_t)trailer_len(format);
     uint64_t ends[2];
+    uint32_t holds = 1;                                             // the sidecar folds to the trailer (read with the index's ends)
+    if (sc.cks) if (int rc = dec_sidecar_fold(c, sc, npk, P, format, s + sn, st)) return rc;
     HIPCHK(hipMemcpyAsync(&ends[0], d_index, 8, hipMemcpyDeviceToHost, st));
     HIPCHK(hipMemcpyAsync(&ends[1], d_index + npk, 8, hipMemcpyDeviceToHost, st));
+    if (sc.cks && format != ZZ_DEFLATE) HIPCHK(hipMemcpyAsync(&holds, D.verdict.p, 4, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     if (ends[0] != 0 || ends[1] != sn) { set_err("the index does not describe this stream: its ends are not the DEFLATE bytes' ends"); return ZZ_E_DATA; }
+    if (holds != 1) {
+        *out_len = ~0ull;
+        set_err("the packet checksums do not describe this stream: they do not fold to its trailer (checksum or length)");
+        return ZZ_E_DATA;
+    }
     const uint64_t k0 = first / P;
     const uint64_t lastk = (first + nbytes - 1) / P;
     const uint64_t k1 = lastk + 1 < npk ? lastk + 1 : npk;
     uint64_t h = zi_range_first_lookback(P, k0);
     for (uint32_t tries = 1;; ++tries) {
         const uint64_t kb = k0 - h;
-        uint64_t ext = 0, pending = 0, m = 0;
-        if (int rc = dec_range_attempt(c, s, sn, d_index, npk, P, kb, k1, first, nbytes, d_dst, cap, st, &ext, &pending, &m)) return rc;
+        uint64_t ext = 0, pending = 0, m = 0, bad = 0;
+        if (int rc = dec_range_attempt(c, s, sn, d_index, npk, P, kb, k1, first, nbytes, d_dst, cap, st, sc, &ext, &pending, &m, &bad)) {
+            if (checked && rc == ZZ_E_DATA) *out_len = ~0ull;
+            return rc;
+        }
         if (ext != 0) {
             if (kb == 0) { set_err("not a valid stream of the requested format: a reference in front of the stream"); return ZZ_E_DATA; }   // (phase 1 refuses these)
             h = zi_range_next_lookback(h, k0);
             continue;
+        }
+        if (bad != 0) {
+            *out_len = ~0ull;
+            set_err("checksum mismatch: " + std::to_string(bad) + " of the range's packets do not decode to the bytes their checksums (or total_len) describe");
+            return ZZ_E_DATA;
         }
         if (m > cap) {
             *out_len = ~0ull;
@@ -1371,6 +1442,19 @@ extern "C" int zz_decode_range_device(zz_ctx* c, const void* d_src_v, uint64_t s
         *out_len = m;
         return ZZ_OK;
     }
+}
+
+extern "C" int zz_decode_range_device(zz_ctx* c, const void* d_src_v, uint64_t src_len, int format, uint32_t P,
+                                      const uint64_t* d_index, uint64_t entries, uint64_t first, uint64_t nbytes,
+                                      void* d_dst_v, uint64_t cap, uint64_t* out_len, void* hip_stream)
+{
+    return dec_range(c, d_src_v, src_len, format, P, d_index, entries, false, nullptr, 0, first, nbytes, d_dst_v, cap, out_len, hip_stream);
+}
+extern "C" int zz_decode_range_checked_device(zz_ctx* c, const void* d_src_v, uint64_t src_len, int format, uint32_t P,
+                                              const uint64_t* d_index, uint64_t entries, const uint32_t* d_cks, uint64_t total_len,
+                                              uint64_t first, uint64_t nbytes, void* d_dst_v, uint64_t cap, uint64_t* out_len, void* hip_stream)
+{
+    return dec_range(c, d_src_v, src_len, format, P, d_index, entries, true, d_cks, total_len, first, nbytes, d_dst_v, cap, out_len, hip_stream);
 }
 
 extern "C" int zz_ctx_last_decode_range_stats(const zz_ctx* c, uint64_t* first_packet, uint64_t* packets, uint32_t* attempts,
@@ -1388,17 +1472,21 @@ extern "C" int zz_ctx_last_decode_range_stats(const zz_ctx* c, uint64_t* first_p
 // A read's own failure is worded "reads: ..." in zz_last_error (the Python layer tells it from a failure of the call by that).
 // Per attempt: the plan, one wait for its totals and wave table, then per wave descriptors, phase 1, the rounds, the verdict and
 // the copy, nothing of which the host waits for; the next attempt's plan finds what is left.
-extern "C" int zz_decode_ranges_device(zz_ctx* c, const void* d_src_v, uint64_t src_len, int format, uint32_t P,
-                                       const uint64_t* d_index, uint64_t entries,
-                                       uint64_t nranges, const uint64_t* d_firsts, const uint64_t* d_nbytes,
-                                       void* const* d_dsts, const uint64_t* d_caps,
-                                       uint64_t* d_out_lens, int32_t* d_status, void* hip_stream)
+// zz_decode_ranges_device (checked == false: d_cks and total_len are not looked at) and zz_decode_ranges_checked_device: one body
+static_assert(ZI_CKS_ADLER == ZZ_CKS_ADLER && ZI_CKS_CRC == ZZ_CKS_CRC, "the sidecar's kinds are the checksum kernels'");
+static int dec_ranges(zz_ctx* c, const void* d_src_v, uint64_t src_len, int format, uint32_t P,
+                      const uint64_t* d_index, uint64_t entries, bool checked, const uint32_t* d_cks, uint64_t total_len,
+                      uint64_t nranges, const uint64_t* d_firsts, const uint64_t* d_nbytes,
+                      void* const* d_dsts, const uint64_t* d_caps,
+                      uint64_t* d_out_lens, int32_t* d_status, void* hip_stream)
 {
     if (!c || !d_src_v || !d_index || !d_firsts || !d_nbytes || !d_dsts || !d_caps || !d_out_lens) { set_err("null argument"); return ZZ_E_ARG; }
     if (P < 1 || P > ZZ_MAX_PACKET_SIZE) { set_err("packet size must be 1..32768"); return ZZ_E_ARG; }
     if (format < ZZ_ZLIB || format > ZZ_DEFLATE) { set_err("format must be ZZ_ZLIB, ZZ_GZIP or ZZ_DEFLATE"); return ZZ_E_ARG; }
     if (entries < 2) { set_err("the index needs at least two entries (packets + 1)"); return ZZ_E_ARG; }
     if (nranges > 0x7fffffffull) { set_err("at most 2^31 - 1 reads per call"); return ZZ_E_ARG; }
+    if (checked) if (int rc = dec_sidecar_args(d_cks, total_len, entries, P)) return rc;
+    const dec_sidecar sc{ checked ? d_cks : nullptr, total_len, zi_sidecar_kind(format) };
     if (nranges == 0) return ZZ_OK;                                 // nothing to do: the context is not looked at
     if (call_pending(c)) return ZZ_E_ARG;
     const uint64_t npk = entries - 1;
@@ -1423,11 +1511,18 @@ extern "C" int zz_decode_ranges_device(zz_ctx* c, const void* d_src_v, uint64_t 
     const uint8_t* s = d_src + hl;
     const uint64_t sn = src_len - hl - (uint64_t)trailer_len(format);
     uint64_t ends[2];
+    uint32_t holds = 1;                                             // the sidecar folds to the trailer (read with the index's ends)
+    if (sc.cks) if (int rc = dec_sidecar_fold(c, sc, npk, P, format, s + sn, st)) return rc;
     HIPCHK(hipMemcpyAsync(&ends[0], d_index, 8, hipMemcpyDeviceToHost, st));
     HIPCHK(hipMemcpyAsync(&ends[1], d_index + npk, 8, hipMemcpyDeviceToHost, st));
+    if (sc.cks && format != ZZ_DEFLATE) HIPCHK(hipMemcpyAsync(&holds, D.verdict.p, 4, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     if (ends[0] != 0 || ends[1] != sn) {
         set_err("the index does not describe this stream: its ends are not the DEFLATE bytes' ends");
+        return fail_all(ZZ_E_DATA);
+    }
+    if (holds != 1) {
+        set_err("the packet checksums do not describe this stream: they do not fold to its trailer (checksum or length)");
         return fail_all(ZZ_E_DATA);
     }
     if (int rc = D.tot.grow(64)) return rc;
@@ -1437,7 +1532,8 @@ extern "C" int zz_decode_ranges_device(zz_ctx* c, const void* d_src_v, uint64_t 
     const uint32_t words = ((P + 31) / 32 + 3) & ~3u;
     uint64_t B = ZZ_INF_BATCH_BYTES / P;
     if (B > ZZ_INF_BATCH_PACKETS) B = ZZ_INF_BATCH_PACKETS;
-    zz_rng_params Q{ d_firsts, d_nbytes, (uint8_t* const*)d_dsts, d_caps, d_out_lens, d_status, nranges, npk, P, B, B, D.rng_reads, D.rng_tot };
+    zz_rng_params Q{ d_firsts, d_nbytes, (uint8_t* const*)d_dsts, d_caps, d_out_lens, d_status, nranges, npk, P, B, B, D.rng_reads, D.rng_tot,
+                     sc.cks, sc.L };
     const size_t lds = (size_t)words * 4 + ZZ_INF_IBUF + ((P + 15) & ~15u);
     const zz_rng_totals& T = *D.rng_host.p;
     for (uint32_t tries = 1;; ++tries) {
@@ -1466,6 +1562,7 @@ extern "C" int zz_decode_ranges_device(zz_ctx* c, const void* d_src_v, uint64_t 
         if (int rc = D.ends.grow(big)) return rc;
         if (int rc = D.stat.grow(big)) return rc;
         if (int rc = D.rng_desc.grow(big)) return rc;
+        if (sc.cks) if (int rc = D.scks.grow(big)) return rc;
         for (uint64_t w = 0; w < T.nwaves; ++w) {
             if (T.wave_first[w] == ~0ull) continue;                 // (a segment longer than a wave's capacity went over it)
             uint64_t nx = w + 1;
@@ -1484,16 +1581,66 @@ extern "C" int zz_decode_ranges_device(zz_ctx* c, const void* d_src_v, uint64_t 
             hipLaunchKernelGGL(k_inflate_packets_ranges, dim3(nb), dim3(ZZ_INF_THREADS), lds, st, I, X);
             zz_res_params R{ D.stage, 0, P, nb, words, D.st, D.pend, D.pcnt, D.prem, D.tot };
             for (uint32_t r = 1; r <= rounds; ++r) hipLaunchKernelGGL(k_inflate_resolve_ranges, dim3(nb), dim3(ZZ_INF_RES_THREADS), 0, st, R, X, r);
+            if (sc.cks) {                                           // the wave's touched packets: summed, a mismatch charged to the read
+                dec_stage_sums(c, sc, D.stage, D.stat, D.rng_desc.p, nb, P, st);
+                zz_chk_params C{ sc.cks, npk, sc.L, P, sc.kind, D.scks.p, D.stat.p };
+                hipLaunchKernelGGL(k_stage_check_ranges, dim3((nb + 255) / 256), dim3(256), 0, st, C, D.rng_desc.p, nb, D.rng_reads.p);
+            }
             hipLaunchKernelGGL(k_ranges_verdict, dim3((uint32_t)((rhi - rlo + 255) / 256)), dim3(256), 0, st, Q, g0, rlo, rhi, D.stat.p);
             hipLaunchKernelGGL(k_ranges_copy, dim3(nb), dim3(256), 0, st, Q, D.rng_desc.p, D.stage.p);
             HIPCHK(hipGetLastError());
         }
     }
     D.ranges.retried = T.retried;
-    if (T.n_data) { set_err("reads: " + std::to_string(T.n_data) + " met a packet that does not decode as the index says"); return ZZ_E_DATA; }
+    if (T.n_data) {
+        set_err("reads: " + std::to_string(T.n_data) + " met a packet that does not decode as the index says" + (checked ? " or as its checksum says" : ""));
+        return ZZ_E_DATA;
+    }
     if (T.n_unsupported) { set_err("reads: " + std::to_string(T.n_unsupported) + " need more than one batch of packets: use zz_decode_range_device"); return ZZ_E_UNSUPPORTED; }
     if (T.n_arg) { set_err("reads: " + std::to_string(T.n_arg) + " start behind the index's last packet or overflow"); return ZZ_E_ARG; }
     if (T.n_nospace) { set_err("reads: " + std::to_string(T.n_nospace) + " do not fit their destinations"); return ZZ_E_NOSPACE; }
+    return ZZ_OK;
+}
+
+extern "C" int zz_decode_ranges_device(zz_ctx* c, const void* d_src_v, uint64_t src_len, int format, uint32_t P,
+                                       const uint64_t* d_index, uint64_t entries,
+                                       uint64_t nranges, const uint64_t* d_firsts, const uint64_t* d_nbytes,
+                                       void* const* d_dsts, const uint64_t* d_caps,
+                                       uint64_t* d_out_lens, int32_t* d_status, void* hip_stream)
+{
+    return dec_ranges(c, d_src_v, src_len, format, P, d_index, entries, false, nullptr, 0, nranges, d_firsts, d_nbytes, d_dsts, d_caps,
+                      d_out_lens, d_status, hip_stream);
+}
+extern "C" int zz_decode_ranges_checked_device(zz_ctx* c, const void* d_src_v, uint64_t src_len, int format, uint32_t P,
+                                               const uint64_t* d_index, uint64_t entries, const uint32_t* d_cks, uint64_t total_len,
+                                               uint64_t nranges, const uint64_t* d_firsts, const uint64_t* d_nbytes,
+                                               void* const* d_dsts, const uint64_t* d_caps,
+                                               uint64_t* d_out_lens, int32_t* d_status, void* hip_stream)
+{
+    return dec_ranges(c, d_src_v, src_len, format, P, d_index, entries, true, d_cks, total_len, nranges, d_firsts, d_nbytes, d_dsts, d_caps,
+                      d_out_lens, d_status, hip_stream);
+}
+
+// The sidecar of d_data[0, n): zz_checksum.h's per-packet partials, then their public values (zz_inflate_check.h). Stateless.
+extern "C" int zz_packet_checksums_device(zz_ctx* c, const void* d_data, uint64_t n, uint32_t P, int format,
+                                          uint32_t* d_cks, uint64_t max_entries, uint64_t* entries, void* hip_stream)
+{
+    if (!c || !entries || !d_cks || (!d_data && n)) { set_err("null argument"); return ZZ_E_ARG; }
+    if (P < 1 || P > ZZ_MAX_PACKET_SIZE) { set_err("packet size must be 1..32768"); return ZZ_E_ARG; }
+    if (format < ZZ_ZLIB || format > ZZ_DEFLATE) { set_err("format must be ZZ_ZLIB, ZZ_GZIP or ZZ_DEFLATE"); return ZZ_E_ARG; }
+    const uint64_t npk = zi_sidecar_entries(n, P);
+    if (npk > 0x7fffffffull) { set_err("at most 2^31 - 1 packets"); return ZZ_E_ARG; }
+    *entries = npk;
+    if (max_entries < npk) { set_err("checksum buffer too small"); return ZZ_E_NOSPACE; }
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t st = (hipStream_t)hip_stream;
+    if (int rc = c->dec.side.grow(npk)) return rc;
+    zz_packet_params pp = {};
+    pp.src = (const uint8_t*)d_data; pp.n = n; pp.packet_size = P; pp.npk = (uint32_t)npk; pp.cks_kind = zi_sidecar_kind(format); pp.cks = c->dec.side;
+    launch_cks_partials(pp, 16384, st);
+    hipLaunchKernelGGL(k_cks_publish, dim3((uint32_t)((npk + 255) / 256)), dim3(256), 0, st, c->dec.side.p, (uint32_t)npk, P, n, pp.cks_kind, d_cks);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(st));
     return ZZ_OK;
 }
 

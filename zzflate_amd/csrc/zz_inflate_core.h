@@ -482,16 +482,24 @@ ZZ_HD inline uint64_t zi_ranges_plan(zi_read& R, uint64_t first, uint64_t nbytes
     return l;
 }
 ZZ_HD inline uint64_t zi_ranges_wave(uint64_t base, uint64_t W) { return base / W; }
-// the descriptor of stage packet j (0-based) of read `r`'s segment, whose first stage packet is `seg0` of the wave
-ZZ_HD inline zi_read_desc zi_ranges_desc(const zi_read& R, uint32_t r, uint64_t j, uint32_t seg0, uint64_t first, uint64_t nbytes, uint32_t P)
+// bytes [*lo, *hi) of stream packet k lie inside the window [first, first + nbytes) (*lo == *hi: none)
+ZZ_HD inline void zi_ranges_cut(uint64_t k, uint64_t first, uint64_t nbytes, uint32_t P, uint32_t* lo, uint32_t* hi)
+{
+    const uint64_t a = k * P, end = first + nbytes;              // (no overflow: the plan refused it)
+    *lo = first > a ? (first - a < P ? (uint32_t)(first - a) : P) : 0u;
+    *hi = end > a ? (end - a < P ? (uint32_t)(end - a) : P) : 0u;
+    if (*hi < *lo) *hi = *lo;
+}
+// the descriptor of stage packet j (0-based) of read `r`'s segment, whose first stage packet is `seg0` of the wave. `whole` (a
+// checked read): a packet the window touches counts whole, [0, P) -- the widened window of zi_checked_window.
+ZZ_HD inline zi_read_desc zi_ranges_desc(const zi_read& R, uint32_t r, uint64_t j, uint32_t seg0, uint64_t first, uint64_t nbytes, uint32_t P,
+                                         bool whole = false)
 {
     zi_read_desc d;
     d.k = first / P - R.h + j;
     d.read = r; d.seg0 = seg0;
-    const uint64_t a = d.k * P, end = first + nbytes;            // (no overflow: the plan refused it)
-    d.lo = first > a ? (first - a < P ? (uint32_t)(first - a) : P) : 0u;
-    d.hi = end > a ? (end - a < P ? (uint32_t)(end - a) : P) : 0u;
-    if (d.hi < d.lo) d.hi = d.lo;
+    zi_ranges_cut(d.k, first, nbytes, P, &d.lo, &d.hi);
+    if (whole && d.hi > d.lo) { d.lo = 0; d.hi = P; }
     return d;
 }
 // The verdict on a read after its segment's phase 1 and rounds. `last_out`: bytes the segment's last packet produced (read only
@@ -602,6 +610,74 @@ ZZ_HD inline uint32_t adler_combine(uint32_t first, uint32_t second, uint64_t le
     uint64_t a = (uint64_t)(first & 0xFFFF) + (second & 0xFFFF);
     uint64_t b = (uint64_t)(first >> 16) + (second >> 16) + (len2 % ZZ_ADLER_MOD) * (first & 0xFFFF);
     return (uint32_t)(((b % ZZ_ADLER_MOD) << 16) | (a % ZZ_ADLER_MOD));
+}
+
+// ---- checked range reads: the packet checksum sidecar (zz_inflate_check.h; tests/cxx/inflate_checked_harness.cpp) ----------
+// A sidecar holds one PUBLIC value per packet: zlib's adler32 (start value 1) of the packet's decoded bytes for a zlib stream,
+// zlib's crc32 for gzip and raw streams. Inside, a packet's Adler-32 is the start-0 partial (a, b) that folds with adler_combine;
+// a CRC-32 partial IS the public value. The sidecar is never trusted: folded in packet order it must give the stream's trailer
+// (zi_sidecar_*), and only then is a touched packet's sum on the stage compared with its entry (zi_checked_packet_bad).
+enum { ZI_CKS_ADLER = 1, ZI_CKS_CRC = 2 };
+ZZ_HD inline int zi_sidecar_kind(int format) { return format == 0 ? ZI_CKS_ADLER : ZI_CKS_CRC; }
+// entries of the sidecar of L decoded bytes in packets of P: an empty stream has one (empty) packet
+ZZ_HD inline uint64_t zi_sidecar_entries(uint64_t L, uint32_t P)
+{
+    const uint64_t n = L / P + (L % P ? 1 : 0);
+    return n ? n : 1;
+}
+// decoded bytes of packet k of npk, by the caller's total length (0 when the total does not reach the packet)
+ZZ_HD inline uint32_t zi_sidecar_len(uint64_t k, uint64_t L, uint32_t P)
+{
+    const uint64_t off = k * (uint64_t)P;
+    if (off >= L) return 0;
+    return L - off < P ? (uint32_t)(L - off) : P;
+}
+// partial -> public value
+ZZ_HD inline uint32_t zi_cks_public(int kind, uint32_t a, uint32_t b, uint32_t len)
+{
+    if (kind != ZI_CKS_ADLER) return a;
+    return (((b + len % ZZ_ADLER_MOD) % ZZ_ADLER_MOD) << 16) | ((a + 1u) % ZZ_ADLER_MOD);
+}
+// public value -> partial; false: no packet of `len` bytes has this value (a half at or above 65521, or an empty packet with
+// anything but the empty value)
+ZZ_HD inline bool zi_cks_partial(int kind, uint32_t v, uint32_t len, uint32_t* a, uint32_t* b)
+{
+    if (kind != ZI_CKS_ADLER) { *a = v; *b = 0; return len != 0 || v == 0; }
+    const uint32_t A = v & 0xFFFFu, B = v >> 16;
+    *a = (A + ZZ_ADLER_MOD - 1u) % ZZ_ADLER_MOD;
+    *b = (B + ZZ_ADLER_MOD - len % ZZ_ADLER_MOD) % ZZ_ADLER_MOD;
+    if (A >= ZZ_ADLER_MOD || B >= ZZ_ADLER_MOD) return false;
+    return len != 0 || v == 1u;
+}
+// The window inside which an external byte sends a read back for a longer look-back, as stream positions [*lo, *hi). Unchecked:
+// the bytes asked for, as far as the packets [k0, k1) go. Checked: those packets whole -- a packet with an unresolved byte cannot
+// be summed, wherever in the packet the byte lies.
+ZZ_HD inline void zi_checked_window(bool checked, uint64_t first, uint64_t nbytes, uint32_t P, uint64_t k0, uint64_t k1, uint64_t* lo, uint64_t* hi)
+{
+    if (checked) { *lo = k0 * P; *hi = k1 * P; return; }
+    *lo = first;
+    *hi = nbytes < k1 * P - first ? first + nbytes : k1 * P;
+}
+// The verdict on one touched packet: stream packet k of npk produced `len` bytes (phase 1's word) whose partial is (a, b); `want`
+// is its sidecar entry. The stream's last packet must also hold exactly what the caller's total length leaves for it.
+ZZ_HD inline bool zi_checked_packet_bad(int kind, uint32_t a, uint32_t b, uint32_t len, uint32_t want, uint64_t k, uint64_t npk, uint64_t L, uint32_t P)
+{
+    if (k + 1 == npk && (uint64_t)len != L - (npk - 1) * (uint64_t)P) return true;
+    return zi_cks_public(kind, a, b, len) != want;
+}
+// the trailer against the sidecar's fold: `fa`, `fb` the folded start-0 partial of all L bytes (zlib), or the folded CRC-32
+ZZ_HD inline bool zi_sidecar_trailer_ok(int format, const uint8_t* t, uint32_t fa, uint32_t fb, uint64_t L)
+{
+    if (format == 0) {
+        const uint32_t want = ((uint32_t)t[0] << 24) | ((uint32_t)t[1] << 16) | ((uint32_t)t[2] << 8) | t[3];
+        return adler_combine(1u, L ? ((fb << 16) | fa) : 0u, L) == want;
+    }
+    if (format == 1) {
+        const uint32_t c = t[0] | ((uint32_t)t[1] << 8) | ((uint32_t)t[2] << 16) | ((uint32_t)t[3] << 24);
+        const uint32_t l = t[4] | ((uint32_t)t[5] << 8) | ((uint32_t)t[6] << 16) | ((uint32_t)t[7] << 24);
+        return (L ? fa : 0u) == c && l == (uint32_t)L;
+    }
+    return true;                                                   // a raw stream has no trailer: the sidecar is the caller's own witness
 }
 
 // ---- one complete stream: container header, blocks, trailer, checksum (an item of zz_decode_batch_device) -----------

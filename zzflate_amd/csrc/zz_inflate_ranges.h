@@ -10,6 +10,8 @@
 //                              ZZ_RNG_MAX_WAVES wait for the next attempt with their look-back unchanged.
 //   per wave k_ranges_desc     one thread per stage packet: its read (binary search over the reads' bases) and its descriptor
 //            phase 1, rounds   zz_inflate.h, ceil(log2(longest segment)) + 2 rounds
+//            (checked calls)   zz_inflate_check.h: the wave's touched packets summed on the stage and held to the sidecar; a mismatch is
+//                              charged to the packet's read as a failed packet, in front of the verdict
 //            k_ranges_verdict  one thread per read of the wave: zi_ranges_verdict; status and out_len of a settled read
 //            k_ranges_copy     one workgroup per stage packet: its share of the window to d_dsts[read], for reads settled ZZ_OK
 //
@@ -47,6 +49,7 @@ struct zz_rng_params {
     uint64_t limit;                            // packets a segment may hold
     uint64_t W;                                // wave capacity in stage packets
     zi_read* reads; zz_rng_totals* tot;
+    const uint32_t* cks; uint64_t total_len;   // a checked call's sidecar and decoded length (zz_inflate_check.h); null: unchecked
 };
 
 __device__ __forceinline__ void ranges_settle(const zz_rng_params& Q, uint64_t r, const zi_read& R)
@@ -138,7 +141,7 @@ __global__ __launch_bounds__(256) void k_ranges_desc(zz_rng_params Q, uint64_t g
         else hi = mid;
     }
     const zi_read R = Q.reads[lo];
-    desc[j] = zi_ranges_desc(R, (uint32_t)lo, g - R.base, (uint32_t)(R.base - g0), Q.firsts[lo], Q.nbytes[lo], Q.P);
+    desc[j] = zi_ranges_desc(R, (uint32_t)lo, g - R.base, (uint32_t)(R.base - g0), Q.firsts[lo], Q.nbytes[lo], Q.P, Q.cks != nullptr);
 }
 
 // one thread per read of the wave; `stat` is phase 1's, per stage packet of the wave
@@ -157,19 +160,22 @@ __global__ __launch_bounds__(256) void k_ranges_verdict(zz_rng_params Q, uint64_
 }
 
 // one workgroup per stage packet: bytes [lo, hi) of it, cut at the read's m, to the read's destination. 16-byte stores once the
-// destination is aligned (the source is read as it lies).
+// destination is aligned (the source is read as it lies). The cut is made here from the read itself: a checked call's descriptors
+// hold the widened window.
 __global__ __launch_bounds__(256) void k_ranges_copy(zz_rng_params Q, const zi_read_desc* desc, const uint8_t* stage)
 {
     const zi_read_desc D = desc[blockIdx.x];
     const zi_read R = Q.reads[D.read];
     if (R.state != ZI_RS_DONE || R.status != ZI_RV_OK) return;          // unfinished or failed: nothing is copied in this attempt
     const uint64_t first = Q.firsts[D.read];
-    const uint64_t a = D.k * Q.P + D.lo;                    // stream position of the first byte to copy: >= first
-    uint64_t e = D.k * Q.P + D.hi;
+    uint32_t lo, hi;
+    zi_ranges_cut(D.k, first, Q.nbytes[D.read], Q.P, &lo, &hi);
+    const uint64_t a = D.k * Q.P + lo;                      // stream position of the first byte to copy: >= first
+    uint64_t e = D.k * Q.P + hi;
     if (e > first + R.m) e = first + R.m;
     if (e <= a) return;
     const uint64_t n = e - a;
-    const uint8_t* src = stage + (uint64_t)blockIdx.x * Q.P + D.lo;
+    const uint8_t* src = stage + (uint64_t)blockIdx.x * Q.P + lo;
     uint8_t* dst = Q.dsts[D.read] + (a - first);
     const uint32_t t = threadIdx.x;
     uint64_t head = (16 - ((uintptr_t)dst & 15)) & 15;
