@@ -285,6 +285,44 @@ int zz_packet_index_device(zz_ctx* ctx, uint64_t* d_index, uint64_t max_entries,
 int zz_decode_device(zz_ctx* ctx, const void* d_src, uint64_t src_len, void* d_dst, uint64_t cap, uint64_t* out_len,
                      int format, uint32_t packet_size, const uint64_t* d_index, uint64_t entries, void* hip_stream);
 
+/* ---- any stream, decoded in parallel from a point index ----------------------------------------------------------------
+ * A stream this library did not write (gzip, zlib.compress, pigz, libdeflate, ..) has no packets; without help it takes
+ * zz_decode_device's serial path. Its blocks, though, decode independently once their starts are known, and what crosses a
+ * block start -- matches up to 32 KiB back -- is what zz_decode_device's rounds already resolve. The POINT INDEX says where:
+ * `entries` = segments + 1 rows of two little-endian uint64, (in_bit, out_byte). in_bit counts from the first DEFLATE byte
+ * (behind the container header); row 0 is (0, 0); row k is the header bit of a block (its BFINAL bit) and the decoded bytes in
+ * front of it; the last row is (the bit behind the final block, the decoded length). in_bit ascends strictly, out_byte ascends
+ * (a segment may decode to nothing, it never consumes nothing). 16 bytes per segment and no window copies: about 128 KiB for
+ * a GiB at the default spacing.
+ *
+ * zz_points_index_host builds it: ONE sequential pass over src[0, src_len) in HOST memory, no GPU, no context, the decoded
+ * bytes not kept (a 64 KiB ring is the window). A point is recorded at the first block boundary at or behind every multiple
+ * of `spacing` decoded bytes (spacing >= 1; spacing 1: every block). The container header and the trailer (Adler-32, or CRC-32
+ * and ISIZE) are checked: ZZ_E_DATA for an invalid stream, ZZ_E_UNSUPPORTED for a preset dictionary, as zz_decode_device gives
+ * them. *entries and *out_len are set for every valid stream, also when max_entries is too small (ZZ_E_NOSPACE, nothing
+ * written to points). ZZ_POINTS_SPACING_DEFAULT gives a GiB two segments per resident wavefront (4,096 of them): derived, not
+ * tuned -- measured on 512 MiB streams of host zlib, a spacing of 32768 decodes about twice as fast, because a 64 MiB batch then
+ * holds more segments. */
+#define ZZ_POINTS_SPACING_DEFAULT 131072ull
+int zz_points_index_host(const uint8_t* src, uint64_t src_len, int format, uint64_t spacing, uint64_t* points,
+                         uint64_t max_entries, uint64_t* entries, uint64_t* out_len);
+
+/* zz_decode_device for a stream with a point index: d_src and d_dst in device memory, `points` (entries rows) in HOST memory --
+ * the builder makes it there, it is small, and the call walks it batch by batch. One wavefront decodes one segment straight
+ * into d_dst; bytes that copy from in front of their segment are finished by the rounds; the trailer is checked on the device.
+ * The index is never trusted: rows that are not an index of the shape above, a segment that does not begin at a block header,
+ * does not end at its row's bit or does not decode to exactly its row's bytes, or a checksum mismatch send the call to the
+ * serial path, which decides the result -- every valid stream decodes to its bytes whatever the index says; it decides speed,
+ * not the result. That includes a destination smaller than the stream: the index's own claim about the length is not
+ * evidence, so ZZ_E_NOSPACE comes from the serial path, at its rate (a few MB/s). Results as zz_decode_device: ZZ_E_DATA,
+ * ZZ_E_UNSUPPORTED, ZZ_E_NOSPACE; nothing is written behind `cap`. ZZ_E_ARG before anything is launched: a null context,
+ * source, out_len or points, fewer than 2 entries, a format outside 0..2, an unfinished zz_encode_device_async.
+ * zz_ctx_last_decode_path gives ZZ_DECODE_POINTS (or ZZ_DECODE_SERIAL), zz_ctx_last_decode_stats the pending bytes and rounds.
+ * Workspace: zz_decode_device's batch (4 bytes and one bit per output byte of at most 64 MiB, 8 bytes per 32 KiB tile) plus
+ * 32 bytes per segment of a batch. Synchronous; the host waits once or twice per batch. */
+int zz_decode_points_device(zz_ctx* ctx, const void* d_src, uint64_t src_len, void* d_dst, uint64_t cap, uint64_t* out_len,
+                            int format, const uint64_t* points, uint64_t entries, void* hip_stream);
+
 /* Many independent streams back to their bytes, one call: the mirror image of zz_encode_batch_device. Item i =
  * d_srcs[i][0, d_src_lens[i]) -- one complete zlib / gzip / raw stream: any single-member RFC 1950 / 1951 / 1952 stream,
  * packet-mode or not, any level, written by this library or another -- is decoded into d_dsts[i][0, d_caps[i]);
@@ -526,14 +564,14 @@ int zz_decode_members_ranges_device(zz_ctx* ctx, const void* d_src, uint64_t src
 /* what the last zz_decode_members_ranges_device did: the members it decoded (each once), and the waves */
 int zz_ctx_last_decode_members_ranges_stats(const zz_ctx* ctx, uint64_t* members_decoded, uint32_t* waves);
 
-enum { ZZ_DECODE_INDEXED = 1, ZZ_DECODE_DISCOVERED = 2, ZZ_DECODE_SERIAL = 3 };
-/* which path the last zz_decode_device finished on (0: none) */
+enum { ZZ_DECODE_INDEXED = 1, ZZ_DECODE_DISCOVERED = 2, ZZ_DECODE_SERIAL = 3, ZZ_DECODE_POINTS = 4 };
+/* which path the last zz_decode_device / zz_decode_points_device finished on (0: none) */
 int zz_ctx_last_decode_path(const zz_ctx* ctx);
 /* the packet index the last zz_decode_device recovered by discovery (path ZZ_DECODE_DISCOVERED; ZZ_E_ARG otherwise), in
  * the form of zz_packet_index_device: *entries = packets + 1 (set even when max_entries is too small: ZZ_E_NOSPACE) */
 int zz_ctx_last_decode_index_device(zz_ctx* ctx, uint64_t* d_index, uint64_t max_entries, uint64_t* entries, void* hip_stream);
-/* what the last zz_decode_device's parallel path saw: bytes phase 1 left pending (their match source lay in front of
- * their packet) and the pointer-jumping rounds that resolved them (0 and 0 on the serial path) */
+/* what the last zz_decode_device's or zz_decode_points_device's parallel path saw: bytes phase 1 left pending (their match
+ * source lay in front of their packet or segment) and the pointer-jumping rounds that resolved them (0 and 0 on the serial path) */
 int zz_ctx_last_decode_stats(const zz_ctx* ctx, uint64_t* pending_bytes, uint32_t* rounds);
 
 /* container pieces for assembling shards on the host */

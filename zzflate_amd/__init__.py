@@ -21,6 +21,7 @@ __all__ = [
 ]
 
 DEFAULT_PACKET = 32768
+POINTS_SPACING = 131072          # decoded bytes between two points of a point index (ZZ_POINTS_SPACING_DEFAULT)
 MEMBERS_BLOCK = 65280            # input bytes per member of a blocked gzip file (bgzip's)
 MEMBERS_NO_EOF = 1
 _ERR = (1 << 64) - 1
@@ -94,6 +95,8 @@ def _load():
         "zz_packet_extent_device": (i32, [vp, u64, pu64, pu64, vp]),
         "zz_packet_index_device": (i32, [vp, vp, u64, pu64, vp]),
         "zz_decode_device": (i32, [vp, vp, u64, vp, u64, pu64, i32, u32, vp, u64, vp]),
+        "zz_points_index_host": (i32, [vp, u64, i32, u64, vp, u64, pu64, pu64]),
+        "zz_decode_points_device": (i32, [vp, vp, u64, vp, u64, pu64, i32, vp, u64, vp]),
         "zz_decode_batch_device": (i32, [vp, u64, vp, vp, vp, vp, vp, vp, i32, vp]),
         "zz_decode_range_device": (i32, [vp, vp, u64, i32, u32, vp, u64, u64, u64, vp, u64, pu64, vp]),
         "zz_ctx_last_decode_range_stats": (i32, [vp, pu64, pu64, ctypes.POINTER(u32), pu64]),
@@ -238,6 +241,29 @@ def packet_checksums_host(data, format=Format.Zlib, packet_size=DEFAULT_PACKET):
     return [f(data[k: k + packet_size]) for k in range(0, max(len(data), 1), packet_size)]
 
 
+def points_index_host(data, format=Format.Zlib, spacing=POINTS_SPACING):
+    """The point index of the zlib / gzip / raw stream ``data`` (bytes-like, host memory), made in one sequential pass on the
+    host: ``(points, decoded_length)`` with ``points`` an ``(entries, 2)`` int64 CPU tensor of (bit offset of a block header
+    behind the container header, decoded bytes in front of it); the first row is (0, 0), the last (end of the final block,
+    decoded length). A point is taken at the first block boundary at or behind every multiple of ``spacing`` decoded bytes
+    (1: every block). The stream is checked, trailer included: ZzFlateError (E_DATA, E_UNSUPPORTED) otherwise. What
+    ``Context.decode_points`` takes."""
+    import torch
+    if isinstance(spacing, bool) or not isinstance(spacing, int):
+        raise TypeError("spacing must be an int")
+    if spacing < 1:
+        raise ValueError("spacing must be at least 1")
+    data = bytes(data)
+    entries, n = ctypes.c_uint64(0), ctypes.c_uint64(0)
+    rc = lib.zz_points_index_host(data, len(data), int(format), spacing, None, 0, ctypes.byref(entries), ctypes.byref(n))
+    if rc != E_NOSPACE:
+        _check(rc)
+    points = torch.zeros((entries.value, 2), dtype=torch.int64)
+    _check(lib.zz_points_index_host(data, len(data), int(format), spacing, points.data_ptr(), entries.value, ctypes.byref(entries),
+                                    ctypes.byref(n)))
+    return points, n.value
+
+
 def members_bound(n, block_size=MEMBERS_BLOCK, packet_size=DEFAULT_PACKET, eof=True):
     """The largest file ``Context.encode_members`` can write for ``n`` input bytes (every member stored)."""
     b = lib.zz_encode_members_bound(n, block_size, packet_size, 0 if eof else MEMBERS_NO_EOF)
@@ -293,7 +319,7 @@ def generate_host(kind, seed, first_byte, n):
 
 GEN_TEXT, GEN_RANDOM, GEN_LOG, GEN_MIX = 0, 1, 2, 3
 # which path a decode finished on (Context.last_decode_path)
-DECODE_INDEXED, DECODE_DISCOVERED, DECODE_SERIAL = 1, 2, 3
+DECODE_INDEXED, DECODE_DISCOVERED, DECODE_SERIAL, DECODE_POINTS = 1, 2, 3, 4
 # which path a members decode finished on (Context.last_decode_members_stats)
 MEMBERS_BLOCKED, MEMBERS_WALKED, MEMBERS_SERIAL = 1, 2, 3
 E_NOSPACE, E_ARG, E_UNSUPPORTED, E_DATA = -2, -4, -5, -6
@@ -592,6 +618,24 @@ class Context:
                                     packet_size, ip, ne, st))
         return out.value
 
+    def decode_points(self, src, src_len, dst, cap, points, format=Format.Zlib, stream=None):
+        """``decode`` for any stream that comes with a point index (``points_index_host``): the segments between its points are
+        decoded in parallel, one wavefront each, straight into ``dst``. ``points`` is an ``(entries, 2)`` int64 CPU tensor. The
+        index decides speed, not the result: one that does not describe the stream sends the call to the serial path
+        (``last_decode_path()`` tells DECODE_POINTS from DECODE_SERIAL). Returns the decoded length; raises ZzFlateError as
+        ``decode`` does."""
+        import torch
+        if (not isinstance(points, torch.Tensor) or points.dtype != torch.int64 or points.dim() != 2 or points.shape[1] != 2
+                or not points.is_contiguous()):
+            raise TypeError("points must be a contiguous (entries, 2) int64 tensor (as points_index_host() returns)")
+        if points.device.type != "cpu":
+            raise ValueError(f"points must live in host memory, not on {points.device}")
+        out = ctypes.c_uint64(0)
+        st = self._stream() if stream is None else stream
+        _check(lib.zz_decode_points_device(self._h, self._ptr(src), src_len, self._ptr(dst), cap, ctypes.byref(out), int(format),
+                                           points.data_ptr(), points.shape[0], st))
+        return out.value
+
     def decode_range(self, src, src_len, dst, cap, first, nbytes, format=Format.Zlib, packet_size=DEFAULT_PACKET, index=None,
                      stream=None):
         """Decoded bytes ``[first, first + nbytes)`` of the packet-mode stream ``src[:src_len]`` into ``dst`` (``cap`` bytes);
@@ -795,7 +839,7 @@ class Context:
         return m.value, waves.value
 
     def last_decode_path(self):
-        """DECODE_INDEXED, DECODE_DISCOVERED or DECODE_SERIAL: the path the last decode finished on (0: none)."""
+        """DECODE_INDEXED, DECODE_DISCOVERED, DECODE_SERIAL or DECODE_POINTS: the path the last decode finished on (0: none)."""
         return lib.zz_ctx_last_decode_path(self._h)
 
     def last_decode_index(self, stream=None):

@@ -32,6 +32,7 @@
 #include "zz_inflate.h"
 #include "zz_inflate_ranges.h"
 #include "zz_inflate_check.h"
+#include "zz_inflate_points.h"
 #include "zz_inflate_members.h"
 #include "zz_inflate_members_ranges.h"
 #include "zz_batch.h"
@@ -196,6 +197,8 @@ struct zz_ctx {
         // or the producer's sums), per stage packet its sum, the sidecar's fold, the verdict words
         zz_buf<zz_cks> side, scks; zz_buf<zz_cks_total> side_total; zz_buf<uint32_t> verdict;
         std::vector<uint64_t> last_index;                     // the index discovery recovered (zz_ctx_last_decode_index_device)
+        // zz_decode_points_device (zz_inflate_points.h): a batch's rows, its segments' results, the dealing counter
+        struct { zz_buf<uint64_t> rows; zz_buf<zz_pt_stat> stat; zz_buf<unsigned int> next; } pts;
         // zz_decode_members_device: per stretch of the mark pass (count, base), per candidate (offset, length; then the member
         // list), per member k_inflate_items' descriptors, what the host reads, the serial path's result
         struct {
@@ -1246,6 +1249,124 @@ extern "C" int zz_decode_device(zz_ctx* c, const void* d_src_v, uint64_t src_len
     if (!good) { set_err("not a valid stream of the requested format: checksum or ISIZE mismatch"); return ZZ_E_DATA; }
     *out_len = out;
     return ZZ_OK;
+}
+
+// ---- any stream through a point index (zz_inflate_points.h; the rules in zz_inflate_core.h) -----------------------------------
+// The builder: one sequential pass on the host, no GPU, no context.
+extern "C" int zz_points_index_host(const uint8_t* src, uint64_t src_len, int format, uint64_t spacing, uint64_t* points,
+                                    uint64_t max_entries, uint64_t* entries, uint64_t* out_len)
+{
+    if (!entries || !out_len || (!src && src_len)) { set_err("null argument"); return ZZ_E_ARG; }
+    *entries = 0; *out_len = 0;
+    if (format < ZZ_ZLIB || format > ZZ_DEFLATE) { set_err("format must be ZZ_ZLIB, ZZ_GZIP or ZZ_DEFLATE"); return ZZ_E_ARG; }
+    if (spacing == 0) { set_err("spacing must be at least 1"); return ZZ_E_ARG; }
+    struct sink_t { std::vector<uint64_t> rows; void put(uint64_t bit, uint64_t pos) { rows.push_back(bit); rows.push_back(pos); } } sink;
+    std::vector<uint8_t> ring(ZI_RING);
+    std::vector<zi_tables> S(1);
+    std::vector<zi_sum> sum(1);
+    uint64_t n = 0;
+    const int rc = zi_points_build(src, src_len, format, spacing, sink, ring.data(), S[0], sum[0], &n);
+    if (rc == ZI_ITEM_UNSUPPORTED) { set_err("the stream needs a preset dictionary (FDICT): not supported"); return ZZ_E_UNSUPPORTED; }
+    if (rc) { set_err("not a valid stream of the requested format"); return ZZ_E_DATA; }
+    *entries = sink.rows.size() / 2;
+    *out_len = n;
+    if (!points || max_entries < *entries) { set_err("point index buffer too small"); return ZZ_E_NOSPACE; }
+    memcpy(points, sink.rows.data(), sink.rows.size() * 8);
+    return ZZ_OK;
+}
+
+// phase 1 over the segments, the tile counts and the rounds, batch by batch. DEC_SERIAL: the index or a segment's run was refused
+// (what this wrote so far lies inside [0, cap) and the serial path writes over it).
+static int dec_points(zz_ctx* c, const uint8_t* s, uint64_t sn, const uint64_t* points, uint64_t entries, uint8_t* dst, uint64_t cap,
+                      hipStream_t st, uint64_t* out)
+{
+    auto& D = c->dec;
+    if (!zi_points_check(points, entries, sn, cap, ZZ_INF_BATCH_BYTES)) return DEC_SERIAL;
+    const uint64_t nseg_total = entries - 1;
+    if ((points[2 * nseg_total] + 7) / 8 != sn) return DEC_SERIAL;          // the trailer begins behind the final block's last byte
+    uint64_t max_bytes = 1, max_segs = 1;
+    for (uint64_t k0 = 0, k1; k0 < nseg_total; k0 = k1) {
+        k1 = zi_points_batches(points, entries, k0, ZZ_INF_BATCH_BYTES, ZZ_PT_BATCH_SEGMENTS);
+        max_bytes = std::max(max_bytes, points[2 * k1 + 1] - points[2 * k0 + 1]);
+        max_segs = std::max(max_segs, k1 - k0);
+    }
+    const uint32_t words = ZI_POINTS_TILE / 32;
+    const uint64_t max_tiles = (max_bytes + ZI_POINTS_TILE - 1) / ZI_POINTS_TILE;
+    if (!dec_try_grow(D.st, max_bytes) || !dec_try_grow(D.pend, max_tiles * words) || !dec_try_grow(D.pcnt, max_tiles) ||
+        !dec_try_grow(D.prem, max_tiles) || !dec_try_grow(D.pts.rows, 2 * (max_segs + 1)) || !dec_try_grow(D.pts.stat, max_segs) ||
+        !dec_try_grow(D.pts.next, 1))
+        return DEC_SERIAL;
+    uint64_t pending = 0;
+    uint32_t rounds_used = 0;
+    const uint64_t resident = 256ull * ZZ_PT_WG_PER_CU;                     // persistent wavefronts: what the CUs hold at once
+    for (uint64_t k0 = 0, k1; k0 < nseg_total; k0 = k1) {
+        k1 = zi_points_batches(points, entries, k0, ZZ_INF_BATCH_BYTES, ZZ_PT_BATCH_SEGMENTS);
+        const uint32_t nseg = (uint32_t)(k1 - k0);
+        const uint64_t base = points[2 * k0 + 1], nbytes = points[2 * k1 + 1] - base;
+        const uint32_t tiles = (uint32_t)((nbytes + ZI_POINTS_TILE - 1) / ZI_POINTS_TILE);
+        HIPCHK(hipMemsetAsync(D.tot, 0, 64 * sizeof(unsigned long long), st));
+        HIPCHK(hipMemsetAsync(D.pts.next, 0, sizeof(unsigned int), st));
+        if (tiles) HIPCHK(hipMemsetAsync(D.pend, 0, (uint64_t)tiles * words * 4, st));
+        HIPCHK(hipMemcpyAsync(D.pts.rows, points + 2 * k0, (uint64_t)(nseg + 1) * 16, hipMemcpyHostToDevice, st));
+        zz_pt_params Q;
+        Q.s = s; Q.sn = sn; Q.rows = D.pts.rows; Q.nseg = nseg; Q.last = k1 == nseg_total; Q.dst = dst; Q.base = base; Q.nbytes = nbytes;
+        Q.st = D.st; Q.pend = D.pend; Q.words = (uint64_t)tiles * words; Q.stat = D.pts.stat; Q.next = D.pts.next; Q.tot = D.tot;
+        hipLaunchKernelGGL(k_inflate_segments, dim3((uint32_t)(nseg < resident ? nseg : resident)), dim3(ZZ_INF_THREADS), 0, st, Q);
+        if (tiles) hipLaunchKernelGGL(k_points_count, dim3(tiles), dim3(256), 0, st, D.pend, D.pcnt, D.prem, D.tot);
+        HIPCHK(hipGetLastError());
+        unsigned long long tot[64];
+        HIPCHK(hipMemcpyAsync(tot, D.tot, sizeof tot, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        if (tot[63] != 0) return DEC_SERIAL;                                // a segment is not what the index says
+        if (tot[0] == 0) continue;
+        const uint32_t rounds = dec_ceil_log2(nseg) + 2;                    // a chain has at most one link per segment of a batch
+        zz_res_params R{ dst, base, ZI_POINTS_TILE, tiles, words, D.st, D.pend, D.pcnt, D.prem, D.tot };
+        for (uint32_t r = 1; r <= rounds; ++r) hipLaunchKernelGGL(k_inflate_resolve, dim3(tiles), dim3(ZZ_INF_RES_THREADS), 0, st, R, r);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(tot, D.tot, sizeof tot, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        if (tot[1 + rounds] != 0) return DEC_SERIAL;                        // (cannot happen: the rounds suffice for any chain)
+        uint32_t r = 1;
+        while (r < rounds && tot[1 + r] != 0) ++r;
+        pending += tot[0];
+        rounds_used = std::max(rounds_used, r);
+    }
+    D.last_pending = pending; D.last_rounds = rounds_used;
+    *out = points[2 * nseg_total + 1];
+    return DEC_DONE;
+}
+
+extern "C" int zz_decode_points_device(zz_ctx* c, const void* d_src_v, uint64_t src_len, void* d_dst_v, uint64_t cap, uint64_t* out_len,
+                                       int format, const uint64_t* points, uint64_t entries, void* hip_stream)
+{
+    if (!c || !out_len) { set_err("null argument"); return ZZ_E_ARG; }
+    *out_len = 0;
+    if (format < ZZ_ZLIB || format > ZZ_DEFLATE) { set_err("format must be ZZ_ZLIB, ZZ_GZIP or ZZ_DEFLATE"); return ZZ_E_ARG; }
+    if (!d_src_v || (!d_dst_v && cap)) { set_err("null buffer"); return ZZ_E_ARG; }
+    if (!points || entries < 2) { set_err("a point index has at least two rows (host memory)"); return ZZ_E_ARG; }
+    if (call_pending(c)) return ZZ_E_ARG;
+    const uint8_t* d_src = (const uint8_t*)d_src_v;
+    uint8_t* d_dst = (uint8_t*)d_dst_v;
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t st = (hipStream_t)hip_stream;
+    auto& D = c->dec;
+    D.last_path = 0; D.last_pending = 0; D.last_rounds = 0; D.last_index.clear();
+    if (int rc = D.tot.grow(64)) return rc;
+    if (int rc = D.ok.grow(1)) return rc;
+    int64_t hl = 0;
+    if (int rc = dec_container(d_src, src_len, format, st, &hl)) return rc;
+    const uint64_t tl = (uint64_t)trailer_len(format);
+    const uint64_t sn = src_len - hl - tl;
+    uint64_t out = 0;
+    int got = dec_points(c, d_src + hl, sn, points, entries, d_dst, cap, st, &out);
+    if (got < 0) return got;
+    if (got == DEC_DONE) {
+        bool good = true;
+        if (int rc = dec_check_trailer(c, d_src + src_len - tl, format, d_dst, out, st, &good)) return rc;
+        if (good) { D.last_path = ZZ_DECODE_POINTS; *out_len = out; return ZZ_OK; }
+    }
+    // the index, a segment or the checksum was refused: the serial path decides the result, as if no index had been given
+    return zz_decode_device(c, d_src_v, src_len, d_dst_v, cap, out_len, format, 0, nullptr, 0, hip_stream);
 }
 
 // ---- bytes [first, first + nbytes) of an indexed stream (zz_inflate.h's range kernels; the rules in zz_inflate_core.h) -----

@@ -178,7 +178,8 @@ ZZ_HD inline int zi_decode(const zi_view<uint16_t>& tab, uint64_t& bb, uint32_t&
 // ---- what ends a run of blocks ---------------------------------------------------------------------------------
 enum { ZI_RUN_STREAM = 0,     // until the final block (serial path)
        ZI_RUN_INDEXED = 1,    // a packet with a known end: non-final blocks until bit `end * 8`, or the final block
-       ZI_RUN_DISCOVER = 2 }; // a packet from a candidate start: until `want` bytes at a byte-aligned block end, or the final block
+       ZI_RUN_DISCOVER = 2,   // a packet from a candidate start: until `want` bytes at a byte-aligned block end, or the final block
+       ZI_RUN_POINT = 3 };    // a segment of a point index (zi_pt_segment below): from a bit to a bit, exactly `want` bytes
 struct zi_result {
     int err;
     int final;               // the run ended with the final block
@@ -188,12 +189,34 @@ struct zi_result {
 
 // Out is a policy: lit(v), copy(dist, len), stored(in view, pos, len) return ZI_*; `pos` = bytes produced so far.
 // `view` is the input [0, n) of the run (the packet or the whole stream) in global memory; `in` the byte source over it.
-template <class In, class Out>
+//
+// Pt is a policy known at compile time: what a run does at its block boundaries on top of `mode`. With zi_pt_none (every call
+// that names no policy) nothing of it is compiled in.
+//   skip             bits of byte `start` that lie in front of the run's first block header: a start that is a bit
+//   block(bit, pos)  called in front of every block header: `bit` = consumed() at its BFINAL bit (before any stored-block
+//                    alignment), `pos` = bytes produced so far
+//   stop, last       ZI_RUN_POINT: the bit where the segment ends; whether it is the stream's last segment
+//   end_bit          set by the run: consumed() where it ended
+// ZI_RUN_POINT (segment k of a point index, zi_points_check below): blocks from bit start * 8 + skip until the block boundary
+// where consumed() == stop; a block that ends behind `stop` is ZI_E_SHAPE; the final block is allowed only in the last segment
+// and required there; the segment produces exactly `want` bytes. Behind the last segment R.end is where the trailer starts.
+struct zi_pt_none {
+    static constexpr bool on = false;
+    uint32_t skip; uint64_t stop; bool last; uint64_t end_bit;
+    ZZ_HD void block(uint64_t, uint64_t) {}
+};
+struct zi_pt_segment {
+    static constexpr bool on = true;
+    uint32_t skip; uint64_t stop; bool last; uint64_t end_bit;
+    ZZ_HD void block(uint64_t, uint64_t) {}
+};
+template <class In, class Out, class Pt>
 ZZ_HD zi_result zi_run(In& in, zi_view<const uint8_t> view, uint64_t start, Out& o, zi_tables& S, int mode, uint64_t want,
-                       uint32_t lane, uint32_t nl)
+                       uint32_t lane, uint32_t nl, Pt& pt)
 {
     zi_result R{ ZI_OK, 0, 0, 0 };
     zi_bits<In> b(in, start, view.n);
+    if (Pt::on && pt.skip) (void)b.get(pt.skip);
     zi_view<uint16_t> lit{ S.lit, ZI_TAB }, dst{ S.dst, ZI_TAB };
     zi_view<uint8_t> lens{ S.lens, 320 };
     bool any_block = false;
@@ -201,8 +224,10 @@ ZZ_HD zi_result zi_run(In& in, zi_view<const uint8_t> view, uint64_t start, Out&
         if (any_block) {
             if (mode == ZI_RUN_INDEXED && b.consumed() == view.n * 8) break;
             if (mode == ZI_RUN_DISCOVER && o.pos == want && (b.consumed() & 7) == 0) break;
+            if (Pt::on && mode == ZI_RUN_POINT && b.consumed() == pt.stop) break;
         }
         if (b.consumed() >= view.n * 8) { R.err = ZI_E_DATA; break; }          // the run needs another block that is not there
+        if (Pt::on) pt.block(b.consumed(), o.pos);
         b.refill();
         const uint32_t bfinal = b.get(1), type = b.get(2);
         any_block = true;
@@ -289,15 +314,29 @@ ZZ_HD zi_result zi_run(In& in, zi_view<const uint8_t> view, uint64_t start, Out&
         }
         if (bfinal) { R.final = 1; break; }
         if (mode == ZI_RUN_INDEXED && b.consumed() > view.n * 8) { R.err = ZI_E_DATA; break; }
+        if (Pt::on && mode == ZI_RUN_POINT && b.consumed() > pt.stop) { R.err = ZI_E_SHAPE; break; }
     }
     R.end = (b.consumed() + 7) >> 3;
     R.out = o.pos;
+    if (Pt::on) pt.end_bit = b.consumed();
     if (R.err) return R;
     if (mode == ZI_RUN_STREAM) { if (!R.final) R.err = ZI_E_DATA; return R; }
+    if (Pt::on && mode == ZI_RUN_POINT) {
+        if ((R.final != 0) != pt.last || b.consumed() != pt.stop || o.pos != want) R.err = ZI_E_SHAPE;
+        return R;
+    }
     // a packet: a non-final one is exactly `want` bytes and ends on a byte; the final one holds at most `want`
     if (R.final) { if (o.pos > want) R.err = ZI_E_SHAPE; }
     else if (o.pos != want || (b.consumed() & 7) != 0) R.err = ZI_E_SHAPE;
     return R;
+}
+
+template <class In, class Out>
+ZZ_HD zi_result zi_run(In& in, zi_view<const uint8_t> view, uint64_t start, Out& o, zi_tables& S, int mode, uint64_t want,
+                       uint32_t lane, uint32_t nl)
+{
+    zi_pt_none pt{ 0, 0, false, 0 };
+    return zi_run(in, view, start, o, S, mode, want, lane, nl, pt);
 }
 
 // ---- the whole output as the window (serial path; the CPU reference) -----------------------------------------------
@@ -1049,6 +1088,246 @@ ZZ_HD inline int zi_mr_verdict(const zi_mr_read& R, const zi_mr_tables& T)
     if (T.F[b] != T.F[a]) return ZI_RV_DATA;
     if (T.G[b] != T.G[a]) return ZI_RV_UNSUPPORTED;
     return ZI_RV_OK;
+}
+
+// ---- any stream through a point index (zz_decode_points_device, zz_inflate_points.h; tests/cxx/inflate_points_harness.cpp) ----
+// A stream this library did not write has no packets, but its BLOCKS decode independently once one knows where each starts: a
+// block start carries no Huffman state, and what crosses it are match sources up to 32 KiB back -- pending bytes, which the rounds
+// finish. The POINT INDEX is `entries` = segments + 1 rows (in_bit, out_byte): row k is the header bit of a block (its BFINAL bit,
+// counted from the first DEFLATE byte) and the decoded bytes in front of it; row 0 is (0, 0), the last row (the bit behind the
+// final block, the decoded length). in_bit ascends strictly, out_byte ascends: a segment may produce no byte (an empty stored
+// block), but it never consumes no bit. The index holds no window copies and is never trusted: zi_points_check judges its shape,
+// ZI_RUN_POINT every segment, the trailer's checksum the bytes -- and whatever one of them refuses goes to the serial path.
+//
+// Segments run onto the destination itself (zi_out_segment), BATCHES of whole segments share the pointer array: a batch is a
+// greedy run of segments with at most `limit` bytes of output (and at most `max_segs` segments), its base the first segment's
+// out_byte; pointers, bitmap bits and the tiles of ZI_POINTS_TILE bytes the rounds work on count from that base. A pointer below
+// the base is an earlier batch and therefore final.
+#define ZI_POINTS_TILE 32768u
+ZZ_HD inline bool zi_points_check(const uint64_t* points, uint64_t entries, uint64_t deflate_len, uint64_t cap, uint64_t limit)
+{
+    if (entries < 2 || deflate_len > (~0ull >> 3)) return false;
+    const zi_view<const uint64_t> p{ points, 2 * entries };
+    if (p[0] != 0 || p[1] != 0) return false;
+    for (uint64_t k = 0; k + 1 < entries; ++k) {
+        if (p[2 * k + 2] <= p[2 * k] || p[2 * k + 3] < p[2 * k + 1]) return false;
+        if (p[2 * k + 3] - p[2 * k + 1] > limit) return false;                 // no segment is longer than a batch
+    }
+    return p[2 * entries - 2] <= deflate_len * 8 && p[2 * entries - 1] <= cap;
+}
+// the batch that begins with segment k0 ends in front of segment (return value); the index has passed the check
+ZZ_HD inline uint64_t zi_points_batches(const uint64_t* points, uint64_t entries, uint64_t k0, uint64_t limit, uint64_t max_segs)
+{
+    const zi_view<const uint64_t> p{ points, 2 * entries };
+    uint64_t k1 = k0 + 1;
+    while (k1 + 1 < entries && k1 - k0 < max_segs && p[2 * k1 + 3] - p[2 * k0 + 1] <= limit) ++k1;
+    return k1;
+}
+// pending bytes of a tile: the rounds look at a tile only through its count, and segments and tiles do not line up
+ZZ_HD inline uint32_t zi_popc32(uint32_t v)
+{
+    v = v - ((v >> 1) & 0x55555555u);
+    v = (v & 0x33333333u) + ((v >> 2) & 0x33333333u);
+    return (((v + (v >> 4)) & 0x0F0F0F0Fu) * 0x01010101u) >> 24;
+}
+
+// One segment onto the destination: out[0, n) are the segment's bytes -- n is its announced length, so more than that is
+// ZI_E_SHAPE and a segment never writes outside its own bytes. zi_out_packet's contract with positions counted from the batch
+// base: a byte whose source lies in front of the segment's first byte is PENDING -- its bit in the BATCH's bitmap (at rel + pos)
+// and st[rel + pos] = rel + s + ZI_BIAS; a copy from a pending byte copies its pointer, so chains inside a segment are folded
+// and every pointer leaves its segment. The window is the destination, as for zi_out_linear: a copy reads what other lanes wrote,
+// hence the fence in front of every copy. Or: set(m, q) sets a bit that other lanes and other segments may share a word with,
+// test(m, q) reads one that another lane of this segment may have set.
+template <class Fence, class Or> struct zi_out_segment {
+    zi_view<uint8_t> out;          // the segment's place in the destination
+    zi_view<uint32_t> pend;        // the batch's bitmap, zero before phase 1
+    zi_view<uint32_t> st;          // the batch's pointers
+    uint64_t abs;                  // absolute output position of the segment's first byte
+    uint64_t rel;                  // the same, relative to the batch base
+    uint64_t pos;
+    uint32_t npend;                // pending bytes this lane wrote
+    bool any_pend;                 // uniform: the segment has pending bytes
+    uint32_t lane, nl;
+    Fence fence; Or bits;
+    ZZ_HD int lit(uint32_t v)
+    {
+        if (pos >= out.n) return ZI_E_SHAPE;
+        if (lane == 0) out[pos] = (uint8_t)v;
+        ++pos;
+        return ZI_OK;
+    }
+    ZZ_HD int copy(uint32_t dist, uint32_t len)
+    {
+        if (dist > abs + pos) return ZI_E_FAR;                    // in front of the stream
+        if (out.n - pos < len) return ZI_E_SHAPE;
+        fence();                                                  // bytes, pointers and bits other lanes wrote are visible
+        if (dist > pos || any_pend) {                             // the copy starts in front of the segment, or may meet a pending byte
+            for (uint32_t i = lane; i < len; i += nl) {
+                const int64_t s = (int64_t)pos - (int64_t)dist + (int64_t)(i < dist ? i : i % dist);
+                const uint64_t q = pos + i;
+                if (s < 0) {
+                    st[rel + q] = (uint32_t)((int64_t)rel + s + (int64_t)ZI_BIAS);
+                    bits.set(pend, rel + q); ++npend;
+                } else if (bits.test(pend, rel + (uint64_t)s)) {
+                    st[rel + q] = st[rel + (uint64_t)s];
+                    bits.set(pend, rel + q); ++npend;
+                } else {
+                    out[q] = out[(uint64_t)s];
+                }
+            }
+            any_pend = true;
+        } else {
+            for (uint32_t i = lane; i < len; i += nl) out[pos + i] = out[pos - dist + (i < dist ? i : i % dist)];
+        }
+        pos += len;
+        return ZI_OK;
+    }
+    ZZ_HD int stored(const zi_view<const uint8_t>& in, uint64_t at, uint32_t len)
+    {
+        if (out.n - pos < len) return ZI_E_SHAPE;
+        for (uint32_t i = lane; i < len; i += nl) out[pos + i] = in[at + i];
+        pos += len;
+        return ZI_OK;
+    }
+};
+struct zi_bits_plain {
+    ZZ_HD void set(zi_view<uint32_t>& m, uint64_t q) const { m[q >> 5] |= 1u << (q & 31); }
+    ZZ_HD bool test(const zi_view<uint32_t>& m, uint64_t q) const { return ((m[q >> 5] >> (q & 31)) & 1u) != 0; }
+};
+
+// -- the builder: one sequential pass of one lane, nothing of the output kept (zz_points_index_host) --
+// the stream's checksum, summed piece by piece: Adler-32 (zlib), CRC-32 by a byte table (gzip), nothing (raw)
+struct zi_sum {
+    int format;
+    uint32_t a, b, crc;
+    uint32_t tab[256];
+    ZZ_HD void init(int fmt)
+    {
+        format = fmt; a = 1; b = 0; crc = ~0u;
+        if (fmt != 1) return;
+        for (uint32_t i = 0; i < 256; ++i) {
+            uint32_t c = i;
+            for (int k = 0; k < 8; ++k) c = (c >> 1) ^ ((c & 1u) * ZZ_CRC_POLY);
+            tab[i] = c;
+        }
+    }
+    ZZ_HD void add(const zi_view<const uint8_t>& v, uint64_t at, uint64_t n)
+    {
+        if (format == 0) {
+            while (n) {
+                const uint64_t m = n < 5552 ? n : 5552;            // zlib's NMAX: the sums stay below 2^32
+                for (uint64_t i = 0; i < m; ++i) { a += v[at + i]; b += a; }
+                a %= ZZ_ADLER_MOD; b %= ZZ_ADLER_MOD;
+                at += m; n -= m;
+            }
+        } else if (format == 1) {
+            const zi_view<const uint32_t> t{ tab, 256 };
+            for (uint64_t i = 0; i < n; ++i) crc = (crc >> 8) ^ t[(crc ^ v[at + i]) & 0xFFu];
+        }
+    }
+    // the trailer t[0, 4) or t[0, 8) against the sums over `len` bytes
+    ZZ_HD bool trailer_ok(const zi_view<const uint8_t>& t, uint64_t len) const
+    {
+        if (format == 0) return ((b << 16) | a) == (((uint32_t)t[0] << 24) | ((uint32_t)t[1] << 16) | ((uint32_t)t[2] << 8) | t[3]);
+        if (format != 1) return true;
+        const uint32_t c = t[0] | ((uint32_t)t[1] << 8) | ((uint32_t)t[2] << 16) | ((uint32_t)t[3] << 24);
+        const uint32_t l = t[4] | ((uint32_t)t[5] << 8) | ((uint32_t)t[6] << 16) | ((uint32_t)t[7] << 24);
+        return ~crc == c && l == (uint32_t)len;
+    }
+};
+// The out policy of the builder: a ring of ZI_RING bytes is the window (a match reaches 32 KiB back, the ring holds 64), and the
+// bytes are summed as the ring turns -- every ZI_RING_TURN bytes, long before they are overwritten -- and then forgotten. One lane.
+#define ZI_RING 65536u
+#define ZI_RING_TURN 16384u
+struct zi_out_ring {
+    zi_view<uint8_t> ring;         // ZI_RING bytes
+    zi_sum* sum;
+    uint64_t pos, summed;
+    ZZ_HD void turn()
+    {
+        const zi_view<const uint8_t> r{ ring.p, ring.n };
+        while (summed < pos) {
+            const uint64_t at = summed & (ZI_RING - 1);
+            uint64_t n = pos - summed;
+            if (n > ZI_RING - at) n = ZI_RING - at;
+            sum->add(r, at, n);
+            summed += n;
+        }
+    }
+    ZZ_HD int lit(uint32_t v)
+    {
+        ring[pos & (ZI_RING - 1)] = (uint8_t)v;
+        ++pos;
+        if (pos - summed >= ZI_RING_TURN) turn();
+        return ZI_OK;
+    }
+    ZZ_HD int copy(uint32_t dist, uint32_t len)
+    {
+        if (dist > pos) return ZI_E_FAR;
+        for (uint32_t i = 0; i < len; ++i) ring[(pos + i) & (ZI_RING - 1)] = ring[(pos + i - dist) & (ZI_RING - 1)];
+        pos += len;
+        if (pos - summed >= ZI_RING_TURN) turn();
+        return ZI_OK;
+    }
+    ZZ_HD int stored(const zi_view<const uint8_t>& in, uint64_t at, uint32_t len)
+    {
+        while (len) {
+            const uint32_t n = len < ZI_RING_TURN ? len : ZI_RING_TURN;
+            for (uint32_t i = 0; i < n; ++i) ring[(pos + i) & (ZI_RING - 1)] = in[at + i];
+            pos += n; at += n; len -= n;
+            turn();
+        }
+        return ZI_OK;
+    }
+};
+// the input of a host pass: plain memory
+struct zi_in_mem {
+    zi_view<const uint8_t> v;
+    ZZ_HD uint64_t peek8(uint64_t pos) const
+    {
+        uint64_t r = 0;
+        for (uint32_t i = 0; i < 8; ++i) if (pos + i < v.n) r |= (uint64_t)v[pos + i] << (8 * i);
+        return r;
+    }
+};
+// The builder's block hook: a point at the first block boundary at or behind every multiple of `spacing` decoded bytes (spacing 1:
+// at every block, the empty ones included). Sink: put(in_bit, out_byte), one row.
+template <class Sink> struct zi_pt_record {
+    static constexpr bool on = true;
+    uint32_t skip; uint64_t stop; bool last; uint64_t end_bit;
+    Sink* sink;
+    uint64_t spacing, next;        // the next point: the first boundary with at least `next` bytes in front of it
+    ZZ_HD void block(uint64_t bit, uint64_t pos)
+    {
+        if (pos < next && !(spacing == 1 && bit != 0)) return;
+        sink->put(bit, pos);
+        next = pos - pos % spacing + spacing;
+    }
+};
+// The whole pass: container header, blocks onto the ring, trailer and checksum -- zi_item's verdict (ZI_ITEM_OK, ZI_ITEM_DATA,
+// ZI_ITEM_UNSUPPORTED), the rows through `sink` (the last one included) and the decoded length. ring: ZI_RING bytes.
+template <class Sink>
+ZZ_HD int zi_points_build(const uint8_t* src, uint64_t src_len, int format, uint64_t spacing, Sink& sink, uint8_t* ring, zi_tables& S,
+                          zi_sum& sum, uint64_t* out_len)
+{
+    const int64_t hl = zi_header(format, src, src_len);
+    if (hl == -2) return ZI_ITEM_UNSUPPORTED;
+    if (hl < 0 || spacing == 0) return ZI_ITEM_DATA;
+    const uint64_t tl = format == 0 ? 4 : format == 1 ? 8 : 0;
+    const zi_view<const uint8_t> view{ src + hl, src_len - (uint64_t)hl };     // the blocks and the trailer
+    zi_in_mem in{ view };
+    sum.init(format);
+    zi_out_ring o{ zi_view<uint8_t>{ ring, ZI_RING }, &sum, 0, 0 };
+    zi_pt_record<Sink> pt{ 0, 0, false, 0, &sink, spacing, 0 };
+    S.kind = 0;
+    const zi_result R = zi_run(in, view, 0, o, S, ZI_RUN_STREAM, 0, 0, 1, pt);
+    if (R.err) return ZI_ITEM_DATA;
+    if (R.end > view.n || view.n - R.end != tl) return ZI_ITEM_DATA;           // truncated trailer, or bytes behind it
+    o.turn();
+    if (!sum.trailer_ok(zi_view<const uint8_t>{ view.p + R.end, tl }, R.out)) return ZI_ITEM_DATA;
+    sink.put(pt.end_bit, R.out);
+    *out_len = R.out;
+    return ZI_ITEM_OK;
 }
 
 }  // namespace zz
