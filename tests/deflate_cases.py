@@ -526,15 +526,15 @@ def verdict_counts(cases, at):
 
 
 # ---- packet-mode streams written by zlib -------------------------------------------------------------------------------------
-def foreign_packets(data, P, level, strategy):
-    """(zlib stream, index, data): `data` in packets of P bytes, each written by its own zlib.compressobj that has the 32 KiB in
-    front of the packet as its dictionary -- so matches reach in front of the packet, at any distance -- and closed by the
-    one-byte stored block in place of the sync flush's empty one. Index: offsets from the first DEFLATE byte."""
+def foreign_packets(data, P, level, strategy, window=32768):
+    """(zlib stream, index, data): `data` in packets of P bytes, each written by its own zlib.compressobj that has the `window`
+    bytes (32 KiB) in front of the packet as its dictionary -- so matches reach in front of the packet, at any distance -- and closed
+    by the one-byte stored block in place of the sync flush's empty one. Index: offsets from the first DEFLATE byte."""
     assert data
     npk = (len(data) + P - 1) // P
     index, body = [0], bytearray()
     for k in range(npk):
-        kw = {"zdict": data[max(0, k * P - 32768): k * P]} if k else {}
+        kw = {"zdict": data[max(0, k * P - window): k * P]} if k else {}
         co = zlib.compressobj(level, zlib.DEFLATED, -15, 9, strategy, **kw)
         if k + 1 < npk:
             s = co.compress(data[k * P: (k + 1) * P - 1]) + co.flush(zlib.Z_SYNC_FLUSH)

@@ -321,6 +321,154 @@ def test_garbage_gives_errors(ctx):
                     assert e.code in (zz.E_DATA, zz.E_NOSPACE, zz.E_UNSUPPORTED)
 
 
+EDGE_P = 64
+EDGE_PACKETS = (1 << 18) + 3       # at P <= 256 a batch holds 2^18 packets: the smallest stream that takes two batches
+
+
+def test_indexed_decode_across_the_batch_edge(ctx):
+    """Every packet copies from the one in front of it, the second batch's first packets from the first batch's last."""
+    from deflate_cases import foreign_packets
+    rng = random.Random(41)
+    period = bytes(rng.getrandbits(8) for _ in range(97))
+    n = EDGE_PACKETS * EDGE_P - 5
+    data = (period * (n // 97 + 1))[:n]
+    s, index, _ = foreign_packets(data, EDGE_P, 9, zlib.Z_DEFAULT_STRATEGY, window=512)
+    assert len(index) == EDGE_PACKETS + 1
+    stream, idx = dev(s), torch.tensor(index, dtype=torch.int64).cuda()
+    out, got = decode(ctx, stream, len(s), n, 0, EDGE_P, idx)
+    assert got == n and torch.equal(out[:n], dev(data))
+    assert ctx.last_decode_path() == zz.DECODE_INDEXED
+    assert ctx.last_decode_stats()[0] > 0
+    out.fill_(0x5A)
+    expect(zz.E_NOSPACE, lambda: ctx.decode(stream, len(s), out, n - 1, 0, EDGE_P, idx))
+    assert bool((out[n - 1:] == 0x5A).all())
+
+
+def test_discovery_with_more_candidates_than_a_batch(ctx):
+    n = EDGE_PACKETS * EDGE_P - 5
+    data = synth("words", n, 17)
+    src = dev(data)
+    stream, w = encode(ctx, src, n, 0, 1, EDGE_P)
+    idx = ctx.packet_index()
+    assert idx.numel() == EDGE_PACKETS + 1
+    out, got = decode(ctx, stream, w, n, 0, EDGE_P, None)
+    assert got == n and torch.equal(out[:n], src)
+    assert ctx.last_decode_path() == zz.DECODE_DISCOVERED
+    assert torch.equal(ctx.last_decode_index(), idx)
+
+
+def every_path_calls():
+    """(name, call) for every decode entry point, on inputs made once: call(context) -> a value that compares (bytes, lengths,
+    statuses). 300,000 bytes in packets of 1000."""
+    P, n = 1000, 300000
+    data = synth("words", 200000, 23) + synth("period", n - 200000, 23)
+    src = dev(data)
+    b = zz.Context(0)
+    stream, w = encode(b, src, n, 0, 2, P)
+    idx = b.packet_index()
+    cks = b.packet_checksums(src, n, 0, P)
+    foreign = zlib.compress(data, 6)
+    fsrc = dev(foreign)
+    points, pn = zz.points_index_host(foreign, zz.Format.Zlib, 16384)
+    assert pn == n
+    items = [zlib.compress(data[3000 * i: 3000 * (i + 1) + i], 6) for i in range(40)]
+    isrcs = [dev(s) for s in items]
+    icaps = [3000 + i if i != 7 else 100 for i in range(40)]
+    mcap = zz.members_bound(n)
+    mfile = torch.zeros(mcap, dtype=torch.uint8, device="cuda")
+    mw = b.encode_members(src, n, mfile, mcap, level=1)
+    midx = b.members_index(mfile, mw)
+    b.close()
+    firsts, lens = [0, 999, 150000, n - 500, n + P], [10, 2002, 40000, 1000, 5]
+
+    def whole(P2, index):
+        def call(c):
+            out, got = decode(c, stream, w, n, 0, P2, index)
+            return got, bytes(out[:got].cpu().numpy()), c.last_decode_path(), c.last_decode_stats()
+        return call
+
+    def by_points(c):
+        out = torch.zeros(n, dtype=torch.uint8, device="cuda")
+        got = c.decode_points(fsrc, len(foreign), out, n, points, zz.Format.Zlib)
+        return got, bytes(out[:got].cpu().numpy()), c.last_decode_path(), c.last_decode_stats()
+
+    def one_range(checked):
+        def call(c):
+            out = torch.zeros(70000, dtype=torch.uint8, device="cuda")
+            if checked:
+                got = c.decode_range_checked(stream, w, out, 70000, 123456, 70000, cks, n, 0, P, idx)
+            else:
+                got = c.decode_range(stream, w, out, 70000, 123456, 70000, 0, P, idx)
+            return got, bytes(out[:got].cpu().numpy()), c.last_decode_range_stats()
+        return call
+
+    def many_ranges(checked):
+        def call(c):
+            outs = [torch.zeros(ln, dtype=torch.uint8, device="cuda") for ln in lens]
+            if checked:
+                got, status = c.decode_ranges_checked(stream, w, firsts, lens, outs, cks, n, None, 0, P, idx)
+            else:
+                got, status = c.decode_ranges(stream, w, firsts, lens, outs, None, 0, P, idx)
+            return got, status, [bytes(o.cpu().numpy()) for o in outs], c.last_decode_ranges_stats()
+        return call
+
+    def batch(c):
+        outs = [torch.zeros(3100, dtype=torch.uint8, device="cuda") for _ in items]
+        got, status = c.decode_batch(isrcs, outs, zz.Format.Zlib, icaps)
+        return got, status, [bytes(o[:g].cpu().numpy()) for o, g in zip(outs, got) if g is not None]
+
+    def members(c):
+        out = torch.zeros(n, dtype=torch.uint8, device="cuda")
+        got = c.decode_members(mfile, mw, out, n)
+        return got, bytes(out[:got].cpu().numpy()), c.last_decode_members_stats()
+
+    def members_index(c):
+        return c.members_index(mfile, mw).cpu().tolist()
+
+    def members_ranges(c):
+        outs = [torch.zeros(ln, dtype=torch.uint8, device="cuda") for ln in lens]
+        got, status = c.decode_members_ranges(mfile, mw, midx, firsts, lens, outs)
+        return got, status, [bytes(o.cpu().numpy()) for o in outs], c.last_decode_members_ranges_stats()
+
+    return [("decode indexed", whole(P, idx)), ("decode discovered", whole(P, None)), ("decode serial", whole(0, None)),
+            ("decode_points", by_points), ("decode_range", one_range(False)), ("decode_range_checked", one_range(True)),
+            ("decode_ranges", many_ranges(False)), ("decode_ranges_checked", many_ranges(True)), ("decode_batch", batch),
+            ("decode_members", members), ("members_index", members_index), ("decode_members_ranges", members_ranges)], data
+
+
+@pytest.fixture(scope="module")
+def every_path():
+    """The calls, and what each gives on a context of its own."""
+    calls, data = every_path_calls()
+    fresh = {}
+    for name, call in calls:
+        c = zz.Context(0)
+        fresh[name] = call(c)
+        c.close()
+    # the references are the data's own bytes, whichever path made them
+    for name in ("decode indexed", "decode discovered", "decode serial", "decode_points", "decode_members"):
+        assert fresh[name][:2] == (len(data), data), name
+    assert [fresh[name][2] for name in ("decode indexed", "decode discovered", "decode serial", "decode_points")] == \
+        [zz.DECODE_INDEXED, zz.DECODE_DISCOVERED, zz.DECODE_SERIAL, zz.DECODE_POINTS]
+    assert fresh["decode_range"][:2] == (70000, data[123456:193456]) and fresh["decode_range_checked"][:2] == fresh["decode_range"][:2]
+    for name in ("decode_ranges", "decode_ranges_checked", "decode_members_ranges"):
+        got, status, outs = fresh[name][:3]
+        assert got == [10, 2002, 40000, 500, None] and status == [0, 0, 0, 0, zz.E_ARG], name
+        assert all(o[:g] == data[f:f + g] for o, g, f in zip(outs, got, (0, 999, 150000, len(data) - 500))), name
+    assert fresh["decode_batch"][1] == [0 if i != 7 else zz.E_NOSPACE for i in range(40)]
+    return calls, fresh
+
+
+@pytest.mark.parametrize("order", ["listed", "reversed"])
+def test_one_context_every_decode_path(every_path, order):
+    """The paths share the context's buffers: a call after a smaller (or larger) one of another path gives what it gives alone."""
+    calls, fresh = every_path
+    c = zz.Context(0)
+    for name, call in (calls if order == "listed" else calls[::-1]):
+        assert call(c) == fresh[name], name
+    c.close()
+
+
 GIB = 1 << 30
 
 

@@ -980,54 +980,130 @@ extern "C" int zz_ctx_last_decode_stats(const zz_ctx* c, uint64_t* pending_bytes
     return ZZ_OK;
 }
 
-// the parallel paths' workspace: when it cannot be had, the call goes to the serial path, which needs none
-template <class T> static bool dec_try_grow(zz_buf<T>& b, uint64_t count)
-{
-    if (b.grow(count) == ZZ_OK) return true;
-    (void)hipGetLastError();
-    return false;
-}
-static uint32_t dec_ceil_log2(uint64_t x) { uint32_t r = 0; while ((1ull << r) < x) ++r; return r; }
+// the parallel paths' workspace (rc: what growing it gave): when it cannot be had, the sticky HIP error is cleared and the call goes
+// to the serial path, which needs none
+static bool dec_have(int rc) { if (rc != ZZ_OK) (void)hipGetLastError(); return rc == ZZ_OK; }
 
 // what the parallel paths return (negative: a HIP error)
 enum { DEC_SERIAL = 0,      // not taken: the index, the packet size or discovery does not fit this stream
        DEC_DONE = 1,        // decoded; *out = bytes
        DEC_NOSPACE = 2 };   // decoded -- so this is the stream's true output -- but it does not fit the destination
 
-// phase 1 and phase 2 over packets [0, npk) starting at starts[0, nstarts) (device). Indexed: per-packet results per batch,
-// the last packet's kept in *last_stat; discovery: per candidate in dec.ends / dec.stat. Counters in dec.tot.
-static int dec_packets(zz_ctx* c, const uint8_t* s, uint64_t sn, const uint64_t* starts, uint64_t nstarts, uint64_t npk, int mode,
-                       uint32_t P, uint8_t* dst, uint64_t cap, hipStream_t st, uint32_t* rounds_launched, uint32_t* last_stat)
+// ---- what the decode drivers share (a batch's geometry and its rounds: zz_inf_geometry, zz_inf_rounds in zz_inflate.h) ---------
+static bool dec_format_ok(int format) { const bool ok = format >= ZZ_ZLIB && format <= ZZ_DEFLATE; if (!ok) set_err("format must be ZZ_ZLIB, ZZ_GZIP or ZZ_DEFLATE"); return ok; }
+static bool dec_packet_ok(uint32_t P, uint32_t min) { const bool ok = P >= min && P <= ZZ_MAX_PACKET_SIZE; if (!ok) set_err("packet size must be " + std::to_string(min) + "..32768"); return ok; }
+// zz_decode_device and zz_decode_points_device start here: the stats they report, the counter block, the trailer's verdict word
+static int begin_decode_call(zz_ctx* c)
 {
     auto& D = c->dec;
-    const uint32_t words = ((P + 31) / 32 + 3) & ~3u;
-    uint64_t B = ZZ_INF_BATCH_BYTES / P;
-    if (B > ZZ_INF_BATCH_PACKETS) B = ZZ_INF_BATCH_PACKETS;
-    if (B > npk) B = npk;
-    if (B == 0) B = 1;
-    const uint64_t per = mode == ZZ_INF_INDEXED ? B : npk;      // results kept per batch, or per candidate (bounded)
-    if (!dec_try_grow(D.st, B * P) || !dec_try_grow(D.pend, B * words) || !dec_try_grow(D.pcnt, B) || !dec_try_grow(D.prem, B) ||
-        !dec_try_grow(D.ends, per) || !dec_try_grow(D.stat, per))
-        return DEC_SERIAL;
-    HIPCHK(hipMemsetAsync(D.tot, 0, 64 * sizeof(unsigned long long), st));
-    const uint32_t rounds = dec_ceil_log2(B) + 2;               // a chain has at most one link per packet of a batch
+    D.last_path = 0; D.last_pending = 0; D.last_rounds = 0; D.last_index.clear();
+    if (int rc = D.tot.grow(ZZ_TOT_SLOTS)) return rc;
+    return D.ok.grow(1);
+}
+// The DEFLATE bytes a parallel path works on and where their packets start: an index of npk + 1 entries, or discovery's candidates
+struct dec_stream { const uint8_t* s; uint64_t sn; const uint64_t* starts; uint64_t nstarts, npk; uint32_t P; };
+// phase 1 and phase 2's workspace for `packets` packets (points: tiles) of `bytes` output bytes and `results` per-packet results. The
+// range reads return a failure; the whole-stream and points paths go serial (dec_have).
+static int dec_batch_workspace(zz_ctx* c, uint64_t packets, uint64_t bytes, uint32_t words, uint64_t results)
+{
+    auto& D = c->dec;
+    if (int rc = D.st.grow(bytes)) return rc;
+    if (int rc = D.pend.grow(packets * words)) return rc;
+    if (int rc = D.pcnt.grow(packets)) return rc;
+    if (int rc = D.prem.grow(packets)) return rc;
+    if (int rc = D.ends.grow(results)) return rc;
+    return D.stat.grow(results);
+}
+// phase 1's parameters but for the batch: the caller sets k0, npk, mode, dst, cap and ebase
+static zz_inf_params dec_inf_params(zz_ctx* c, const dec_stream& S, uint32_t words)
+{
+    auto& D = c->dec;
+    zz_inf_params Q = {};
+    Q.s = S.s; Q.sn = S.sn; Q.starts = S.starts; Q.nstarts = S.nstarts; Q.npk_total = S.npk; Q.P = S.P;
+    Q.st = D.st; Q.pend = D.pend; Q.words = words; Q.pcnt = D.pcnt; Q.prem = D.prem; Q.ends = D.ends; Q.stat = D.stat; Q.tot = D.tot;
+    return Q;
+}
+// the counter block on the host: one copy, one wait
+static int dec_read_tot(zz_ctx* c, unsigned long long (&tot)[ZZ_TOT_SLOTS], hipStream_t st)
+{
+    HIPCHK(hipMemcpyAsync(tot, c->dec.tot, sizeof tot, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return ZZ_OK;
+}
+// A checked read's sidecar (zz_inflate_check.h) and the container whose trailer it folds to, built by the checked entry points; the
+// unchecked calls pass none (nullptr).
+struct dec_sidecar { const uint32_t* cks; uint64_t L; int kind, format; };
+// what the checked calls refuse before anything is launched, on top of the unchecked calls' own
+static int dec_sidecar_args(const dec_sidecar& sc, uint64_t entries, uint32_t P)
+{
+    if (!sc.cks) { set_err("null argument"); return ZZ_E_ARG; }
+    if (entries - 1 > 0x7fffffffull) { set_err("at most 2^31 - 1 packets"); return ZZ_E_ARG; }
+    if (entries - 1 != zi_sidecar_entries(sc.L, P)) { set_err("the index's packets are not total_len's: entries - 1 != max(1, ceil(total_len / packet_size))"); return ZZ_E_ARG; }
+    return ZZ_OK;
+}
+// The sidecar against the stream's trailer, enqueued: unpack, fold, verdict. The caller reads D.verdict[0] (1: it holds) with its
+// next wait. A raw stream has no trailer: nothing is launched, and nothing is read.
+static int dec_sidecar_fold(zz_ctx* c, const dec_sidecar& sc, uint64_t npk, uint32_t P, const uint8_t* trailer, hipStream_t st)
+{
+    auto& D = c->dec;
+    if (sc.format == ZZ_DEFLATE) return ZZ_OK;
+    if (int rc = D.side.grow(npk)) return rc;
+    if (int rc = D.side_total.grow(1)) return rc;
+    if (int rc = D.verdict.grow(2)) return rc;
+    HIPCHK(hipMemsetAsync(D.verdict, 0, 8, st));
+    hipLaunchKernelGGL(k_sidecar_unpack, dim3((uint32_t)((npk + 255) / 256)), dim3(256), 0, st, sc.cks, (uint32_t)npk, P, sc.L, sc.kind, D.side.p, D.verdict.p);
+    hipLaunchKernelGGL(k_cks_reduce, dim3(1), dim3(ZZ_RED_THREADS), 0, st, D.side.p, (uint32_t)npk, P, sc.L, sc.kind, D.side_total.p);
+    hipLaunchKernelGGL(k_sidecar_verdict, dim3(1), dim3(1), 0, st, trailer, sc.format, D.side_total.p, sc.L, D.verdict.p);
+    HIPCHK(hipGetLastError());
+    return ZZ_OK;
+}
+// The front of every indexed call: the index's two ends -- and the sidecar's verdict, its fold enqueued first -- read in one wait.
+// What a mismatch means is the caller's: the serial path, an error, or every read's failure.
+enum { DEC_FRONT_OK = 0, DEC_FRONT_ENDS = 1, DEC_FRONT_SIDECAR = 2 };       // (negative: a HIP error)
+static int dec_index_front(zz_ctx* c, const dec_stream& S, const dec_sidecar* sc, hipStream_t st)
+{
+    uint64_t ends[2];
+    uint32_t holds = 1;                                             // the sidecar folds to the trailer
+    if (sc) if (int rc = dec_sidecar_fold(c, *sc, S.npk, S.P, S.s + S.sn, st)) return rc;
+    HIPCHK(hipMemcpyAsync(&ends[0], S.starts, 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(&ends[1], S.starts + S.npk, 8, hipMemcpyDeviceToHost, st));
+    if (sc && sc->format != ZZ_DEFLATE) HIPCHK(hipMemcpyAsync(&holds, c->dec.verdict.p, 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (ends[0] != 0 || ends[1] != S.sn) return DEC_FRONT_ENDS;
+    return holds == 1 ? DEC_FRONT_OK : DEC_FRONT_SIDECAR;
+}
+static int dec_front_refused(int front)                             // (the range reads: either is ZZ_E_DATA)
+{
+    set_err(front == DEC_FRONT_ENDS ? "the index does not describe this stream: its ends are not the DEFLATE bytes' ends"
+                                    : "the packet checksums do not describe this stream: they do not fold to its trailer (checksum or length)");
+    return ZZ_E_DATA;
+}
+
+// phase 1 and phase 2 over S's packets [0, npk) (starts on the device). Indexed: per-packet results per batch,
+// the last packet's kept in *last_stat; discovery: per candidate in dec.ends / dec.stat. Counters in dec.tot.
+static int dec_packets(zz_ctx* c, const dec_stream& S, int mode, uint8_t* dst, uint64_t cap, hipStream_t st, uint32_t* rounds_launched,
+                       uint32_t* last_stat)
+{
+    auto& D = c->dec;
+    const uint32_t P = S.P;
+    const zz_inf_geom geo = zz_inf_geometry(P, S.npk ? S.npk : 1);
+    const uint64_t B = geo.B;
+    const uint64_t per = mode == ZZ_INF_INDEXED ? B : S.npk;    // results kept per batch, or per candidate (bounded)
+    if (!dec_have(dec_batch_workspace(c, B, B * P, geo.words, per))) return DEC_SERIAL;
+    HIPCHK(hipMemsetAsync(D.tot, 0, ZZ_TOT_SLOTS * sizeof(unsigned long long), st));
+    const uint32_t rounds = zz_inf_rounds(B);
     *rounds_launched = rounds;
-    const size_t lds = (size_t)words * 4 + ZZ_INF_IBUF + ((P + 15) & ~15u);
-    uint64_t last_base = 0;
-    for (uint64_t k0 = 0; k0 < npk; k0 += B) {
-        const uint32_t nb = (uint32_t)(npk - k0 < B ? npk - k0 : B);
-        zz_inf_params Q;
-        Q.s = s; Q.sn = sn; Q.starts = starts; Q.nstarts = nstarts; Q.k0 = k0; Q.npk = nb; Q.npk_total = npk;
-        Q.P = P; Q.mode = mode; Q.dst = dst; Q.cap = cap;
-        Q.st = D.st; Q.pend = D.pend; Q.words = words; Q.pcnt = D.pcnt; Q.prem = D.prem; Q.ends = D.ends; Q.stat = D.stat; Q.tot = D.tot;
-        Q.ebase = mode == ZZ_INF_INDEXED ? k0 : 0;
-        last_base = Q.ebase;
-        hipLaunchKernelGGL(k_inflate_packets, dim3(nb), dim3(ZZ_INF_THREADS), lds, st, Q);
-        zz_res_params R{ dst, k0 * P, P, nb, words, D.st, D.pend, D.pcnt, D.prem, D.tot };
+    zz_inf_params Q = dec_inf_params(c, S, geo.words);
+    Q.mode = mode; Q.dst = dst; Q.cap = cap;
+    for (uint64_t k0 = 0; k0 < S.npk; k0 += B) {
+        const uint32_t nb = (uint32_t)(S.npk - k0 < B ? S.npk - k0 : B);
+        Q.k0 = k0; Q.npk = nb; Q.ebase = mode == ZZ_INF_INDEXED ? k0 : 0;
+        hipLaunchKernelGGL(k_inflate_packets, dim3(nb), dim3(ZZ_INF_THREADS), geo.lds, st, Q);
+        zz_res_params R{ dst, k0 * P, P, nb, geo.words, D.st, D.pend, D.pcnt, D.prem, D.tot };
         for (uint32_t r = 1; r <= rounds; ++r) hipLaunchKernelGGL(k_inflate_resolve, dim3(nb), dim3(ZZ_INF_RES_THREADS), 0, st, R, r);
     }
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(last_stat, D.stat + (npk - 1 - last_base), 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(last_stat, D.stat + (S.npk - 1 - Q.ebase), 4, hipMemcpyDeviceToHost, st));
     return DEC_DONE;
 }
 
@@ -1035,16 +1111,15 @@ static int dec_packets(zz_ctx* c, const uint8_t* s, uint64_t sn, const uint64_t*
 static int dec_collect(zz_ctx* c, uint64_t npk, uint32_t P, uint32_t rounds, uint32_t last, hipStream_t st, uint64_t* out)
 {
     auto& D = c->dec;
-    unsigned long long tot[64];
-    HIPCHK(hipMemcpyAsync(tot, D.tot, sizeof tot, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    if (tot[63] != 0 || !(last & 1u) || !(last & 2u)) return DEC_SERIAL;
+    unsigned long long tot[ZZ_TOT_SLOTS];
+    if (int rc = dec_read_tot(c, tot, st)) return rc;
+    if (tot[ZZ_TOT_FAILED] != 0 || !(last & 1u) || !(last & 2u)) return DEC_SERIAL;
     *out = (npk - 1) * (uint64_t)P + (last >> 3);
-    if (tot[62] != 0) return DEC_NOSPACE;
-    if (tot[1 + rounds] != 0) return DEC_SERIAL;            // (cannot happen: the rounds suffice for any chain)
-    D.last_pending = tot[0];
+    if (tot[ZZ_TOT_UNWRITTEN] != 0) return DEC_NOSPACE;
+    if (tot[ZZ_TOT_OPEN + rounds] != 0) return DEC_SERIAL;  // (cannot happen: the rounds suffice for any chain)
+    D.last_pending = tot[ZZ_TOT_PENDING];
     D.last_rounds = 0;
-    if (tot[0]) { uint32_t r = 1; while (r < rounds && tot[1 + r] != 0) ++r; D.last_rounds = r; }
+    if (tot[ZZ_TOT_PENDING]) { uint32_t r = 1; while (r < rounds && tot[ZZ_TOT_OPEN + r] != 0) ++r; D.last_rounds = r; }
     return DEC_DONE;
 }
 
@@ -1054,13 +1129,10 @@ static int dec_indexed(zz_ctx* c, const uint8_t* s, uint64_t sn, const uint64_t*
     if (entries < 2) return DEC_SERIAL;
     const uint64_t npk = entries - 1;
     if (npk > (1ull << 40)) return DEC_SERIAL;
-    uint64_t ends[2];
-    HIPCHK(hipMemcpyAsync(&ends[0], d_index, 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(&ends[1], d_index + npk, 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    if (ends[0] != 0 || ends[1] != sn) return DEC_SERIAL;
+    const dec_stream S{ s, sn, d_index, entries, npk, P };
+    if (const int front = dec_index_front(c, S, nullptr, st)) return front < 0 ? front : DEC_SERIAL;
     uint32_t rounds = 0, last = 0;
-    int rc = dec_packets(c, s, sn, d_index, entries, npk, ZZ_INF_INDEXED, P, dst, cap, st, &rounds, &last);
+    int rc = dec_packets(c, S, ZZ_INF_INDEXED, dst, cap, st, &rounds, &last);
     if (rc != DEC_DONE) return rc;
     return dec_collect(c, npk, P, rounds, last, st, out);
 }
@@ -1075,8 +1147,8 @@ static int dec_discover(zz_ctx* c, const uint8_t* s, uint64_t sn, uint32_t P, ui
     // block): twice the packets that can fit bounds the speculative work on adversarial input
     uint64_t cap_c = 2 * (sn / ((uint64_t)P / 1032 + 6)) + 64;
     if (cap_c > ZZ_INF_MAX_CANDIDATES) cap_c = ZZ_INF_MAX_CANDIDATES;
-    if (!dec_try_grow(D.cand, cap_c + 1)) return DEC_SERIAL;
-    HIPCHK(hipMemsetAsync(D.tot, 0, 64 * sizeof(unsigned long long), st));
+    if (!dec_have(D.cand.grow(cap_c + 1))) return DEC_SERIAL;
+    HIPCHK(hipMemsetAsync(D.tot, 0, ZZ_TOT_SLOTS * sizeof(unsigned long long), st));
     {
         uint64_t g = (sn + 255) / 256;
         if (g > 8192) g = 8192;
@@ -1097,7 +1169,7 @@ static int dec_discover(zz_ctx* c, const uint8_t* s, uint64_t sn, uint32_t P, ui
     const uint64_t nc = cand.size();
     HIPCHK(hipMemcpyAsync(D.cand, cand.data(), nc * 8, hipMemcpyHostToDevice, st));
     uint32_t rounds = 0, last = 0;
-    int rc = dec_packets(c, s, sn, D.cand, nc, nc, ZZ_INF_DISCOVER, P, dst, cap, st, &rounds, &last);
+    int rc = dec_packets(c, dec_stream{ s, sn, D.cand, nc, nc, P }, ZZ_INF_DISCOVER, dst, cap, st, &rounds, &last);
     if (rc != DEC_DONE) return rc;
     std::vector<uint64_t> ends(nc);
     std::vector<uint32_t> stat(nc);
@@ -1195,8 +1267,7 @@ extern "C" int zz_decode_device(zz_ctx* c, const void* d_src_v, uint64_t src_len
 {
     if (!c || !out_len) { set_err("null argument"); return ZZ_E_ARG; }
     *out_len = 0;
-    if (format < ZZ_ZLIB || format > ZZ_DEFLATE) { set_err("format must be ZZ_ZLIB, ZZ_GZIP or ZZ_DEFLATE"); return ZZ_E_ARG; }
-    if (P > ZZ_MAX_PACKET_SIZE) { set_err("packet size must be 0..32768"); return ZZ_E_ARG; }
+    if (!dec_format_ok(format) || !dec_packet_ok(P, 0)) return ZZ_E_ARG;
     if ((!d_src_v && src_len) || (!d_dst_v && cap)) { set_err("null buffer"); return ZZ_E_ARG; }
     if (call_pending(c)) return ZZ_E_ARG;
     const uint8_t* d_src = (const uint8_t*)d_src_v;
@@ -1204,10 +1275,8 @@ extern "C" int zz_decode_device(zz_ctx* c, const void* d_src_v, uint64_t src_len
     HIPCHK(hipSetDevice(c->device));
     hipStream_t st = (hipStream_t)hip_stream;
     auto& D = c->dec;
-    D.last_path = 0; D.last_pending = 0; D.last_rounds = 0; D.last_index.clear();
-    if (int rc = D.tot.grow(64)) return rc;
+    if (int rc = begin_decode_call(c)) return rc;
     if (int rc = D.sres.grow(1)) return rc;
-    if (int rc = D.ok.grow(1)) return rc;
     int64_t hl = 0;
     if (int rc = dec_container(d_src, src_len, format, st, &hl)) return rc;
     const uint64_t tl = (uint64_t)trailer_len(format);
@@ -1258,7 +1327,7 @@ extern "C" int zz_points_index_host(const uint8_t* src, uint64_t src_len, int fo
 {
     if (!entries || !out_len || (!src && src_len)) { set_err("null argument"); return ZZ_E_ARG; }
     *entries = 0; *out_len = 0;
-    if (format < ZZ_ZLIB || format > ZZ_DEFLATE) { set_err("format must be ZZ_ZLIB, ZZ_GZIP or ZZ_DEFLATE"); return ZZ_E_ARG; }
+    if (!dec_format_ok(format)) return ZZ_E_ARG;
     if (spacing == 0) { set_err("spacing must be at least 1"); return ZZ_E_ARG; }
     struct sink_t { std::vector<uint64_t> rows; void put(uint64_t bit, uint64_t pos) { rows.push_back(bit); rows.push_back(pos); } } sink;
     std::vector<uint8_t> ring(ZI_RING);
@@ -1292,9 +1361,8 @@ static int dec_points(zz_ctx* c, const uint8_t* s, uint64_t sn, const uint64_t* 
     }
     const uint32_t words = ZI_POINTS_TILE / 32;
     const uint64_t max_tiles = (max_bytes + ZI_POINTS_TILE - 1) / ZI_POINTS_TILE;
-    if (!dec_try_grow(D.st, max_bytes) || !dec_try_grow(D.pend, max_tiles * words) || !dec_try_grow(D.pcnt, max_tiles) ||
-        !dec_try_grow(D.prem, max_tiles) || !dec_try_grow(D.pts.rows, 2 * (max_segs + 1)) || !dec_try_grow(D.pts.stat, max_segs) ||
-        !dec_try_grow(D.pts.next, 1))
+    if (!dec_have(dec_batch_workspace(c, max_tiles, max_bytes, words, 0)) || !dec_have(D.pts.rows.grow(2 * (max_segs + 1))) ||
+        !dec_have(D.pts.stat.grow(max_segs)) || !dec_have(D.pts.next.grow(1)))
         return DEC_SERIAL;
     uint64_t pending = 0;
     uint32_t rounds_used = 0;
@@ -1304,7 +1372,7 @@ static int dec_points(zz_ctx* c, const uint8_t* s, uint64_t sn, const uint64_t* 
         const uint32_t nseg = (uint32_t)(k1 - k0);
         const uint64_t base = points[2 * k0 + 1], nbytes = points[2 * k1 + 1] - base;
         const uint32_t tiles = (uint32_t)((nbytes + ZI_POINTS_TILE - 1) / ZI_POINTS_TILE);
-        HIPCHK(hipMemsetAsync(D.tot, 0, 64 * sizeof(unsigned long long), st));
+        HIPCHK(hipMemsetAsync(D.tot, 0, ZZ_TOT_SLOTS * sizeof(unsigned long long), st));
         HIPCHK(hipMemsetAsync(D.pts.next, 0, sizeof(unsigned int), st));
         if (tiles) HIPCHK(hipMemsetAsync(D.pend, 0, (uint64_t)tiles * words * 4, st));
         HIPCHK(hipMemcpyAsync(D.pts.rows, points + 2 * k0, (uint64_t)(nseg + 1) * 16, hipMemcpyHostToDevice, st));
@@ -1314,21 +1382,19 @@ static int dec_points(zz_ctx* c, const uint8_t* s, uint64_t sn, const uint64_t* 
         hipLaunchKernelGGL(k_inflate_segments, dim3((uint32_t)(nseg < resident ? nseg : resident)), dim3(ZZ_INF_THREADS), 0, st, Q);
         if (tiles) hipLaunchKernelGGL(k_points_count, dim3(tiles), dim3(256), 0, st, D.pend, D.pcnt, D.prem, D.tot);
         HIPCHK(hipGetLastError());
-        unsigned long long tot[64];
-        HIPCHK(hipMemcpyAsync(tot, D.tot, sizeof tot, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        if (tot[63] != 0) return DEC_SERIAL;                                // a segment is not what the index says
-        if (tot[0] == 0) continue;
-        const uint32_t rounds = dec_ceil_log2(nseg) + 2;                    // a chain has at most one link per segment of a batch
+        unsigned long long tot[ZZ_TOT_SLOTS];
+        if (int rc = dec_read_tot(c, tot, st)) return rc;
+        if (tot[ZZ_TOT_FAILED] != 0) return DEC_SERIAL;                     // a segment is not what the index says
+        if (tot[ZZ_TOT_PENDING] == 0) continue;
+        const uint32_t rounds = zz_inf_rounds(nseg);                        // a chain has at most one link per segment of a batch
         zz_res_params R{ dst, base, ZI_POINTS_TILE, tiles, words, D.st, D.pend, D.pcnt, D.prem, D.tot };
         for (uint32_t r = 1; r <= rounds; ++r) hipLaunchKernelGGL(k_inflate_resolve, dim3(tiles), dim3(ZZ_INF_RES_THREADS), 0, st, R, r);
         HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(tot, D.tot, sizeof tot, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        if (tot[1 + rounds] != 0) return DEC_SERIAL;                        // (cannot happen: the rounds suffice for any chain)
+        if (int rc = dec_read_tot(c, tot, st)) return rc;
+        if (tot[ZZ_TOT_OPEN + rounds] != 0) return DEC_SERIAL;              // (cannot happen: the rounds suffice for any chain)
         uint32_t r = 1;
-        while (r < rounds && tot[1 + r] != 0) ++r;
-        pending += tot[0];
+        while (r < rounds && tot[ZZ_TOT_OPEN + r] != 0) ++r;
+        pending += tot[ZZ_TOT_PENDING];
         rounds_used = std::max(rounds_used, r);
     }
     D.last_pending = pending; D.last_rounds = rounds_used;
@@ -1341,7 +1407,7 @@ extern "C" int zz_decode_points_device(zz_ctx* c, const void* d_src_v, uint64_t 
 {
     if (!c || !out_len) { set_err("null argument"); return ZZ_E_ARG; }
     *out_len = 0;
-    if (format < ZZ_ZLIB || format > ZZ_DEFLATE) { set_err("format must be ZZ_ZLIB, ZZ_GZIP or ZZ_DEFLATE"); return ZZ_E_ARG; }
+    if (!dec_format_ok(format)) return ZZ_E_ARG;
     if (!d_src_v || (!d_dst_v && cap)) { set_err("null buffer"); return ZZ_E_ARG; }
     if (!points || entries < 2) { set_err("a point index has at least two rows (host memory)"); return ZZ_E_ARG; }
     if (call_pending(c)) return ZZ_E_ARG;
@@ -1350,9 +1416,7 @@ extern "C" int zz_decode_points_device(zz_ctx* c, const void* d_src_v, uint64_t 
     HIPCHK(hipSetDevice(c->device));
     hipStream_t st = (hipStream_t)hip_stream;
     auto& D = c->dec;
-    D.last_path = 0; D.last_pending = 0; D.last_rounds = 0; D.last_index.clear();
-    if (int rc = D.tot.grow(64)) return rc;
-    if (int rc = D.ok.grow(1)) return rc;
+    if (int rc = begin_decode_call(c)) return rc;
     int64_t hl = 0;
     if (int rc = dec_container(d_src, src_len, format, st, &hl)) return rc;
     const uint64_t tl = (uint64_t)trailer_len(format);
@@ -1374,33 +1438,6 @@ extern "C" int zz_decode_points_device(zz_ctx* c, const void* d_src_v, uint64_t 
 // but the last go to d_dst at once (such a batch holds full packets only), the last batch's after the host has seen the
 // attempt's counters: *ext = external bytes inside the window (then nothing more is copied: the caller tries again),
 // *m = the bytes the range holds.
-// A checked read's sidecar (zz_inflate_check.h); cks == nullptr: the unchecked call.
-struct dec_sidecar { const uint32_t* cks; uint64_t L; int kind; };
-
-// what the checked calls refuse before anything is launched, on top of the unchecked calls' own
-static int dec_sidecar_args(const uint32_t* d_cks, uint64_t total_len, uint64_t entries, uint32_t P)
-{
-    if (!d_cks) { set_err("null argument"); return ZZ_E_ARG; }
-    if (entries - 1 > 0x7fffffffull) { set_err("at most 2^31 - 1 packets"); return ZZ_E_ARG; }
-    if (entries - 1 != zi_sidecar_entries(total_len, P)) { set_err("the index's packets are not total_len's: entries - 1 != max(1, ceil(total_len / packet_size))"); return ZZ_E_ARG; }
-    return ZZ_OK;
-}
-// The sidecar against the stream's trailer, enqueued: unpack, fold, verdict. The caller reads D.verdict[0] (1: it holds) with its
-// next wait. A raw stream has no trailer: nothing is launched, and nothing is read.
-static int dec_sidecar_fold(zz_ctx* c, const dec_sidecar& sc, uint64_t npk, uint32_t P, int format, const uint8_t* trailer, hipStream_t st)
-{
-    auto& D = c->dec;
-    if (format == ZZ_DEFLATE) return ZZ_OK;
-    if (int rc = D.side.grow(npk)) return rc;
-    if (int rc = D.side_total.grow(1)) return rc;
-    if (int rc = D.verdict.grow(2)) return rc;
-    HIPCHK(hipMemsetAsync(D.verdict, 0, 8, st));
-    hipLaunchKernelGGL(k_sidecar_unpack, dim3((uint32_t)((npk + 255) / 256)), dim3(256), 0, st, sc.cks, (uint32_t)npk, P, sc.L, sc.kind, D.side.p, D.verdict.p);
-    hipLaunchKernelGGL(k_cks_reduce, dim3(1), dim3(ZZ_RED_THREADS), 0, st, D.side.p, (uint32_t)npk, P, sc.L, sc.kind, D.side_total.p);
-    hipLaunchKernelGGL(k_sidecar_verdict, dim3(1), dim3(1), 0, st, trailer, format, D.side_total.p, sc.L, D.verdict.p);
-    HIPCHK(hipGetLastError());
-    return ZZ_OK;
-}
 // Stage packets [0, n) at `stage` (phase 1's words at `stat`) summed into D.scks: the MAP forms of zz_checksum.h's bodies.
 static void dec_stage_sums(zz_ctx* c, const dec_sidecar& sc, const uint8_t* stage, const uint32_t* stat, const zi_read_desc* desc, uint32_t n,
                            uint32_t P, hipStream_t st)
@@ -1412,63 +1449,54 @@ static void dec_stage_sums(zz_ctx* c, const dec_sidecar& sc, const uint8_t* stag
     else hipLaunchKernelGGL(k_adler_stage, dim3(n < 16384 ? n : 16384), dim3(ZZ_WAVE), 0, st, pp, M);
 }
 
-static int dec_range_attempt(zz_ctx* c, const uint8_t* s, uint64_t sn, const uint64_t* d_index, uint64_t npk, uint32_t P,
-                             uint64_t kb, uint64_t k1, uint64_t first, uint64_t nbytes, uint8_t* dst, uint64_t cap, hipStream_t st,
-                             const dec_sidecar& sc, uint64_t* ext, uint64_t* pending, uint64_t* m, uint64_t* bad)
+static int dec_range_attempt(zz_ctx* c, const dec_stream& S, uint64_t kb, uint64_t k1, uint64_t first, uint64_t nbytes, uint8_t* dst,
+                             uint64_t cap, hipStream_t st, const dec_sidecar* sc, uint64_t* ext, uint64_t* pending, uint64_t* m, uint64_t* bad)
 {
     auto& D = c->dec;
-    const uint32_t words = ((P + 31) / 32 + 3) & ~3u;
-    uint64_t B = ZZ_INF_BATCH_BYTES / P;
-    if (B > ZZ_INF_BATCH_PACKETS) B = ZZ_INF_BATCH_PACKETS;
-    if (B > k1 - kb) B = k1 - kb;
+    const uint32_t P = S.P;
+    const uint64_t npk = S.npk;
+    const zz_inf_geom geo = zz_inf_geometry(P, k1 - kb);
+    const uint64_t B = geo.B;
     if (int rc = D.stage.grow(ZI_BIAS + B * P + 16)) return rc;
-    if (int rc = D.st.grow(B * P)) return rc;
-    if (int rc = D.pend.grow(B * words)) return rc;
-    if (int rc = D.pcnt.grow(B)) return rc;
-    if (int rc = D.prem.grow(B)) return rc;
-    if (int rc = D.ends.grow(B)) return rc;
-    if (int rc = D.stat.grow(B)) return rc;
-    if (sc.cks) if (int rc = D.scks.grow(B)) return rc;
-    HIPCHK(hipMemsetAsync(D.tot, 0, 64 * sizeof(unsigned long long), st));
+    if (int rc = dec_batch_workspace(c, B, B * P, geo.words, B)) return rc;
+    if (sc) if (int rc = D.scks.grow(B)) return rc;
+    HIPCHK(hipMemsetAsync(D.tot, 0, ZZ_TOT_SLOTS * sizeof(unsigned long long), st));
     HIPCHK(hipMemsetAsync(D.xcarry, 0xFF, ZI_BIAS / 8, st));   // the first batch: whatever lies below it is external
-    const uint32_t rounds = dec_ceil_log2(B) + 2;
-    const size_t lds = (size_t)words * 4 + ZZ_INF_IBUF + ((P + 15) & ~15u);
+    const uint32_t rounds = zz_inf_rounds(B);
     const uint64_t k0 = first / P;
     const uint64_t wend = nbytes < k1 * P - first ? first + nbytes : k1 * P;       // the window's end, as far as packets go
     uint64_t xlo = 0, xhi = 0;                                  // where an external byte sends the call back: the window, or its packets whole
-    zi_checked_window(sc.cks != nullptr, first, nbytes, P, k0, k1, &xlo, &xhi);
+    zi_checked_window(sc != nullptr, first, nbytes, P, k0, k1, &xlo, &xhi);
+    zz_inf_params Q = dec_inf_params(c, S, geo.words);
+    Q.mode = ZZ_INF_INDEXED; Q.dst = D.stage + ZI_BIAS;
     for (uint64_t kf = kb; kf < k1; kf += B) {
         const uint32_t nb = (uint32_t)(k1 - kf < B ? k1 - kf : B);
         const uint64_t base = kf * P;
-        zz_inf_params Q;
-        Q.s = s; Q.sn = sn; Q.starts = d_index; Q.nstarts = npk + 1; Q.k0 = kf; Q.npk = nb; Q.npk_total = npk;
-        Q.P = P; Q.mode = ZZ_INF_INDEXED; Q.dst = D.stage + ZI_BIAS; Q.cap = (uint64_t)nb * P;
-        Q.st = D.st; Q.pend = D.pend; Q.words = words; Q.pcnt = D.pcnt; Q.prem = D.prem; Q.ends = D.ends; Q.stat = D.stat; Q.tot = D.tot;
-        Q.ebase = kf;
-        hipLaunchKernelGGL(k_inflate_packets_range, dim3(nb), dim3(ZZ_INF_THREADS), lds, st, Q);
-        zz_res_params R{ D.stage, ZI_BIAS, P, nb, words, D.st, D.pend, D.pcnt, D.prem, D.tot };
+        Q.k0 = kf; Q.npk = nb; Q.cap = (uint64_t)nb * P; Q.ebase = kf;
+        hipLaunchKernelGGL(k_inflate_packets_range, dim3(nb), dim3(ZZ_INF_THREADS), geo.lds, st, Q);
+        zz_res_params R{ D.stage, ZI_BIAS, P, nb, geo.words, D.st, D.pend, D.pcnt, D.prem, D.tot };
         zz_res_range X{ D.xcarry, (int64_t)xlo - (int64_t)base, (int64_t)xhi - (int64_t)base };
         for (uint32_t r = 1; r <= rounds; ++r) hipLaunchKernelGGL(k_inflate_resolve_range, dim3(nb), dim3(ZZ_INF_RES_THREADS), 0, st, R, X, r);
-        if (sc.cks && kf + nb > k0) {                               // the batch's touched packets: summed, held to the sidecar (tot[60])
-            const uint32_t g = (uint32_t)(k0 > kf ? k0 - kf : 0), n = nb - g;
-            dec_stage_sums(c, sc, D.stage + ZI_BIAS + (uint64_t)g * P, D.stat + g, nullptr, n, P, st);
-            zz_chk_params C{ sc.cks, npk, sc.L, P, sc.kind, D.scks.p, D.stat + g };
-            hipLaunchKernelGGL(k_stage_check_range, dim3((n + 255) / 256), dim3(256), 0, st, C, kf + g, n, D.tot + 60);
+        if (sc && kf + nb > k0) {                                   // the batch's touched packets: summed, held to the sidecar (ZZ_TOT_BAD_SUM)
+            const uint32_t skip = (uint32_t)(k0 > kf ? k0 - kf : 0), n = nb - skip;
+            dec_stage_sums(c, *sc, D.stage + ZI_BIAS + (uint64_t)skip * P, D.stat + skip, nullptr, n, P, st);
+            zz_chk_params C{ sc->cks, npk, sc->L, P, sc->kind, D.scks.p, D.stat + skip };
+            hipLaunchKernelGGL(k_stage_check_range, dim3((n + 255) / 256), dim3(256), 0, st, C, kf + skip, n, D.tot + ZZ_TOT_BAD_SUM);
         }
         // this batch's share of the window: stream bytes [lo, hi)
         const uint64_t lo = first > base ? first : base;
         uint64_t hi = base + (uint64_t)nb * P < wend ? base + (uint64_t)nb * P : wend;
         const bool last = kf + nb == k1;
         if (last) {
-            unsigned long long tot[64];
+            unsigned long long tot[ZZ_TOT_SLOTS];
             uint32_t stat = 0;
             HIPCHK(hipGetLastError());
-            HIPCHK(hipMemcpyAsync(tot, D.tot, sizeof tot, hipMemcpyDeviceToHost, st));
+            HIPCHK(hipMemcpyAsync(tot, D.tot, sizeof tot, hipMemcpyDeviceToHost, st));     // (not dec_read_tot: the last packet's word rides behind it)
             HIPCHK(hipMemcpyAsync(&stat, D.stat + (nb - 1), 4, hipMemcpyDeviceToHost, st));
             HIPCHK(hipStreamSynchronize(st));
-            if (tot[63] != 0) { set_err("not a valid stream of the requested format: " + std::to_string(tot[63]) + " of the range's packets do not decode as the index says"); return ZZ_E_DATA; }
-            if (tot[1 + rounds] != 0) { set_err("pending bytes left unresolved"); return ZZ_E_DATA; }   // (cannot happen: the rounds suffice for any chain)
-            *ext = tot[61]; *pending = tot[0]; *bad = tot[60];
+            if (tot[ZZ_TOT_FAILED] != 0) { set_err("not a valid stream of the requested format: " + std::to_string(tot[ZZ_TOT_FAILED]) + " of the range's packets do not decode as the index says"); return ZZ_E_DATA; }
+            if (tot[ZZ_TOT_OPEN + rounds] != 0) { set_err("pending bytes left unresolved"); return ZZ_E_DATA; }   // (cannot happen: the rounds suffice for any chain)
+            *ext = tot[ZZ_TOT_EXTERNAL]; *pending = tot[ZZ_TOT_PENDING]; *bad = tot[ZZ_TOT_BAD_SUM];
             uint64_t have = nbytes;                                 // bytes of the stream from `first` on, if its end is in sight
             if (k1 == npk) { const uint64_t L = (npk - 1) * (uint64_t)P + (stat >> 3); have = L > first ? L - first : 0; }
             *m = nbytes < have ? nbytes : have;
@@ -1483,7 +1511,7 @@ static int dec_range_attempt(zz_ctx* c, const uint8_t* s, uint64_t sn, const uin
             if (g == 0) g = 1;
             hipLaunchKernelGGL(k_inflate_range_copy, dim3((uint32_t)g), dim3(256), 0, st, D.stage + ZI_BIAS + (lo - base), dst + (lo - first), n);
         }
-        if (!last) hipLaunchKernelGGL(k_inflate_range_carry, dim3(ZI_BIAS / 256), dim3(256), 0, st, D.stage.p, (uint64_t)nb * P, P, words,
+        if (!last) hipLaunchKernelGGL(k_inflate_range_carry, dim3(ZI_BIAS / 256), dim3(256), 0, st, D.stage.p, (uint64_t)nb * P, P, geo.words,
                                       D.st.p, D.pend.p, D.pcnt.p, D.xcarry.p);
     }
     HIPCHK(hipGetLastError());
@@ -1491,22 +1519,20 @@ static int dec_range_attempt(zz_ctx* c, const uint8_t* s, uint64_t sn, const uin
     return ZZ_OK;
 }
 
-// zz_decode_range_device (checked == false: d_cks and total_len are not looked at) and zz_decode_range_checked_device: one body
+// zz_decode_range_device (sc == nullptr) and zz_decode_range_checked_device: one body
 static int dec_range(zz_ctx* c, const void* d_src_v, uint64_t src_len, int format, uint32_t P,
-                     const uint64_t* d_index, uint64_t entries, bool checked, const uint32_t* d_cks, uint64_t total_len,
+                     const uint64_t* d_index, uint64_t entries, const dec_sidecar* sc,
                      uint64_t first, uint64_t nbytes, void* d_dst_v, uint64_t cap, uint64_t* out_len, void* hip_stream)
 {
     if (!c || !d_src_v || !d_index || !out_len) { set_err("null argument"); return ZZ_E_ARG; }
     *out_len = 0;
-    if (P < 1 || P > ZZ_MAX_PACKET_SIZE) { set_err("packet size must be 1..32768"); return ZZ_E_ARG; }
-    if (format < ZZ_ZLIB || format > ZZ_DEFLATE) { set_err("format must be ZZ_ZLIB, ZZ_GZIP or ZZ_DEFLATE"); return ZZ_E_ARG; }
+    if (!dec_packet_ok(P, 1) || !dec_format_ok(format)) return ZZ_E_ARG;
     if (entries < 2) { set_err("the index needs at least two entries (packets + 1)"); return ZZ_E_ARG; }
     const uint64_t npk = entries - 1;
     if (first / P >= npk) { set_err("the range starts behind the index's last packet"); return ZZ_E_ARG; }
     if (first + nbytes < first) { set_err("first + nbytes overflows"); return ZZ_E_ARG; }
     if (!d_dst_v && cap) { set_err("null buffer"); return ZZ_E_ARG; }
-    if (checked) if (int rc = dec_sidecar_args(d_cks, total_len, entries, P)) return rc;
-    const dec_sidecar sc{ checked ? d_cks : nullptr, total_len, zi_sidecar_kind(format) };
+    if (sc) if (int rc = dec_sidecar_args(*sc, entries, P)) return rc;
     if (nbytes == 0) return ZZ_OK;                                  // nothing to do: the context is not looked at
     if (call_pending(c)) return ZZ_E_ARG;
     const uint8_t* d_src = (const uint8_t*)d_src_v;
@@ -1514,25 +1540,15 @@ static int dec_range(zz_ctx* c, const void* d_src_v, uint64_t src_len, int forma
     HIPCHK(hipSetDevice(c->device));
     hipStream_t st = (hipStream_t)hip_stream;
     auto& D = c->dec;
-    if (int rc = D.tot.grow(64)) return rc;
+    if (int rc = D.tot.grow(ZZ_TOT_SLOTS)) return rc;
     if (int rc = D.xcarry.grow(ZI_BIAS / 32)) return rc;
     int64_t hl = 0;
     if (int rc = dec_container(d_src, src_len, format, st, &hl)) return rc;
-    const uint8_t* s = d_src + hl;
-    const uint64_t sn = src_len - hl - (uint64_t)trailer_len(format);
-    uint64_t ends[2];
-    uint32_t holds = 1;                                             // the sidecar folds to the trailer (read with the index's ends)
-    if (sc.cks) if (int rc = dec_sidecar_fold(c, sc, npk, P, format, s + sn, st)) return rc;
-    HIPCHK(hipMemcpyAsync(&ends[0], d_index, 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(&ends[1], d_index + npk, 8, hipMemcpyDeviceToHost, st));
-    if (sc.cks && format != ZZ_DEFLATE) HIPCHK(hipMemcpyAsync(&holds, D.verdict.p, 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    if (ends[0] != 0 || ends[1] != sn) { set_err("the index does not describe this stream: its ends are not the DEFLATE bytes' ends"); return ZZ_E_DATA; }
-    if (holds != 1) {
-        *out_len = ~0ull;
-        set_err("the packet checksums do not describe this stream: they do not fold to its trailer (checksum or length)");
-        return ZZ_E_DATA;
-    }
+    const dec_stream S{ d_src + hl, src_len - hl - (uint64_t)trailer_len(format), d_index, entries, npk, P };
+    const int front = dec_index_front(c, S, sc, st);
+    if (front < 0) return front;
+    if (front == DEC_FRONT_SIDECAR) *out_len = ~0ull;
+    if (front) return dec_front_refused(front);
     const uint64_t k0 = first / P;
     const uint64_t lastk = (first + nbytes - 1) / P;
     const uint64_t k1 = lastk + 1 < npk ? lastk + 1 : npk;
@@ -1540,8 +1556,8 @@ static int dec_range(zz_ctx* c, const void* d_src_v, uint64_t src_len, int forma
     for (uint32_t tries = 1;; ++tries) {
         const uint64_t kb = k0 - h;
         uint64_t ext = 0, pending = 0, m = 0, bad = 0;
-        if (int rc = dec_range_attempt(c, s, sn, d_index, npk, P, kb, k1, first, nbytes, d_dst, cap, st, sc, &ext, &pending, &m, &bad)) {
-            if (checked && rc == ZZ_E_DATA) *out_len = ~0ull;
+        if (int rc = dec_range_attempt(c, S, kb, k1, first, nbytes, d_dst, cap, st, sc, &ext, &pending, &m, &bad)) {
+            if (sc && rc == ZZ_E_DATA) *out_len = ~0ull;
             return rc;
         }
         if (ext != 0) {
@@ -1569,13 +1585,14 @@ extern "C" int zz_decode_range_device(zz_ctx* c, const void* d_src_v, uint64_t s
                                       const uint64_t* d_index, uint64_t entries, uint64_t first, uint64_t nbytes,
                                       void* d_dst_v, uint64_t cap, uint64_t* out_len, void* hip_stream)
 {
-    return dec_range(c, d_src_v, src_len, format, P, d_index, entries, false, nullptr, 0, first, nbytes, d_dst_v, cap, out_len, hip_stream);
+    return dec_range(c, d_src_v, src_len, format, P, d_index, entries, nullptr, first, nbytes, d_dst_v, cap, out_len, hip_stream);
 }
 extern "C" int zz_decode_range_checked_device(zz_ctx* c, const void* d_src_v, uint64_t src_len, int format, uint32_t P,
                                               const uint64_t* d_index, uint64_t entries, const uint32_t* d_cks, uint64_t total_len,
                                               uint64_t first, uint64_t nbytes, void* d_dst_v, uint64_t cap, uint64_t* out_len, void* hip_stream)
 {
-    return dec_range(c, d_src_v, src_len, format, P, d_index, entries, true, d_cks, total_len, first, nbytes, d_dst_v, cap, out_len, hip_stream);
+    const dec_sidecar sc{ d_cks, total_len, zi_sidecar_kind(format), format };
+    return dec_range(c, d_src_v, src_len, format, P, d_index, entries, &sc, first, nbytes, d_dst_v, cap, out_len, hip_stream);
 }
 
 extern "C" int zz_ctx_last_decode_range_stats(const zz_ctx* c, uint64_t* first_packet, uint64_t* packets, uint32_t* attempts,
@@ -1593,21 +1610,19 @@ extern "C" int zz_ctx_last_decode_range_stats(const zz_ctx* c, uint64_t* first_p
 // A read's own failure is worded "reads: ..." in zz_last_error (the Python layer tells it from a failure of the call by that).
 // Per attempt: the plan, one wait for its totals and wave table, then per wave descriptors, phase 1, the rounds, the verdict and
 // the copy, nothing of which the host waits for; the next attempt's plan finds what is left.
-// zz_decode_ranges_device (checked == false: d_cks and total_len are not looked at) and zz_decode_ranges_checked_device: one body
+// zz_decode_ranges_device (sc == nullptr) and zz_decode_ranges_checked_device: one body
 static_assert(ZI_CKS_ADLER == ZZ_CKS_ADLER && ZI_CKS_CRC == ZZ_CKS_CRC, "the sidecar's kinds are the checksum kernels'");
 static int dec_ranges(zz_ctx* c, const void* d_src_v, uint64_t src_len, int format, uint32_t P,
-                      const uint64_t* d_index, uint64_t entries, bool checked, const uint32_t* d_cks, uint64_t total_len,
+                      const uint64_t* d_index, uint64_t entries, const dec_sidecar* sc,
                       uint64_t nranges, const uint64_t* d_firsts, const uint64_t* d_nbytes,
                       void* const* d_dsts, const uint64_t* d_caps,
                       uint64_t* d_out_lens, int32_t* d_status, void* hip_stream)
 {
     if (!c || !d_src_v || !d_index || !d_firsts || !d_nbytes || !d_dsts || !d_caps || !d_out_lens) { set_err("null argument"); return ZZ_E_ARG; }
-    if (P < 1 || P > ZZ_MAX_PACKET_SIZE) { set_err("packet size must be 1..32768"); return ZZ_E_ARG; }
-    if (format < ZZ_ZLIB || format > ZZ_DEFLATE) { set_err("format must be ZZ_ZLIB, ZZ_GZIP or ZZ_DEFLATE"); return ZZ_E_ARG; }
+    if (!dec_packet_ok(P, 1) || !dec_format_ok(format)) return ZZ_E_ARG;
     if (entries < 2) { set_err("the index needs at least two entries (packets + 1)"); return ZZ_E_ARG; }
     if (nranges > 0x7fffffffull) { set_err("at most 2^31 - 1 reads per call"); return ZZ_E_ARG; }
-    if (checked) if (int rc = dec_sidecar_args(d_cks, total_len, entries, P)) return rc;
-    const dec_sidecar sc{ checked ? d_cks : nullptr, total_len, zi_sidecar_kind(format) };
+    if (sc) if (int rc = dec_sidecar_args(*sc, entries, P)) return rc;
     if (nranges == 0) return ZZ_OK;                                 // nothing to do: the context is not looked at
     if (call_pending(c)) return ZZ_E_ARG;
     const uint64_t npk = entries - 1;
@@ -1629,33 +1644,17 @@ static int dec_ranges(zz_ctx* c, const void* d_src_v, uint64_t src_len, int form
         if (rc == ZZ_E_DATA || rc == ZZ_E_UNSUPPORTED) return fail_all(rc);
         return rc;
     }
-    const uint8_t* s = d_src + hl;
-    const uint64_t sn = src_len - hl - (uint64_t)trailer_len(format);
-    uint64_t ends[2];
-    uint32_t holds = 1;                                             // the sidecar folds to the trailer (read with the index's ends)
-    if (sc.cks) if (int rc = dec_sidecar_fold(c, sc, npk, P, format, s + sn, st)) return rc;
-    HIPCHK(hipMemcpyAsync(&ends[0], d_index, 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(&ends[1], d_index + npk, 8, hipMemcpyDeviceToHost, st));
-    if (sc.cks && format != ZZ_DEFLATE) HIPCHK(hipMemcpyAsync(&holds, D.verdict.p, 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    if (ends[0] != 0 || ends[1] != sn) {
-        set_err("the index does not describe this stream: its ends are not the DEFLATE bytes' ends");
-        return fail_all(ZZ_E_DATA);
-    }
-    if (holds != 1) {
-        set_err("the packet checksums do not describe this stream: they do not fold to its trailer (checksum or length)");
-        return fail_all(ZZ_E_DATA);
-    }
-    if (int rc = D.tot.grow(64)) return rc;
+    const dec_stream S{ d_src + hl, src_len - hl - (uint64_t)trailer_len(format), d_index, entries, npk, P };
+    const int front = dec_index_front(c, S, sc, st);
+    if (front < 0) return front;
+    if (front) return fail_all(dec_front_refused(front));
+    if (int rc = D.tot.grow(ZZ_TOT_SLOTS)) return rc;
     if (int rc = D.rng_reads.grow(nranges)) return rc;
     if (int rc = D.rng_tot.grow(1)) return rc;
     if (int rc = D.rng_host.grow(1)) return rc;
-    const uint32_t words = ((P + 31) / 32 + 3) & ~3u;
-    uint64_t B = ZZ_INF_BATCH_BYTES / P;
-    if (B > ZZ_INF_BATCH_PACKETS) B = ZZ_INF_BATCH_PACKETS;
-    zz_rng_params Q{ d_firsts, d_nbytes, (uint8_t* const*)d_dsts, d_caps, d_out_lens, d_status, nranges, npk, P, B, B, D.rng_reads, D.rng_tot,
-                     sc.cks, sc.L };
-    const size_t lds = (size_t)words * 4 + ZZ_INF_IBUF + ((P + 15) & ~15u);
+    const zz_inf_geom geo = zz_inf_geometry(P, ~0ull);
+    zz_rng_params Q{ d_firsts, d_nbytes, (uint8_t* const*)d_dsts, d_caps, d_out_lens, d_status, nranges, npk, P, geo.B, geo.B, D.rng_reads, D.rng_tot,
+                     sc ? sc->cks : nullptr, sc ? sc->L : 0 };
     const zz_rng_totals& T = *D.rng_host.p;
     for (uint32_t tries = 1;; ++tries) {
         hipLaunchKernelGGL(k_ranges_plan, dim3(1), dim3(ZZ_RNG_PLAN_THREADS), 0, st, Q, tries == 1 ? 1 : 0);
@@ -1667,7 +1666,7 @@ static int dec_ranges(zz_ctx* c, const void* d_src_v, uint64_t src_len, int form
             break;
         }
         D.ranges.attempts = tries; D.ranges.packets += T.stage_end;
-        const uint32_t rounds = dec_ceil_log2(T.longest) + 2;
+        const uint32_t rounds = zz_inf_rounds(T.longest);
         // the workspace follows the attempt's largest wave (nothing is grown while a wave's kernels run)
         uint64_t big = 0, prev = T.stage_end;
         for (uint64_t w = T.nwaves; w-- > 0;) {
@@ -1676,14 +1675,11 @@ static int dec_ranges(zz_ctx* c, const void* d_src_v, uint64_t src_len, int form
             prev = T.wave_first[w];
         }
         if (int rc = D.stage.grow(big * P + 16)) return rc;
-        if (int rc = D.st.grow(big * P)) return rc;
-        if (int rc = D.pend.grow(big * words)) return rc;
-        if (int rc = D.pcnt.grow(big)) return rc;
-        if (int rc = D.prem.grow(big)) return rc;
-        if (int rc = D.ends.grow(big)) return rc;
-        if (int rc = D.stat.grow(big)) return rc;
+        if (int rc = dec_batch_workspace(c, big, big * P, geo.words, big)) return rc;
         if (int rc = D.rng_desc.grow(big)) return rc;
-        if (sc.cks) if (int rc = D.scks.grow(big)) return rc;
+        if (sc) if (int rc = D.scks.grow(big)) return rc;
+        zz_inf_params I = dec_inf_params(c, S, geo.words);      // (k0 = 0, ebase = 0: a wave's packets are its descriptors')
+        I.mode = ZZ_INF_INDEXED; I.dst = D.stage;
         for (uint64_t w = 0; w < T.nwaves; ++w) {
             if (T.wave_first[w] == ~0ull) continue;                 // (a segment longer than a wave's capacity went over it)
             uint64_t nx = w + 1;
@@ -1693,18 +1689,14 @@ static int dec_ranges(zz_ctx* c, const void* d_src_v, uint64_t src_len, int form
             const uint32_t nb = (uint32_t)(g1 - g0);                // < 2 * B, <= big
             ++D.ranges.waves;
             hipLaunchKernelGGL(k_ranges_desc, dim3((nb + 255) / 256), dim3(256), 0, st, Q, g0, nb, rlo, rhi, D.rng_desc.p);
-            zz_inf_params I;
-            I.s = s; I.sn = sn; I.starts = d_index; I.nstarts = npk + 1; I.k0 = 0; I.npk = nb; I.npk_total = npk;
-            I.P = P; I.mode = ZZ_INF_INDEXED; I.dst = D.stage; I.cap = (uint64_t)nb * P;
-            I.st = D.st; I.pend = D.pend; I.words = words; I.pcnt = D.pcnt; I.prem = D.prem; I.ends = D.ends; I.stat = D.stat; I.tot = D.tot;
-            I.ebase = 0;
+            I.npk = nb; I.cap = (uint64_t)nb * P;
             zz_inf_ranges X{ D.rng_desc.p, D.rng_reads.p };
-            hipLaunchKernelGGL(k_inflate_packets_ranges, dim3(nb), dim3(ZZ_INF_THREADS), lds, st, I, X);
-            zz_res_params R{ D.stage, 0, P, nb, words, D.st, D.pend, D.pcnt, D.prem, D.tot };
+            hipLaunchKernelGGL(k_inflate_packets_ranges, dim3(nb), dim3(ZZ_INF_THREADS), geo.lds, st, I, X);
+            zz_res_params R{ D.stage, 0, P, nb, geo.words, D.st, D.pend, D.pcnt, D.prem, D.tot };
             for (uint32_t r = 1; r <= rounds; ++r) hipLaunchKernelGGL(k_inflate_resolve_ranges, dim3(nb), dim3(ZZ_INF_RES_THREADS), 0, st, R, X, r);
-            if (sc.cks) {                                           // the wave's touched packets: summed, a mismatch charged to the read
-                dec_stage_sums(c, sc, D.stage, D.stat, D.rng_desc.p, nb, P, st);
-                zz_chk_params C{ sc.cks, npk, sc.L, P, sc.kind, D.scks.p, D.stat.p };
+            if (sc) {                                               // the wave's touched packets: summed, a mismatch charged to the read
+                dec_stage_sums(c, *sc, D.stage, D.stat, D.rng_desc.p, nb, P, st);
+                zz_chk_params C{ sc->cks, npk, sc->L, P, sc->kind, D.scks.p, D.stat.p };
                 hipLaunchKernelGGL(k_stage_check_ranges, dim3((nb + 255) / 256), dim3(256), 0, st, C, D.rng_desc.p, nb, D.rng_reads.p);
             }
             hipLaunchKernelGGL(k_ranges_verdict, dim3((uint32_t)((rhi - rlo + 255) / 256)), dim3(256), 0, st, Q, g0, rlo, rhi, D.stat.p);
@@ -1714,7 +1706,7 @@ static int dec_ranges(zz_ctx* c, const void* d_src_v, uint64_t src_len, int form
     }
     D.ranges.retried = T.retried;
     if (T.n_data) {
-        set_err("reads: " + std::to_string(T.n_data) + " met a packet that does not decode as the index says" + (checked ? " or as its checksum says" : ""));
+        set_err("reads: " + std::to_string(T.n_data) + " met a packet that does not decode as the index says" + (sc ? " or as its checksum says" : ""));
         return ZZ_E_DATA;
     }
     if (T.n_unsupported) { set_err("reads: " + std::to_string(T.n_unsupported) + " need more than one batch of packets: use zz_decode_range_device"); return ZZ_E_UNSUPPORTED; }
@@ -1729,7 +1721,7 @@ extern "C" int zz_decode_ranges_device(zz_ctx* c, const void* d_src_v, uint64_t 
                                        void* const* d_dsts, const uint64_t* d_caps,
                                        uint64_t* d_out_lens, int32_t* d_status, void* hip_stream)
 {
-    return dec_ranges(c, d_src_v, src_len, format, P, d_index, entries, false, nullptr, 0, nranges, d_firsts, d_nbytes, d_dsts, d_caps,
+    return dec_ranges(c, d_src_v, src_len, format, P, d_index, entries, nullptr, nranges, d_firsts, d_nbytes, d_dsts, d_caps,
                       d_out_lens, d_status, hip_stream);
 }
 extern "C" int zz_decode_ranges_checked_device(zz_ctx* c, const void* d_src_v, uint64_t src_len, int format, uint32_t P,
@@ -1738,7 +1730,8 @@ extern "C" int zz_decode_ranges_checked_device(zz_ctx* c, const void* d_src_v, u
                                                void* const* d_dsts, const uint64_t* d_caps,
                                                uint64_t* d_out_lens, int32_t* d_status, void* hip_stream)
 {
-    return dec_ranges(c, d_src_v, src_len, format, P, d_index, entries, true, d_cks, total_len, nranges, d_firsts, d_nbytes, d_dsts, d_caps,
+    const dec_sidecar sc{ d_cks, total_len, zi_sidecar_kind(format), format };
+    return dec_ranges(c, d_src_v, src_len, format, P, d_index, entries, &sc, nranges, d_firsts, d_nbytes, d_dsts, d_caps,
                       d_out_lens, d_status, hip_stream);
 }
 
@@ -1747,8 +1740,7 @@ extern "C" int zz_packet_checksums_device(zz_ctx* c, const void* d_data, uint64_
                                           uint32_t* d_cks, uint64_t max_entries, uint64_t* entries, void* hip_stream)
 {
     if (!c || !entries || !d_cks || (!d_data && n)) { set_err("null argument"); return ZZ_E_ARG; }
-    if (P < 1 || P > ZZ_MAX_PACKET_SIZE) { set_err("packet size must be 1..32768"); return ZZ_E_ARG; }
-    if (format < ZZ_ZLIB || format > ZZ_DEFLATE) { set_err("format must be ZZ_ZLIB, ZZ_GZIP or ZZ_DEFLATE"); return ZZ_E_ARG; }
+    if (!dec_packet_ok(P, 1) || !dec_format_ok(format)) return ZZ_E_ARG;
     const uint64_t npk = zi_sidecar_entries(n, P);
     if (npk > 0x7fffffffull) { set_err("at most 2^31 - 1 packets"); return ZZ_E_ARG; }
     *entries = npk;
@@ -2342,13 +2334,31 @@ static int dec_items(zz_ctx* c, zz_inf_items_params q, hipStream_t st)
     HIPCHK(hipStreamSynchronize(st));
     return ZZ_OK;
 }
+// the members of a file as k_inflate_items' items (mem's five descriptor arrays), for zz_decode_members_device and the member reads
+static int ensure_member_items(zz_ctx* c, uint64_t items)
+{
+    auto& M = c->dec.mem;
+    if (int rc = M.srcs.grow(items)) return rc;
+    if (int rc = M.dsts.grow(items)) return rc;
+    if (int rc = M.src_lens.grow(items)) return rc;
+    if (int rc = M.caps.grow(items)) return rc;
+    return M.out_lens.grow(items);
+}
+static zz_inf_items_params member_items_params(zz_ctx* c, uint32_t nitems, int32_t* status)
+{
+    auto& M = c->dec.mem;
+    zz_inf_items_params p;
+    p.srcs = (const uint8_t* const*)M.srcs.p; p.src_lens = M.src_lens; p.dsts = (uint8_t* const*)M.dsts.p; p.caps = M.caps;
+    p.out_lens = M.out_lens; p.status = status; p.nitems = nitems; p.format = ZZ_GZIP;
+    return p;
+}
 extern "C" int zz_decode_batch_device(zz_ctx* c, uint64_t nitems, const void* const* d_srcs, const uint64_t* d_src_lens,
                                       void* const* d_dsts, const uint64_t* d_caps, uint64_t* d_out_lens, int32_t* d_status,
                                       int format, void* hip_stream)
 {
     if (!c) { set_err("null ctx"); return ZZ_E_ARG; }
     if (nitems == 0) return ZZ_OK;
-    if (format < ZZ_ZLIB || format > ZZ_DEFLATE) { set_err("format must be ZZ_ZLIB, ZZ_GZIP or ZZ_DEFLATE"); return ZZ_E_ARG; }
+    if (!dec_format_ok(format)) return ZZ_E_ARG;
     if (call_pending(c)) return ZZ_E_ARG;
     if (!d_srcs || !d_src_lens || !d_dsts || !d_caps || !d_out_lens) { set_err("null array"); return ZZ_E_ARG; }
     if (nitems > 0x7FFFFFFFull) { set_err("too many items for one call"); return ZZ_E_ARG; }
@@ -2464,11 +2474,7 @@ extern "C" int zz_decode_members_device(zz_ctx* c, const void* d_src_v, uint64_t
     if (!listed) return serial();
 
     // slots: one readback for fill, check, hop (only if the check failed) and slots
-    if (int rc = M.srcs.grow(ncand)) return rc;
-    if (int rc = M.dsts.grow(ncand)) return rc;
-    if (int rc = M.src_lens.grow(ncand)) return rc;
-    if (int rc = M.caps.grow(ncand)) return rc;
-    if (int rc = M.out_lens.grow(ncand)) return rc;
+    if (int rc = ensure_member_items(c, ncand)) return rc;
     zz_mem_slots q;
     q.src = src; q.n = src_len; q.dst = dst; q.cap = cap; q.offs = M.offs; q.lens = M.lens;
     q.srcs = M.srcs; q.src_lens = M.src_lens; q.dsts = M.dsts; q.caps = M.caps; q.st = M.st;
@@ -2482,10 +2488,7 @@ extern "C" int zz_decode_members_device(zz_ctx* c, const void* d_src_v, uint64_t
     const uint64_t dealt = have_mstar ? mstar + 1 : members;
 
     // decode: k_inflate_items over the dealt members, as zz_decode_batch_device launches it
-    zz_inf_items_params p;
-    p.srcs = (const uint8_t* const*)M.srcs.p; p.src_lens = M.src_lens; p.dsts = (uint8_t* const*)M.dsts.p; p.caps = M.caps;
-    p.out_lens = M.out_lens; p.status = nullptr; p.nitems = (uint32_t)dealt; p.format = ZZ_GZIP;
-    if (int rc = dec_items(c, p, st)) return rc;
+    if (int rc = dec_items(c, member_items_params(c, (uint32_t)dealt, nullptr), st)) return rc;
     const int v = zi_members_verdict(have_mstar, c->dec.items_host[0], c->dec.items_host[1]);
     if (v == ZI_MEMBERS_SERIAL) return serial();
     const int path = M.h_st->chain_bad ? 2 : 1;
@@ -2607,11 +2610,7 @@ extern "C" int zz_decode_members_ranges_device(zz_ctx* c, const void* d_src_v, u
             big_bytes = std::max(big_bytes, W[2 * w + 3] - W[2 * w + 1]);
         }
         if (int rc = R.stage.grow(big_bytes + 16)) return rc;
-        if (int rc = M.srcs.grow(big_items)) return rc;
-        if (int rc = M.dsts.grow(big_items)) return rc;
-        if (int rc = M.src_lens.grow(big_items)) return rc;
-        if (int rc = M.caps.grow(big_items)) return rc;
-        if (int rc = M.out_lens.grow(big_items)) return rc;
+        if (int rc = ensure_member_items(c, big_items)) return rc;
         if (int rc = R.status.grow(big_items)) return rc;
         Q.stage = R.stage;
         for (uint64_t w = 0; w < nwaves; ++w) {
@@ -2621,10 +2620,7 @@ extern "C" int zz_decode_members_ranges_device(zz_ctx* c, const void* d_src_v, u
             hipLaunchKernelGGL(k_mr_desc, grid(t1 - t0), dim3(256), 0, st, Q, t0, t1, (const uint8_t**)M.srcs.p, (uint64_t*)M.src_lens,
                                (uint8_t**)M.dsts.p, (uint64_t*)M.caps);
             HIPCHK(hipGetLastError());
-            zz_inf_items_params p;
-            p.srcs = (const uint8_t* const*)M.srcs.p; p.src_lens = M.src_lens; p.dsts = (uint8_t* const*)M.dsts.p; p.caps = M.caps;
-            p.out_lens = M.out_lens; p.status = R.status; p.nitems = (uint32_t)(t1 - t0); p.format = ZZ_GZIP;
-            if (int rc = dec_items(c, p, st)) return rc;
+            if (int rc = dec_items(c, member_items_params(c, (uint32_t)(t1 - t0), R.status), st)) return rc;
             hipLaunchKernelGGL(k_mr_judge, dim3(1), dim3(ZZ_MR_SCAN_THREADS), 0, st, Q, t0, t1, (const uint64_t*)M.caps, (const uint64_t*)M.out_lens,
                                (const int32_t*)R.status);
             hipLaunchKernelGGL(k_mr_cut, dim3(1), dim3(ZZ_MR_SCAN_THREADS), 0, st, Q, t0, t1);

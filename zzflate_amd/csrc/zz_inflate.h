@@ -52,6 +52,31 @@ namespace zz {
 
 enum { ZZ_INF_INDEXED = 1, ZZ_INF_DISCOVER = 2 };
 
+// The slots of the counter block `tot` (ZZ_TOT_SLOTS words) that phase 1, phase 2 and the checked reads share with the host
+enum { ZZ_TOT_PENDING = 0,        // pending bytes phase 1 left
+       ZZ_TOT_OPEN = 1,           // [ZZ_TOT_OPEN + r]: bytes still open after round r (1 .. ZZ_INF_MAX_ROUNDS)
+       ZZ_TOT_BAD_SUM = 60,       // checked range read: packets that do not match their checksum (zz_inflate_check.h)
+       ZZ_TOT_EXTERNAL = 61,      // range read: bytes of the window that turned external
+       ZZ_TOT_UNWRITTEN = 62,     // packets decoded but not written (past cap)
+       ZZ_TOT_FAILED = 63,        // packets (points: segments) that do not decode as the index says
+       ZZ_TOT_SLOTS = 64 };
+
+// One batch of packets of P bytes, for the host: bitmap words per packet, packets per batch (`most`: no more than the caller
+// has), phase 1's dynamic LDS (bitmap, staged input, window); and the rounds that settle any chain over n packets (it has at
+// most one link per packet).
+struct zz_inf_geom { uint32_t words; uint64_t B; size_t lds; };
+inline zz_inf_geom zz_inf_geometry(uint32_t P, uint64_t most)
+{
+    zz_inf_geom g;
+    g.words = ((P + 31) / 32 + 3) & ~3u;
+    g.B = ZZ_INF_BATCH_BYTES / P;
+    if (g.B > ZZ_INF_BATCH_PACKETS) g.B = ZZ_INF_BATCH_PACKETS;
+    if (g.B > most) g.B = most;
+    g.lds = (size_t)g.words * 4 + ZZ_INF_IBUF + ((P + 15) & ~15u);
+    return g;
+}
+inline uint32_t zz_inf_rounds(uint64_t n) { uint32_t r = 0; while ((1ull << r) < n) ++r; return r + 2; }
+
 // phase 1: packets [k0, k0 + npk) of the call, `starts` relative to the first DEFLATE byte
 struct zz_inf_params {
     const uint8_t* s; uint64_t sn;             // the DEFLATE bytes: [d_src + header, d_src + src_len - trailer)
@@ -69,7 +94,7 @@ struct zz_inf_params {
     uint32_t* stat;                            // per packet, at k - ebase: bit 0 ok, bit 1 final, bit 2 not written (past cap),
                                                // bits 3.. bytes produced
     uint64_t ebase;                            // packet number of ends[0] / stat[0] (indexed: the batch's first; discovery: 0)
-    unsigned long long* tot;                   // [0] pending bytes, [1 + r] still open after round r, [62] packets not written, [63] failed packets
+    unsigned long long* tot;                   // the counter block (ZZ_TOT_*)
 };
 
 // the input seen through an LDS stage: bytes g[base, base + ZZ_INF_IBUF) of the run's view g[0, n) (zero outside it)
@@ -182,7 +207,7 @@ template <int FORM> __device__ __forceinline__ void inflate_packets_body(zz_inf_
             for (uint32_t i = lane; i < nb; i += ZZ_INF_THREADS) d[i] = win[i];
         }
         if (np) for (uint32_t i = lane; i < Q.words; i += ZZ_INF_THREADS) Q.pend[(uint64_t)b * Q.words + i] = pend[i];
-        if (lane == 0 && np) atomicAdd(&Q.tot[0], (unsigned long long)np);
+        if (lane == 0 && np) atomicAdd(&Q.tot[ZZ_TOT_PENDING], (unsigned long long)np);
     }
     // phase 2 looks at a packet only through these: a packet that failed or was not written has nothing pending
     if (lane == 0) { const uint32_t v = fits ? np : 0u; Q.pcnt[b] = v; Q.prem[b] = v; }
@@ -195,8 +220,8 @@ template <int FORM> __device__ __forceinline__ void inflate_packets_body(zz_inf_
     } else if (lane == 0 && k < Q.nstarts) {
         Q.ends[k - Q.ebase] = R.err ? 0 : start + R.end;
         Q.stat[k - Q.ebase] = R.err ? 0u : (1u | (R.final ? 2u : 0u) | (fits ? 0u : 4u) | ((uint32_t)R.out << 3));
-        if (R.err) atomicAdd(&Q.tot[63], 1ull);
-        else if (!fits) atomicAdd(&Q.tot[62], 1ull);
+        if (R.err) atomicAdd(&Q.tot[ZZ_TOT_FAILED], 1ull);
+        else if (!fits) atomicAdd(&Q.tot[ZZ_TOT_UNWRITTEN], 1ull);
     }
 }
 __global__ __launch_bounds__(ZZ_INF_THREADS) void k_inflate_packets(zz_inf_params Q) { inflate_packets_body<0>(Q, zz_inf_ranges{ nullptr, nullptr }); }
@@ -211,7 +236,7 @@ struct zz_res_params {
 };
 // what the range form (k_inflate_resolve_range) knows on top: dst is the stage -- ZI_BIAS carried bytes of the batch before, then
 // this batch's -- and base = ZI_BIAS, so a target below the batch base reads a carried byte; `carry` has one bit per carried
-// byte: external (zz_inflate_core.h). Bytes that turn external inside [wlo, whi) (relative to the batch base) are counted in tot[61].
+// byte: external (zz_inflate_core.h). Bytes that turn external inside [wlo, whi) (relative to the batch base) are counted in tot[ZZ_TOT_EXTERNAL].
 struct zz_res_range { const uint32_t* carry; int64_t wlo, whi; };
 // RANGES (form 2, k_inflate_resolve_ranges): the stage holds a wave of segments and base = 0; a pointer counts from its segment's
 // first byte, stage packet d.seg0, and a target below that is external -- nothing is carried, segments do not span batches. The
@@ -260,7 +285,7 @@ template <int FORM> __device__ __forceinline__ void inflate_resolve_body(zz_res_
     if (RANGE) {
         nx = inf_wave_sum(nx);
         if (FORM == 2) { if ((t & 63) == 0 && nx) atomicAdd(&Z.reads[D.read].ext, nx); }
-        else if ((t & 63) == 0 && nx) atomicAdd(&Q.tot[61], (unsigned long long)nx);
+        else if ((t & 63) == 0 && nx) atomicAdd(&Q.tot[ZZ_TOT_EXTERNAL], (unsigned long long)nx);
     }
     left = inf_wave_sum(left);
     if ((t & 63) == 0) red[t >> 6] = left;
@@ -269,7 +294,7 @@ template <int FORM> __device__ __forceinline__ void inflate_resolve_body(zz_res_
         uint32_t sum = 0;
         for (int w = 0; w < ZZ_INF_RES_THREADS / ZZ_WAVE; ++w) sum += red[w];
         Q.prem[k] = sum;
-        if (sum) atomicAdd(&Q.tot[1 + round], (unsigned long long)sum);
+        if (sum) atomicAdd(&Q.tot[ZZ_TOT_OPEN + round], (unsigned long long)sum);
     }
 }
 __global__ __launch_bounds__(ZZ_INF_RES_THREADS) void k_inflate_resolve(zz_res_params Q, uint32_t round)

@@ -12,7 +12,7 @@
 //             k_crc32_stage / k_adler_stage   zz_checksum.h's bodies over the stage through zz_stage_map: a packet's length is what
 //                                phase 1 says it produced (the device's `stat` word), never a length the host knows
 //             k_stage_check_range / k_stage_check_ranges   one thread per stage packet: zi_checked_packet_bad against the sidecar;
-//                                a mismatch is counted in tot[60], or charged to the packet's read as a failed packet
+//                                a mismatch is counted in tot[ZZ_TOT_BAD_SUM], or charged to the packet's read as a failed packet
 //
 // Only the packets a read returns bytes from are summed and compared; look-back packets are not (nothing of them is returned).
 // Every kernel reads the sidecar only at [0, packets) -- the host has held the entry count to the index's -- and the stage only

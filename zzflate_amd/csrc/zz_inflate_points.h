@@ -10,7 +10,7 @@
 //                                 front of the segment is PENDING: its bit in the batch's bitmap (global memory, atomicOr: two
 //                                 segments may share a word) and its pointer in st.
 //   count    k_points_count       segments and tiles do not line up, so phase 1 keeps no per-tile counts: one pass over the
-//                                 bitmap pop-counts every tile of ZI_POINTS_TILE bytes into pcnt / prem and the total into tot[0].
+//                                 bitmap pop-counts every tile of ZI_POINTS_TILE bytes into pcnt / prem and the total into tot[ZZ_TOT_PENDING].
 //   phase 2  k_inflate_resolve    zz_inflate.h's rounds, unchanged: they never looked at packets, only at tiles of P bytes
 //                                 through pend, st, pcnt and prem.
 //
@@ -40,7 +40,7 @@ struct zz_pt_params {
     uint32_t* st; uint32_t* pend; uint64_t words;   // nbytes pointers, the bitmap's words (zero on entry)
     zz_pt_stat* stat;                           // per segment
     unsigned int* next;                         // the next segment to deal out (zero on entry)
-    unsigned long long* tot;                    // [63] failed segments
+    unsigned long long* tot;                    // [ZZ_TOT_FAILED] failed segments
 };
 
 // zi_out_segment's bits on the device: set by an atomic (lanes, and the neighbouring segments, share words), read past the L1
@@ -75,14 +75,14 @@ __global__ __launch_bounds__(ZZ_INF_THREADS) void k_inflate_segments(zz_pt_param
         const zi_result R = zi_run(in, view, b0 >> 3, o, S, ZI_RUN_POINT, o1 - o0, lane, ZZ_INF_THREADS, pt);
         if (lane == 0) {
             Q.stat[i] = zz_pt_stat{ pt.end_bit, R.err ? 0u : (1u | (R.final ? 2u : 0u)), (uint32_t)R.out };
-            if (R.err) atomicAdd(&Q.tot[63], 1ull);
+            if (R.err) atomicAdd(&Q.tot[ZZ_TOT_FAILED], 1ull);
         }
         __syncthreads();                        // the next segment's first stage overwrites the input buffer
     }
 }
 
 // pcnt[t] = prem[t] = pending bytes of tile t (ZI_POINTS_TILE / 32 words each; the bitmap is zero behind the batch's bytes),
-// tot[0] += their sum. One workgroup per tile.
+// tot[ZZ_TOT_PENDING] += their sum. One workgroup per tile.
 __global__ __launch_bounds__(256) void k_points_count(const uint32_t* pend, uint32_t* pcnt, uint32_t* prem, unsigned long long* tot)
 {
     __shared__ uint32_t red[256 / ZZ_WAVE];
@@ -96,7 +96,7 @@ __global__ __launch_bounds__(256) void k_points_count(const uint32_t* pend, uint
         uint32_t sum = 0;
         for (int k = 0; k < 256 / ZZ_WAVE; ++k) sum += red[k];
         pcnt[t] = sum; prem[t] = sum;
-        if (sum) atomicAdd(&tot[0], (unsigned long long)sum);
+        if (sum) atomicAdd(&tot[ZZ_TOT_PENDING], (unsigned long long)sum);
     }
 }
 
