@@ -564,6 +564,63 @@ int zz_decode_members_ranges_device(zz_ctx* ctx, const void* d_src, uint64_t src
 /* what the last zz_decode_members_ranges_device did: the members it decoded (each once), and the waves */
 int zz_ctx_last_decode_members_ranges_stats(const zz_ctx* ctx, uint64_t* members_decoded, uint32_t* waves);
 
+/* ---- reads of any stream through a point index: windows and sums beside the index -----------------------------------------
+ * zz_decode_points_device decodes a foreign stream only whole. To read a little out of a lot -- random access into an ordinary
+ * .gz -- a segment must decode alone, and for that the index gets a SIDECAR of two arrays, for segments = entries - 1:
+ *   windows  `segments` slots of ZZ_POINTS_WINDOW (32,768) bytes. Slot k holds the decoded bytes
+ *            [max(0, out_byte[k] - 32768), out_byte[k]), right-aligned: the byte at distance d in front of segment k is
+ *            slot[32768 - d]. The bytes in front of them in the slot are unspecified and never read; slot 0 is entirely
+ *            unspecified. Slots have a fixed size so that a slot's place needs no second index.
+ *   sums     `segments` little-endian uint32: entry k is the public checksum of segment k's decoded bytes, as a packet's entry
+ *            of zz_packet_checksums_device: adler32 with start value 1 for zlib, crc32 for gzip and raw; an empty segment has 1 or 0.
+ * 32,772 bytes per segment: 3.1 % of the decoded size at a spacing of 1 MiB, 25 % at 128 KiB. That is the trade: a read costs one
+ * segment's decode by one wavefront, which grows with the spacing, and the sidecar shrinks with it.
+ *
+ * zz_points_windows_host makes both arrays: one more sequential pass over src[0, src_len) in HOST memory, no GPU, no context,
+ * for an index from zz_points_index_host or from elsewhere. The index is verified on the way: ZZ_E_DATA unless every row's in_bit
+ * is a block boundary reached with exactly its out_byte in front of it, the last row is the stream's end and length, and header and
+ * trailer pass as zz_points_index_host checks them. ZZ_E_UNSUPPORTED for a preset dictionary; ZZ_E_ARG for a null pointer,
+ * entries < 2 or a format outside 0..2. windows: segments * 32768 bytes, sums: segments words, both the caller's. */
+#define ZZ_POINTS_WINDOW 32768u
+int zz_points_windows_host(const uint8_t* src, uint64_t src_len, int format, const uint64_t* points, uint64_t entries,
+                           uint8_t* windows, uint32_t* sums);
+
+/* Many reads of one zlib / gzip / raw stream through its point index and sidecar in one call: read r receives the decoded bytes
+ * [d_firsts[r], d_firsts[r] + d_nbytes[r]) of the stream d_src[0, src_len). Index (entries rows), windows and sums live in DEVICE
+ * memory -- made once, read many times -- and so do the six arrays of nranges entries (d_status may be NULL). Reads, lengths,
+ * statuses, the return value and its precedence are zz_decode_members_ranges_device's, with L = the last out_byte and a SEGMENT
+ * where that call says member: m = min(nbytes, L - first); ZZ_E_ARG first > L or overflow; ZZ_E_NOSPACE m > cap; ZZ_E_DATA a
+ * touched segment is not what index and sidecar say; ZZ_E_UNSUPPORTED none is like that, but one has a room above 64 MiB. A read
+ * whose status is not ZZ_OK has d_out_lens[r] = ~0 and leaves every other read complete. A touched segment is decoded whole and
+ * once per call, however many reads touch it: the price of the checksum.
+ * NOTHING BESIDE THE STREAM IS TRUSTED. A segment is what index and sidecar say iff it begins at a block header, ends at the next
+ *   row's bit, produces exactly its room, holds the final block iff it is the last one, no distance in it reaches in front of the
+ *   stream (whatever a slot's unspecified bytes hold), and the checksum of the bytes it produced equals d_sums[k]. For zlib and
+ *   gzip the sums, folded in segment order over the lengths the index gives, must give the stream's own trailer -- so a wrong
+ *   window shows as a checksum mismatch, not as wrong bytes. A raw stream has no trailer: there the sums are the caller's own
+ *   witness, as the sidecar of zz_decode_range_checked_device is for a raw stream.
+ *   Failure of the call as a whole, decided on the device (every d_status[r] = ZZ_E_DATA, every d_out_lens[r] = ~0, no destination
+ *   byte written, the call returns ZZ_E_DATA): the rows are not an index (row 0 == (0, 0), in_bit strictly ascending, out_byte
+ *   ascending); the last in_bit does not end exactly where the trailer begins; the container header is invalid (a preset
+ *   dictionary: the call returns ZZ_E_UNSUPPORTED); the sums do not fold to the trailer (Adler-32; CRC-32 and ISIZE against L mod
+ *   2^32; lengths are 64-bit in the fold); an entry that no segment of its length can have.
+ *   ZZ_E_ARG, before anything is launched: a null context, source, index, windows, sums, d_firsts, d_nbytes, d_dsts, d_caps or
+ *   d_out_lens; entries < 2; entries - 1 or nranges above 2^31 - 1; a format outside 0..2; an unfinished zz_encode_device_async.
+ *   nranges == 0 with arguments that pass returns ZZ_OK at once.
+ * There is no serial path: errors come at the parallel rate. How: check, plan, touched scan, waves, cut, copy and
+ * verdict are zz_decode_members_ranges_device's kernels called with the rows; one workgroup reads the header and folds the sums;
+ * per wave one wavefront per touched segment decodes it onto the stage against its window slot, read where it lies, and sums it.
+ * Workspace: the stage (below 128 MiB); 28 bytes per segment; 20 bytes per touched segment of the largest wave; 32 bytes per read;
+ * 16 bytes per wave. Synchronous; the host reads a fixed number of words per call and per wave. Leaves the context's "last call",
+ * "last decode", zz_ctx_last_decode_ranges_stats and zz_ctx_last_decode_members_ranges_stats state alone. */
+int zz_decode_points_ranges_device(zz_ctx* ctx, const void* d_src, uint64_t src_len, int format,
+                                   const uint64_t* d_points, uint64_t entries, const void* d_windows, const uint32_t* d_sums,
+                                   uint64_t nranges, const uint64_t* d_firsts, const uint64_t* d_nbytes,
+                                   void* const* d_dsts, const uint64_t* d_caps,
+                                   uint64_t* d_out_lens, int32_t* d_status, void* hip_stream);
+/* what the last zz_decode_points_ranges_device did: the segments it decoded (each once), and the waves */
+int zz_ctx_last_decode_points_ranges_stats(const zz_ctx* ctx, uint64_t* segments_decoded, uint32_t* waves);
+
 enum { ZZ_DECODE_INDEXED = 1, ZZ_DECODE_DISCOVERED = 2, ZZ_DECODE_SERIAL = 3, ZZ_DECODE_POINTS = 4 };
 /* which path the last zz_decode_device / zz_decode_points_device finished on (0: none) */
 int zz_ctx_last_decode_path(const zz_ctx* ctx);

@@ -110,6 +110,9 @@ def _load():
         "zz_members_index_device": (i32, [vp, vp, u64, vp, u64, pu64, vp]),
         "zz_decode_members_ranges_device": (i32, [vp, vp, u64, vp, u64, u64, vp, vp, vp, vp, vp, vp, vp]),
         "zz_ctx_last_decode_members_ranges_stats": (i32, [vp, pu64, ctypes.POINTER(u32)]),
+        "zz_points_windows_host": (i32, [vp, u64, i32, vp, u64, vp, vp]),
+        "zz_decode_points_ranges_device": (i32, [vp, vp, u64, i32, vp, u64, vp, vp, u64, vp, vp, vp, vp, vp, vp, vp]),
+        "zz_ctx_last_decode_points_ranges_stats": (i32, [vp, pu64, ctypes.POINTER(u32)]),
         "zz_ctx_last_decode_path": (i32, [vp]),
         "zz_ctx_last_decode_stats": (i32, [vp, pu64, ctypes.POINTER(u32)]),
         "zz_ctx_last_decode_index_device": (i32, [vp, vp, u64, pu64, vp]),
@@ -262,6 +265,36 @@ def points_index_host(data, format=Format.Zlib, spacing=POINTS_SPACING):
     _check(lib.zz_points_index_host(data, len(data), int(format), spacing, points.data_ptr(), entries.value, ctypes.byref(entries),
                                     ctypes.byref(n)))
     return points, n.value
+
+
+POINTS_WINDOW = 32768                                   # ZZ_POINTS_WINDOW: bytes of a window slot
+
+
+def _points_tensor(points, where):
+    import torch
+    if not isinstance(points, torch.Tensor) or points.dtype != torch.int64 or points.dim() != 2 or points.shape[1] != 2 or not points.is_contiguous():
+        raise TypeError("points must be a contiguous int64 tensor of shape [segments + 1, 2] (as points_index_host() returns)")
+    if points.shape[0] < 2:
+        raise ValueError("a point index has at least two rows")
+    if where == "cpu" and points.device.type != "cpu":
+        raise ValueError("points must be a CPU tensor")
+
+
+def points_windows_host(data, points, format=Format.Zlib):
+    """The sidecar that lets a segment of the point index ``points`` of the stream ``data`` decode alone, made in one more
+    sequential pass on the host: ``(windows, sums)`` -- a uint8 CPU tensor ``[segments, 32768]`` (slot k: the decoded bytes in
+    front of segment k, right-aligned; what lies in front of them is zero here and unspecified by the format) and an int32 CPU
+    tensor ``[segments]`` (adler32 of a zlib stream's segment, crc32 of a gzip or raw one, as the int32 of the same bits). The
+    index is verified against the stream: ZzFlateError (E_DATA, E_UNSUPPORTED) otherwise. Moved to the device, what
+    ``Context.decode_points_ranges`` takes."""
+    import torch
+    _points_tensor(points, "cpu")
+    data = bytes(data)
+    segments = points.shape[0] - 1
+    windows = torch.zeros((segments, POINTS_WINDOW), dtype=torch.uint8)
+    sums = torch.zeros(segments, dtype=torch.int32)
+    _check(lib.zz_points_windows_host(data, len(data), int(format), points.data_ptr(), points.shape[0], windows.data_ptr(), sums.data_ptr()))
+    return windows, sums
 
 
 def members_bound(n, block_size=MEMBERS_BLOCK, packet_size=DEFAULT_PACKET, eof=True):
@@ -790,20 +823,9 @@ class Context:
         _check(lib.zz_members_index_device(self._h, self._ptr(src), src_len, idx.data_ptr(), entries.value, ctypes.byref(entries), st))
         return idx
 
-    def decode_members_ranges(self, src, src_len, index, firsts, nbytes, dsts, caps=None, stream=None):
-        """Many reads of one blocked gzip (BGZF) file in one call: read r = decoded bytes ``[firsts[r], firsts[r] + nbytes[r])``
-        of the file ``src[:src_len]`` into ``dsts[r]``. ``index`` is an int64 tensor of shape ``[members + 1, 2]`` on this
-        context's device (``members_index``, or ``members_index_from_offsets`` moved there); ``dsts`` are items as
-        ``decode_batch`` takes them; ``caps`` defaults to ``min(nbytes[r], destination size)``. Returns ``(lens, status)``:
-        ``lens[r]`` the bytes read (clipped at the file's decoded length) or ``None``, ``status[r]`` 0, E_ARG, E_NOSPACE, E_DATA
-        or E_UNSUPPORTED -- a read's own failure does not raise and leaves the others complete; an index that is not an index
-        gives every read E_DATA; only a refused call (arguments) raises. Every member a read touches is decoded whole and
-        checked completely: CRC-32, ISIZE and the length the index gives it."""
+    def _reads(self, call, firsts, nbytes, dsts, caps, stream):
+        """the read arrays of decode_members_ranges and decode_points_ranges on the device, the call, and (lens, status) back"""
         import torch
-        if not isinstance(index, torch.Tensor) or index.dtype != torch.int64 or index.dim() != 2 or index.shape[1] != 2 or not index.is_contiguous():
-            raise TypeError("index must be a contiguous int64 tensor of shape [members + 1, 2] (as members_index() returns)")
-        if index.device.type != "cuda" or index.device.index != self.device:
-            raise ValueError(f"index must live on this context's device (cuda:{self.device}), not {index.device}")
         k = len(firsts)
         if len(nbytes) != k or len(dsts) != k:
             raise ValueError(f"{k} starts but {len(nbytes)} lengths and {len(dsts)} destinations")
@@ -824,18 +846,72 @@ class Context:
         out = torch.empty(k, dtype=torch.int64, device=dev)
         status = torch.empty(k, dtype=torch.int32, device=dev)
         st = self._stream() if stream is None else stream
-        rc = lib.zz_decode_members_ranges_device(self._h, self._ptr(src), src_len, index.data_ptr(), index.shape[0],
-                                                 k, table[0].data_ptr(), table[1].data_ptr(), table[2].data_ptr(), table[3].data_ptr(),
-                                                 out.data_ptr(), status.data_ptr(), st)
+        rc = call(k, table[0].data_ptr(), table[1].data_ptr(), table[2].data_ptr(), table[3].data_ptr(), out.data_ptr(), status.data_ptr(), st)
         if rc != 0 and not lib.zz_last_error().startswith(b"reads: "):
             _check(rc)                                 # the call itself was refused (the library words a read's own failure "reads: ...")
         status = status.cpu().tolist()
         return [None if sv != 0 else v for v, sv in zip(out.cpu().tolist(), status)], status
 
+    def decode_members_ranges(self, src, src_len, index, firsts, nbytes, dsts, caps=None, stream=None):
+        """Many reads of one blocked gzip (BGZF) file in one call: read r = decoded bytes ``[firsts[r], firsts[r] + nbytes[r])``
+        of the file ``src[:src_len]`` into ``dsts[r]``. ``index`` is an int64 tensor of shape ``[members + 1, 2]`` on this
+        context's device (``members_index``, or ``members_index_from_offsets`` moved there); ``dsts`` are items as
+        ``decode_batch`` takes them; ``caps`` defaults to ``min(nbytes[r], destination size)``. Returns ``(lens, status)``:
+        ``lens[r]`` the bytes read (clipped at the file's decoded length) or ``None``, ``status[r]`` 0, E_ARG, E_NOSPACE, E_DATA
+        or E_UNSUPPORTED -- a read's own failure does not raise and leaves the others complete; an index that is not an index
+        gives every read E_DATA; only a refused call (arguments) raises. Every member a read touches is decoded whole and
+        checked completely: CRC-32, ISIZE and the length the index gives it."""
+        import torch
+        if not isinstance(index, torch.Tensor) or index.dtype != torch.int64 or index.dim() != 2 or index.shape[1] != 2 or not index.is_contiguous():
+            raise TypeError("index must be a contiguous int64 tensor of shape [members + 1, 2] (as members_index() returns)")
+        if index.device.type != "cuda" or index.device.index != self.device:
+            raise ValueError(f"index must live on this context's device (cuda:{self.device}), not {index.device}")
+        def call(k, firsts, nbytes, dsts, caps, out, status, st):
+            return lib.zz_decode_members_ranges_device(self._h, self._ptr(src), src_len, index.data_ptr(), index.shape[0],
+                                                       k, firsts, nbytes, dsts, caps, out, status, st)
+        return self._reads(call, firsts, nbytes, dsts, caps, stream)
+
     def last_decode_members_ranges_stats(self):
         """(members decoded, each once; waves) of the last ``decode_members_ranges``."""
         m, waves = ctypes.c_uint64(0), ctypes.c_uint32(0)
         _check(lib.zz_ctx_last_decode_members_ranges_stats(self._h, ctypes.byref(m), ctypes.byref(waves)))
+        return m.value, waves.value
+
+    def decode_points_ranges(self, src, src_len, points, windows, sums, firsts, nbytes, dsts, caps=None, format=Format.Zlib, stream=None):
+        """Many reads of one zlib / gzip / raw stream this library need not have written, in one call: read r = decoded bytes
+        ``[firsts[r], firsts[r] + nbytes[r])`` of the stream ``src[:src_len]`` into ``dsts[r]``. ``points`` (int64
+        ``[segments + 1, 2]``), ``windows`` (uint8 ``[segments, 32768]``) and ``sums`` (int32 ``[segments]``) are
+        ``points_index_host`` and ``points_windows_host``'s tensors moved to this context's device; ``dsts``, ``caps`` and the
+        result ``(lens, status)`` are ``decode_members_ranges``'. Every segment a read touches is decoded whole against its
+        window and held to its checksum, and the checksums to the stream's trailer: a wrong index or sidecar gives E_DATA, never
+        wrong bytes; one that fails as a whole gives every read E_DATA. Only a refused call (arguments, a preset dictionary) raises."""
+        import torch
+        _points_tensor(points, "cuda")
+        segments = points.shape[0] - 1
+        if not isinstance(windows, torch.Tensor) or windows.dtype != torch.uint8 or tuple(windows.shape) != (segments, POINTS_WINDOW) or not windows.is_contiguous():
+            raise TypeError(f"windows must be a contiguous uint8 tensor of shape [{segments}, {POINTS_WINDOW}] (as points_windows_host() returns)")
+        if not isinstance(sums, torch.Tensor) or sums.dtype != torch.int32 or tuple(sums.shape) != (segments,) or not sums.is_contiguous():
+            raise TypeError(f"sums must be a contiguous int32 tensor of shape [{segments}] (as points_windows_host() returns)")
+        for name, t in (("points", points), ("windows", windows), ("sums", sums)):
+            if t.device.type != "cuda" or t.device.index != self.device:
+                raise ValueError(f"{name} must live on this context's device (cuda:{self.device}), not {t.device}")
+        def call(k, firsts, nbytes, dsts, caps, out, status, st):
+            return lib.zz_decode_points_ranges_device(self._h, self._ptr(src), src_len, int(format), points.data_ptr(), points.shape[0],
+                                                      windows.data_ptr(), sums.data_ptr(), k, firsts, nbytes, dsts, caps, out, status, st)
+        return self._reads(call, firsts, nbytes, dsts, caps, stream)
+
+    def decode_points_range(self, src, src_len, points, windows, sums, first, nbytes, dst, cap=None, format=Format.Zlib, stream=None):
+        """One read through ``decode_points_ranges``: the bytes read (clipped at the decoded length); raises ZzFlateError on failure."""
+        lens, status = self.decode_points_ranges(src, src_len, points, windows, sums, [first], [nbytes], [dst],
+                                                 None if cap is None else [cap], format=format, stream=stream)
+        if status[0] != 0:
+            raise ZzFlateError(status[0], lib.zz_last_error().decode())
+        return lens[0]
+
+    def last_decode_points_ranges_stats(self):
+        """(segments decoded, each once; waves) of the last ``decode_points_ranges``."""
+        m, waves = ctypes.c_uint64(0), ctypes.c_uint32(0)
+        _check(lib.zz_ctx_last_decode_points_ranges_stats(self._h, ctypes.byref(m), ctypes.byref(waves)))
         return m.value, waves.value
 
     def last_decode_path(self):

@@ -35,6 +35,7 @@
 #include "zz_inflate_points.h"
 #include "zz_inflate_members.h"
 #include "zz_inflate_members_ranges.h"
+#include "zz_inflate_points_ranges.h"
 #include "zz_batch.h"
 #include "zz_members_write.h"
 
@@ -221,6 +222,11 @@ struct zz_ctx {
             zz_buf<zz_mr_state> st; zz_pin<zz_mr_state> h_st;
             uint64_t members_decoded = 0; uint32_t waves_run = 0;
         } mr;
+        // zz_decode_points_ranges_device (zz_inflate_points_ranges.h): what its front leaves; everything else is mr's and mem's
+        struct {
+            zz_buf<zz_pr_state> st; zz_pin<zz_pr_state> h_st;
+            uint64_t segments_decoded = 0; uint32_t waves_run = 0;
+        } pr;
     } dec;
 };
 // one call per context at a time: every entry point that would use the buffers of an enqueued call refuses
@@ -2646,6 +2652,140 @@ extern "C" int zz_ctx_last_decode_members_ranges_stats(const zz_ctx* c, uint64_t
     if (!c) { set_err("null context"); return ZZ_E_ARG; }
     if (members_decoded) *members_decoded = c->dec.mr.members_decoded;
     if (waves) *waves = c->dec.mr.waves_run;
+    return ZZ_OK;
+}
+
+// ---- reads of any stream through a point index with windows (zz_inflate_points_ranges.h; the rules in zz_inflate_core.h) ------
+// The sidecar's builder: a second sequential pass on the host over a stream and an index of it, no GPU, no context.
+extern "C" int zz_points_windows_host(const uint8_t* src, uint64_t src_len, int format, const uint64_t* points, uint64_t entries,
+                                      uint8_t* windows, uint32_t* sums)
+{
+    if (!src || !points || !windows || !sums) { set_err("null argument"); return ZZ_E_ARG; }
+    if (entries < 2) { set_err("a point index has at least two rows"); return ZZ_E_ARG; }
+    if (!dec_format_ok(format)) return ZZ_E_ARG;
+    std::vector<uint8_t> ring(ZI_RING);
+    std::vector<zi_tables> S(1);
+    std::vector<zi_sum> sum(1);
+    const int rc = zi_points_windows_build(src, src_len, format, points, entries, windows, sums, ring.data(), S[0], sum[0]);
+    if (rc == ZI_ITEM_UNSUPPORTED) { set_err("the stream needs a preset dictionary (FDICT): not supported"); return ZZ_E_UNSUPPORTED; }
+    if (rc) { set_err("not a valid stream of the requested format, or not an index of it (a row is no block boundary with its bytes in front of it)"); return ZZ_E_DATA; }
+    return ZZ_OK;
+}
+
+extern "C" int zz_decode_points_ranges_device(zz_ctx* c, const void* d_src_v, uint64_t src_len, int format, const uint64_t* d_points,
+                                              uint64_t entries, const void* d_windows, const uint32_t* d_sums,
+                                              uint64_t nranges, const uint64_t* d_firsts, const uint64_t* d_nbytes,
+                                              void* const* d_dsts, const uint64_t* d_caps,
+                                              uint64_t* d_out_lens, int32_t* d_status, void* hip_stream)
+{
+    if (!c || !d_src_v || !d_points || !d_windows || !d_sums || !d_firsts || !d_nbytes || !d_dsts || !d_caps || !d_out_lens) { set_err("null argument"); return ZZ_E_ARG; }
+    if (entries < 2) { set_err("the index needs at least two rows (segments + 1)"); return ZZ_E_ARG; }
+    if (entries - 1 > 0x7fffffffull) { set_err("at most 2^31 - 1 segments per index"); return ZZ_E_ARG; }
+    if (nranges > 0x7fffffffull) { set_err("at most 2^31 - 1 reads per call"); return ZZ_E_ARG; }
+    if (!dec_format_ok(format)) return ZZ_E_ARG;
+    if (nranges == 0) return ZZ_OK;                                 // nothing to do: the context is not looked at
+    if (call_pending(c)) return ZZ_E_ARG;
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t st = (hipStream_t)hip_stream;
+    auto& R = c->dec.mr;                                            // (its buffers; its stats are the member reads' and stay)
+    auto& M = c->dec.mem;
+    auto& X = c->dec.pr;
+    X.segments_decoded = 0; X.waves_run = 0;
+    if (int rc = R.st.grow(1)) return rc;
+    if (int rc = R.h_st.grow(1)) return rc;
+    if (int rc = X.st.grow(1)) return rc;
+    if (int rc = X.h_st.grow(1)) return rc;
+    if (int rc = R.reads.grow(nranges)) return rc;
+    if (int rc = R.chunk0.grow(nranges + 1)) return rc;
+    if (int rc = R.diff.grow(entries)) return rc;
+    if (int rc = R.cnt.grow(entries)) return rc;
+    if (int rc = R.tlist.grow(entries)) return rc;
+    if (int rc = R.S.grow(entries)) return rc;
+    if (int rc = R.F.grow(entries)) return rc;
+    if (int rc = R.G.grow(entries)) return rc;
+    zz_mr_params Q;
+    Q.src = (const uint8_t*)d_src_v; Q.idx = d_points; Q.entries = entries;
+    Q.src_len = src_len > (~0ull >> 3) ? ~0ull : 8 * src_len;       // k_mr_check's bound on the last row: a bit inside the source (k_pr_front is exact)
+    Q.nranges = nranges; Q.firsts = d_firsts; Q.nbytes = d_nbytes; Q.dsts = (uint8_t* const*)d_dsts; Q.caps = d_caps;
+    Q.out_lens = d_out_lens; Q.status = d_status;
+    Q.reads = R.reads; Q.chunk0 = R.chunk0; Q.diff = R.diff; Q.cnt = R.cnt; Q.tlist = R.tlist; Q.S = R.S; Q.F = R.F; Q.G = R.G;
+    Q.stage = nullptr; Q.st = R.st;
+    zz_pr_params P;
+    P.src = (const uint8_t*)d_src_v; P.src_len = src_len; P.format = format; P.windows = (const uint8_t*)d_windows; P.sums = d_sums;
+    P.ps = X.st; P.rooms = nullptr; P.out_lens = nullptr; P.status = nullptr;
+    const auto grid = [](uint64_t n) { return dim3((uint32_t)std::min<uint64_t>((n + 255) / 256, 4096)); };
+
+    // check, front, plan, touched: one readback
+    HIPCHK(hipMemsetAsync(R.st, 0, sizeof(zz_mr_state), st));
+    HIPCHK(hipMemsetAsync(X.st, 0, sizeof(zz_pr_state), st));
+    HIPCHK(hipMemsetAsync(R.diff, 0, entries * sizeof(int32_t), st));
+    hipLaunchKernelGGL(k_mr_check, grid(entries), dim3(256), 0, st, Q);
+    hipLaunchKernelGGL(k_pr_front, dim3(1), dim3(ZZ_PR_FRONT_THREADS), 0, st, Q, P);
+    hipLaunchKernelGGL(k_mr_plan, grid(nranges), dim3(256), 0, st, Q);
+    hipLaunchKernelGGL(k_mr_touched, dim3(1), dim3(ZZ_MR_SCAN_THREADS), 0, st, Q);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(R.h_st, R.st, sizeof(zz_mr_state), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(X.h_st, X.st, sizeof(zz_pr_state), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (X.h_st->dict) { set_err("the stream needs a preset dictionary (FDICT): not supported"); return ZZ_E_UNSUPPORTED; }
+    if (R.h_st->index_bad) {
+        set_err(X.h_st->refused ? "reads: all fail, the container header is invalid, the last row does not end where the trailer begins, or the sums do not fold to the trailer"
+                                : "reads: all fail, the rows are not a point index (row 0 = (0, 0), bits strictly ascending, bytes ascending)");
+        return ZZ_E_DATA;
+    }
+    const uint64_t touched = R.h_st->touched, nwaves = R.h_st->nwaves;
+    if (touched) {
+        // the waves' first ranks and S there: one readback
+        if (int rc = R.waves.grow(2 * (nwaves + 1))) return rc;
+        if (int rc = R.h_waves.grow(2 * (nwaves + 1))) return rc;
+        hipLaunchKernelGGL(k_mr_waves, grid(nwaves + 1), dim3(256), 0, st, Q, nwaves, (uint64_t*)R.waves);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(R.h_waves, R.waves, 2 * (nwaves + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        const uint64_t* W = R.h_waves.p;
+        uint64_t big_items = 0, big_bytes = 0;
+        for (uint64_t w = 0; w < nwaves; ++w) {
+            big_items = std::max(big_items, W[2 * w + 2] - W[2 * w]);
+            big_bytes = std::max(big_bytes, W[2 * w + 3] - W[2 * w + 1]);
+        }
+        if (int rc = R.stage.grow(big_bytes + 16)) return rc;
+        if (int rc = M.caps.grow(big_items)) return rc;
+        if (int rc = M.out_lens.grow(big_items)) return rc;
+        if (int rc = R.status.grow(big_items)) return rc;
+        Q.stage = R.stage;
+        P.rooms = M.caps; P.out_lens = M.out_lens; P.status = R.status;
+        const uint64_t resident = 256ull * ZZ_PT_WG_PER_CU;         // persistent wavefronts: what the CUs hold at once
+        for (uint64_t w = 0; w < nwaves; ++w) {
+            const uint64_t t0 = W[2 * w], t1 = W[2 * w + 2];
+            if (t1 <= t0) continue;                                     // (cannot happen: a room is at most one wave's)
+            ++X.waves_run;
+            HIPCHK(hipMemsetAsync(&X.st.p->next, 0, sizeof(unsigned int), st));
+            hipLaunchKernelGGL(k_inflate_segments_win, dim3((uint32_t)std::min<uint64_t>(t1 - t0, resident)), dim3(ZZ_INF_THREADS), 0, st, Q, P, t0, t1);
+            hipLaunchKernelGGL(k_mr_judge, dim3(1), dim3(ZZ_MR_SCAN_THREADS), 0, st, Q, t0, t1, (const uint64_t*)M.caps, (const uint64_t*)M.out_lens,
+                               (const int32_t*)R.status);
+            hipLaunchKernelGGL(k_mr_cut, dim3(1), dim3(ZZ_MR_SCAN_THREADS), 0, st, Q, t0, t1);
+            hipLaunchKernelGGL(k_mr_copy, dim3(ZZ_MR_COPY_GRID), dim3(256), 0, st, Q, t0, t1);
+            HIPCHK(hipGetLastError());
+        }
+        X.segments_decoded = touched - R.h_st->big;
+    }
+    hipLaunchKernelGGL(k_mr_verdict, grid(nranges), dim3(256), 0, st, Q);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(R.h_st, R.st, sizeof(zz_mr_state), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    const zz_mr_state& T = *R.h_st.p;
+    if (T.n_data) { set_err("reads: " + std::to_string(T.n_data) + " touch a segment that is not what index and sidecar say"); return ZZ_E_DATA; }
+    if (T.n_unsupported) { set_err("reads: " + std::to_string(T.n_unsupported) + " touch a segment whose room exceeds the stage (64 MiB)"); return ZZ_E_UNSUPPORTED; }
+    if (T.n_arg) { set_err("reads: " + std::to_string(T.n_arg) + " start behind the decoded length or overflow"); return ZZ_E_ARG; }
+    if (T.n_nospace) { set_err("reads: " + std::to_string(T.n_nospace) + " do not fit their destinations"); return ZZ_E_NOSPACE; }
+    return ZZ_OK;
+}
+
+extern "C" int zz_ctx_last_decode_points_ranges_stats(const zz_ctx* c, uint64_t* segments_decoded, uint32_t* waves)
+{
+    if (!c) { set_err("null context"); return ZZ_E_ARG; }
+    if (segments_decoded) *segments_decoded = c->dec.pr.segments_decoded;
+    if (waves) *waves = c->dec.pr.waves_run;
     return ZZ_OK;
 }
 

@@ -1330,4 +1330,178 @@ ZZ_HD int zi_points_build(const uint8_t* src, uint64_t src_len, int format, uint
     return ZI_ITEM_OK;
 }
 
+// ---- reads of any stream through a point index with windows (zz_decode_points_ranges_device, zz_inflate_points_ranges.h;
+// tests/cxx/inflate_points_ranges_harness.cpp) ----------------------------------------------------------------------------------
+// A point index has the shape of a member index: pairs (position in the source, decoded offset), both ascending -- so plan, touched,
+// waves, cut, copy and verdict are zi_mr_* with the rows as they are, a SEGMENT where those say member. What a segment needs to
+// decode alone is the SIDECAR beside the index, for `segments` = entries - 1:
+//   windows  `segments` slots of ZI_PR_WINDOW bytes: slot k holds the decoded bytes [max(0, out_byte[k] - 32768), out_byte[k])
+//            right-aligned -- the byte at distance d in front of segment k is slot[ZI_PR_WINDOW - d]; what lies in front of them in
+//            the slot is unspecified and never read (zi_out_window reads at distance d only behind `d <= out_byte[k] + pos`)
+//   sums     `segments` public checksums (zi_sidecar_kind: adler32 from 1 for zlib, crc32 for gzip and raw) of the segments' bytes
+// Neither is trusted. The sums, folded in segment order over the lengths the index gives (64 bits: a segment nobody reads may
+// exceed 4 GiB), must give the stream's trailer (zi_pr_join, zi_sidecar_trailer_ok), and every entry must be one a segment of its
+// length can have (zi_pr_entry_part); a segment a read touches is decoded whole against its window, summed where it lies on the
+// stage and held to its entry: it is what index and sidecar say iff ZI_RUN_POINT accepts it with exactly its room, no distance
+// reaches in front of the stream, and the sum of the bytes equals the entry. A wrong window is therefore a mismatch, not wrong bytes.
+#define ZI_PR_WINDOW 32768u
+// a checksum partial with its length: Adler-32 as the start-0 partial (b << 16 | a), CRC-32 as it is; (0, 0) is nothing
+struct zi_pr_part { uint32_t v; uint64_t len; };
+ZZ_HD inline zi_pr_part zi_pr_join(int kind, const zi_pr_part& x, const zi_pr_part& y)
+{
+    return zi_pr_part{ kind == ZI_CKS_ADLER ? adler_combine(x.v, y.v, y.len) : crc32_combine(x.v, y.v, y.len), x.len + y.len };
+}
+// a sidecar entry of a segment of `len` bytes as a partial; false: no segment of that length has this entry (zi_cks_partial)
+ZZ_HD inline bool zi_pr_entry_part(int kind, uint32_t entry, uint64_t len, zi_pr_part* p)
+{
+    uint32_t a = 0, b = 0;
+    const bool ok = zi_cks_partial(kind, entry, len ? (uint32_t)(len % ZZ_ADLER_MOD) + ZZ_ADLER_MOD : 0u, &a, &b);   // (the same residue, and 0 only for 0)
+    p->v = kind == ZI_CKS_ADLER ? ((b << 16) | a) : a; p->len = len;
+    return ok;
+}
+// the fold against the trailer t (4 or 8 bytes; raw: none, the sums are the caller's own witness); `all`: every segment joined in order
+ZZ_HD inline bool zi_pr_trailer_ok(int format, const uint8_t* t, const zi_pr_part& all)
+{
+    return zi_sidecar_trailer_ok(format, t, format == 0 ? (all.v & 0xFFFFu) : all.v, format == 0 ? (all.v >> 16) : 0u, all.len);
+}
+// the DEFLATE bytes of a stream of src_len bytes behind a header of hl: where the last row's bit must end. false: truncated
+ZZ_HD inline bool zi_pr_deflate_len(int format, uint64_t src_len, int64_t hl, uint64_t* sn)
+{
+    const uint64_t tl = format == 0 ? 4 : format == 1 ? 8 : 0;
+    if (hl < 0 || src_len < (uint64_t)hl + tl) return false;
+    *sn = src_len - (uint64_t)hl - tl;
+    return true;
+}
+// what zi_mr_entry_bad does not ask of the rows: row 0 is the first DEFLATE bit, and the last row's bit ends exactly where the trailer begins
+ZZ_HD inline bool zi_pr_ends_ok(uint64_t first_bit, uint64_t last_bit, uint64_t sn) { return first_bit == 0 && last_bit / 8 + (last_bit % 8 ? 1 : 0) == sn; }
+
+// One segment onto its slot of the stage, with its window slot in front of it. out[0, n): n is the segment's room, so more than
+// that is ZI_E_SHAPE. A copy whose source lies in front of the segment reads the window slot where it is; one that straddles the
+// edge takes its first bytes from the window and the rest from the slot. Nothing is pending. The slot's bytes are read as other
+// lanes wrote them, hence the fence in front of every copy; the window is nobody's to write. from_win: bytes this lane took
+// from the window.
+template <class Fence> struct zi_out_window {
+    zi_view<uint8_t> out;          // the segment's slot
+    zi_view<const uint8_t> win;    // its window slot: ZI_PR_WINDOW bytes
+    uint64_t abs;                  // absolute output position of the segment's first byte
+    uint64_t pos;
+    uint64_t from_win;
+    uint32_t lane, nl;
+    Fence fence;
+    ZZ_HD int lit(uint32_t v)
+    {
+        if (pos >= out.n) return ZI_E_SHAPE;
+        if (lane == 0) out[pos] = (uint8_t)v;
+        ++pos;
+        return ZI_OK;
+    }
+    ZZ_HD int copy(uint32_t dist, uint32_t len)
+    {
+        if (dist > abs + pos) return ZI_E_FAR;                    // in front of the stream, whatever the slot holds there
+        if (out.n - pos < len) return ZI_E_SHAPE;
+        fence();                                                  // the bytes other lanes wrote are visible
+        if (dist > pos) {                                         // the copy starts `front` bytes in front of the segment: front <= min(abs, 32768)
+            const uint32_t front = dist - (uint32_t)pos;
+            for (uint32_t i = lane; i < len; i += nl) {
+                const uint32_t j = i < dist ? i : i % dist;
+                if (j < front) { out[pos + i] = win[ZI_PR_WINDOW - front + j]; ++from_win; }
+                else out[pos + i] = out[j - front];
+            }
+        } else {
+            for (uint32_t i = lane; i < len; i += nl) out[pos + i] = out[pos - dist + (i < dist ? i : i % dist)];
+        }
+        pos += len;
+        return ZI_OK;
+    }
+    ZZ_HD int stored(const zi_view<const uint8_t>& in, uint64_t at, uint32_t len)
+    {
+        if (out.n - pos < len) return ZI_E_SHAPE;
+        for (uint32_t i = lane; i < len; i += nl) out[pos + i] = in[at + i];
+        pos += len;
+        return ZI_OK;
+    }
+};
+
+// What the decode kernel is told about the touched segment of rank t in the wave that begins at rank t0: its rows, its window
+// slot, its slot on the stage and its room. A big segment is not decoded (`skip`).
+struct zi_pr_slot { uint64_t seg, b0, o0, b1, stage_off, room; bool last, skip; };
+ZZ_HD inline zi_pr_slot zi_pr_desc(const zi_mr_tables& T, uint64_t entries, uint64_t t, uint64_t t0)
+{
+    const uint32_t e = T.tlist[t];
+    const uint64_t j = e & ~ZI_MR_BIG;
+    zi_pr_slot s{ j, zi_mr_c(T.idx, j), zi_mr_u(T.idx, j), zi_mr_c(T.idx, j + 1), 0, 0, j + 2 == entries, (e & ZI_MR_BIG) != 0 };
+    if (!s.skip) { s.stage_off = T.S[t] - T.S[t0]; s.room = zi_mr_room(T.idx, j); }
+    return s;
+}
+// The verdict on a decoded segment, in k_inflate_items' words so that zi_mr_member_bad judges it: ZI_ITEM_OK with `room` bytes iff
+// the run was accepted (err == 0: ZI_RUN_POINT's shape, its room, no far distance) and the bytes' public sum is the entry
+ZZ_HD inline int zi_pr_segment_status(int err, uint64_t out, uint64_t room, uint32_t sum, uint32_t entry)
+{
+    return err == ZI_OK && out == room && sum == entry ? ZI_ITEM_OK : ZI_ITEM_DATA;
+}
+
+// -- the sidecar's builder: a second sequential pass of one lane over a stream and an index somebody made (zz_points_windows_host) --
+// The block hook holds every row to the stream: a row's bit must be a block boundary reached with exactly its bytes in front of
+// it. There the ring holds the 32 KiB in front of the boundary -- the row's window -- and the sum is cut: the ring is summed up to
+// the boundary (zi_out_ring::turn) and the running value is the segment's entry.
+struct zi_pt_windows {
+    static constexpr bool on = true;
+    uint32_t skip; uint64_t stop; bool last; uint64_t end_bit;
+    zi_out_ring* o;
+    zi_view<const uint64_t> rows; uint64_t entries;
+    zi_view<uint8_t> windows; zi_view<uint32_t> sums;      // segments * ZI_PR_WINDOW bytes, segments words
+    uint64_t k;                    // the next row to meet
+    bool bad;
+    // the running sum is segment k - 1's: its entry, and a fresh start
+    ZZ_HD void cut()
+    {
+        o->turn();
+        zi_sum& s = *o->sum;
+        if (k) sums[k - 1] = s.format == 0 ? ((s.b << 16) | s.a) : ~s.crc;
+        s.a = 1; s.b = 0; s.crc = ~0u;
+    }
+    ZZ_HD void block(uint64_t bit, uint64_t pos)
+    {
+        if (bad || k + 1 >= entries) return;                       // (the last row is held to the stream's end, behind the run)
+        if (rows[2 * k] > bit) return;
+        if (rows[2 * k] < bit || rows[2 * k + 1] != pos) { bad = true; return; }     // the row's bit was no boundary, or not with its bytes
+        cut();
+        const uint64_t have = pos < ZI_PR_WINDOW ? pos : ZI_PR_WINDOW;
+        for (uint64_t d = 1; d <= have; ++d) windows[k * ZI_PR_WINDOW + ZI_PR_WINDOW - d] = o->ring[(pos - d) & (ZI_RING - 1)];
+        ++k;
+    }
+};
+// The whole pass: zi_points_build's verdict on the stream (header, blocks, trailer's place) and on the rows; then the sums it made
+// must fold to the trailer. ZI_ITEM_OK, ZI_ITEM_DATA, ZI_ITEM_UNSUPPORTED (a preset dictionary). ring: ZI_RING bytes.
+ZZ_HD inline int zi_points_windows_build(const uint8_t* src, uint64_t src_len, int format, const uint64_t* rows, uint64_t entries,
+                                         uint8_t* windows, uint32_t* sums, uint8_t* ring, zi_tables& S, zi_sum& sum)
+{
+    const int64_t hl = zi_header(format, src, src_len);
+    if (hl == -2) return ZI_ITEM_UNSUPPORTED;
+    if (hl < 0 || entries < 2) return ZI_ITEM_DATA;
+    const uint64_t tl = format == 0 ? 4 : format == 1 ? 8 : 0;
+    const uint64_t segments = entries - 1;
+    const zi_view<const uint8_t> view{ src + hl, src_len - (uint64_t)hl };     // the blocks and the trailer
+    zi_in_mem in{ view };
+    const int kind = zi_sidecar_kind(format);
+    sum.init(kind == ZI_CKS_ADLER ? 0 : 1);                                    // (a raw stream's segments are summed as gzip's)
+    zi_out_ring o{ zi_view<uint8_t>{ ring, ZI_RING }, &sum, 0, 0 };
+    zi_pt_windows pt{ 0, 0, false, 0, &o, zi_view<const uint64_t>{ rows, 2 * entries }, entries,
+                      zi_view<uint8_t>{ windows, segments * ZI_PR_WINDOW }, zi_view<uint32_t>{ sums, segments }, 0, false };
+    S.kind = 0;
+    const zi_result R = zi_run(in, view, 0, o, S, ZI_RUN_STREAM, 0, 0, 1, pt);
+    if (R.err || pt.bad) return ZI_ITEM_DATA;
+    if (R.end > view.n || view.n - R.end != tl) return ZI_ITEM_DATA;           // truncated trailer, or bytes behind it
+    if (pt.k != segments || pt.rows[2 * segments] != pt.end_bit || pt.rows[2 * segments + 1] != R.out) return ZI_ITEM_DATA;
+    pt.cut();                                                                  // the last segment's entry
+    zi_pr_part all{ 0, 0 };
+    for (uint64_t j = 0; j < segments; ++j) {
+        zi_pr_part p;
+        if (!zi_pr_entry_part(kind, pt.sums[j], pt.rows[2 * j + 3] - pt.rows[2 * j + 1], &p)) return ZI_ITEM_DATA;
+        all = zi_pr_join(kind, all, p);
+    }
+    if (all.len != R.out || !zi_pr_trailer_ok(format, view.p + R.end, all)) return ZI_ITEM_DATA;
+    return ZI_ITEM_OK;
+}
+
 }  // namespace zz
