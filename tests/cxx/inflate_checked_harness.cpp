@@ -8,24 +8,13 @@
 //   zch_range   : one call; cks == NULL is the unchecked read. `batch_packets` (0: the device's batch) sends a few KiB through
 //                 several batches; `lanes` (1 or 64) is how many lanes share a packet's sum, each with the device's share of it
 //   zch_sidecar : the sidecar of a buffer, by the same lane sums and zi_cks_public
-#include <cstdint>
-#include <cstring>
-#include <vector>
-#include "../../zzflate_amd/csrc/zz_inflate_core.h"
+#define HARNESS_NAME "inflate_checked_harness"
+#include "harness_lanes.h"
 
 using namespace zz;
 
 namespace {
 
-struct host_in {
-    zi_view<const uint8_t> v;
-    uint64_t peek8(uint64_t pos) const
-    {
-        uint64_t r = 0;
-        for (uint32_t i = 0; i < 8; ++i) if (pos + i < v.n) r |= (uint64_t)v[pos + i] << (8 * i);
-        return r;
-    }
-};
 int tlen(int format) { return format == 0 ? 4 : format == 1 ? 8 : 0; }
 
 // a packet's start-0 partial by `nl` lanes. Adler: lane l takes the 16-byte chunks l, l + nl, ... and the byte l behind the last

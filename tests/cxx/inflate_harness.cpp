@@ -5,24 +5,12 @@
 //   zih_inflate  : a whole zlib / gzip / raw stream, serially (the serial path's run), container and checksum included
 //   zih_packets  : the parallel paths' work done packet by packet -- phase 1 of every packet at its index offsets, then the
 //                  pending bytes resolved by pointer-jumping rounds as the device does them -- and the same checks
-#include <cstdint>
-#include <cstring>
-#include <vector>
-#include "../../zzflate_amd/csrc/zz_inflate_core.h"
+#define HARNESS_NAME "inflate_harness"
+#include "harness_lanes.h"
 
 using namespace zz;
 
 namespace {
-
-struct host_in {
-    zi_view<const uint8_t> v;
-    uint64_t peek8(uint64_t pos) const
-    {
-        uint64_t r = 0;
-        for (uint32_t i = 0; i < 8; ++i) if (pos + i < v.n) r |= (uint64_t)v[pos + i] << (8 * i);
-        return r;
-    }
-};
 
 uint32_t adler(const uint8_t* p, uint64_t n)
 {

@@ -13,40 +13,12 @@
 // its own lane number over the SAME tables, destination, bitmap and pointers. A lane runs alone until it depends on what other
 // lanes wrote -- ZI_LANES_SYNC() in the table builder, the out policy's fence in front of a copy -- and there the next lane runs,
 // round robin: a barrier. Between two barriers the lanes repeat identical writes or write disjoint places, as on the device.
-#include <cstdint>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <ucontext.h>
-#include <vector>
-
-namespace { void lanes_sync(); }
-#define ZI_LANES_SYNC() lanes_sync()
-#include "../../zzflate_amd/csrc/zz_inflate_core.h"
+#define HARNESS_NAME "inflate_points_harness"
+#include "harness_lanes.h"
 
 using namespace zz;
 
 namespace {
-
-constexpr uint32_t MAX_LANES = 64;
-constexpr size_t STACK_BYTES = 256 * 1024;
-
-struct lane_state { ucontext_t ctx; bool done; };
-lane_state g_lane[MAX_LANES];
-ucontext_t g_main;
-uint32_t g_nl = 1, g_cur = 0;
-bool g_sim = false;
-std::vector<uint8_t> g_stacks;
-
-void lanes_sync()
-{
-    if (!g_sim) return;
-    const uint32_t me = g_cur, nx = (me + 1) % g_nl;
-    if (g_lane[nx].done) { fprintf(stderr, "inflate_points_harness: the lanes left their lockstep\n"); abort(); }
-    g_cur = nx;
-    swapcontext(&g_lane[me].ctx, &g_lane[nx].ctx);
-}
-struct host_fence { void operator()() const { lanes_sync(); } };
 
 // one segment's phase 1, as k_inflate_segments sets it up
 struct seg_call {
@@ -70,36 +42,14 @@ void lane_main(int lane)
     c.res[lane] = zi_run(in, c.view, c.b0 >> 3, o, *c.S, ZI_RUN_POINT, c.o1 - c.o0, (uint32_t)lane, g_nl, pt);
     c.end_bit[lane] = pt.end_bit;
     c.npend[lane] = o.npend;
-    g_lane[lane].done = true;
-}
-
-__attribute__((noinline)) void make_lane(uint32_t l)
-{
-    g_lane[l].done = false;
-    getcontext(&g_lane[l].ctx);
-    g_lane[l].ctx.uc_stack.ss_sp = g_stacks.data() + (size_t)l * STACK_BYTES;
-    g_lane[l].ctx.uc_stack.ss_size = STACK_BYTES;
-    g_lane[l].ctx.uc_link = &g_main;
-    makecontext(&g_lane[l].ctx, (void (*)())lane_main, 1, (int)l);
 }
 
 // runs g_seg with `lanes` lanes; false: the lanes disagree (a harness failure)
 bool run_segment(uint32_t lanes)
 {
-    g_nl = lanes;
     memset(g_seg.S, 0xA5, sizeof *g_seg.S);                   // nothing may rely on what the tables held
     g_seg.S->kind = 0;
-    if (lanes == 1) { g_sim = false; lane_main(0); return true; }
-    g_sim = true;
-    if (g_stacks.size() < MAX_LANES * STACK_BYTES) g_stacks.resize(MAX_LANES * STACK_BYTES);
-    for (uint32_t l = 0; l < lanes; ++l) make_lane(l);
-    for (uint32_t l = 0; l < lanes; ++l) {                    // in lockstep: when one returns the others stand at their last barrier
-        if (g_lane[l].done) continue;
-        g_cur = l;
-        swapcontext(&g_main, &g_lane[l].ctx);
-    }
-    g_sim = false;
-    for (uint32_t l = 0; l < lanes; ++l) if (!g_lane[l].done) return false;
+    if (!run_lanes(lanes, lane_main)) return false;
     for (uint32_t l = 1; l < lanes; ++l)
         if (g_seg.res[l].err != g_seg.res[0].err || g_seg.res[l].out != g_seg.res[0].out || g_seg.res[l].final != g_seg.res[0].final ||
             g_seg.end_bit[l] != g_seg.end_bit[0]) return false;

@@ -17,41 +17,14 @@
 // Simulated lanes (lanes = 2..64), as in inflate_points_harness.cpp: every lane is a coroutine running the segment's zi_run with
 // its own lane number over the SAME tables and stage slot; a lane runs alone until it depends on what other lanes wrote --
 // ZI_LANES_SYNC() in the table builder, the out policy's fence in front of a copy -- and there the next lane runs, round robin.
-#include <cstdint>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <ucontext.h>
-#include <vector>
-
-namespace { void lanes_sync(); }
-#define ZI_LANES_SYNC() lanes_sync()
-#include "../../zzflate_amd/csrc/zz_inflate_core.h"
+#define HARNESS_NAME "inflate_points_ranges_harness"
+#include "harness_reads.h"
 
 using namespace zz;
 
 namespace {
 
-constexpr uint32_t MAX_LANES = 64;
-constexpr size_t STACK_BYTES = 256 * 1024;
 constexpr uint32_t FRONT_THREADS = 1024;
-
-struct lane_state { ucontext_t ctx; bool done; };
-lane_state g_lane[MAX_LANES];
-ucontext_t g_main;
-uint32_t g_nl = 1, g_cur = 0;
-bool g_sim = false;
-std::vector<uint8_t> g_stacks;
-
-void lanes_sync()
-{
-    if (!g_sim) return;
-    const uint32_t me = g_cur, nx = (me + 1) % g_nl;
-    if (g_lane[nx].done) { fprintf(stderr, "inflate_points_ranges_harness: the lanes left their lockstep\n"); abort(); }
-    g_cur = nx;
-    swapcontext(&g_lane[me].ctx, &g_lane[nx].ctx);
-}
-struct host_fence { void operator()() const { lanes_sync(); } };
 
 // one segment's run, as k_inflate_segments_win sets it up
 struct seg_call {
@@ -73,49 +46,19 @@ void lane_main(int lane)
     c.res[lane] = zi_run(in, c.view, c.d.b0 >> 3, o, *c.S, ZI_RUN_POINT, c.d.room, (uint32_t)lane, g_nl, pt);
     c.end_bit[lane] = pt.end_bit;
     c.from_win[lane] = o.from_win;
-    g_lane[lane].done = true;
-}
-
-__attribute__((noinline)) void make_lane(uint32_t l)
-{
-    g_lane[l].done = false;
-    getcontext(&g_lane[l].ctx);
-    g_lane[l].ctx.uc_stack.ss_sp = g_stacks.data() + (size_t)l * STACK_BYTES;
-    g_lane[l].ctx.uc_stack.ss_size = STACK_BYTES;
-    g_lane[l].ctx.uc_link = &g_main;
-    makecontext(&g_lane[l].ctx, (void (*)())lane_main, 1, (int)l);
 }
 
 // runs g_seg with `lanes` lanes; false: the lanes disagree (a harness failure)
 bool run_segment(uint32_t lanes)
 {
-    g_nl = lanes;
     memset(g_seg.S, 0xA5, sizeof *g_seg.S);                   // nothing may rely on what the tables held
     g_seg.S->kind = 0;
-    if (lanes == 1) { g_sim = false; lane_main(0); return true; }
-    g_sim = true;
-    if (g_stacks.size() < MAX_LANES * STACK_BYTES) g_stacks.resize(MAX_LANES * STACK_BYTES);
-    for (uint32_t l = 0; l < lanes; ++l) make_lane(l);
-    for (uint32_t l = 0; l < lanes; ++l) {                    // in lockstep: when one returns the others stand at their last barrier
-        if (g_lane[l].done) continue;
-        g_cur = l;
-        swapcontext(&g_main, &g_lane[l].ctx);
-    }
-    g_sim = false;
-    for (uint32_t l = 0; l < lanes; ++l) if (!g_lane[l].done) return false;
+    if (!run_lanes(lanes, lane_main)) return false;
     for (uint32_t l = 1; l < lanes; ++l)
         if (g_seg.res[l].err != g_seg.res[0].err || g_seg.res[l].out != g_seg.res[0].out || g_seg.res[l].final != g_seg.res[0].final ||
             g_seg.end_bit[l] != g_seg.end_bit[0]) return false;
     return true;
 }
-
-// zi_adler_lanes / zi_crc_lanes with one lane
-struct one_lane {
-    uint64_t sum(uint64_t v) const { return v; }
-    uint32_t fold_xor(uint32_t v) const { return v; }
-};
-
-template <class T> zi_view<const T> view_of(const std::vector<T>& v) { return zi_view<const T>{ v.data(), v.size() }; }
 
 // k_pr_front's fold: thread t joins the entries [t * per, (t + 1) * per), a tree joins the threads in order
 bool fold(int kind, const zi_view<const uint32_t>& sums, const std::vector<uint64_t>& lens, zi_pr_part* all)
@@ -201,97 +144,38 @@ extern "C" int zpr_reads(const uint8_t* src_in, uint64_t src_len, int format, co
         if (!ok) index_bad = true;
     }
     if (index_bad) {
-        for (uint64_t r = 0; r < nranges; ++r) { out_lens[r] = ~0ull; if (status) status[r] = ZI_RV_DATA; }
+        reads_all_fail(nranges, out_lens, status);
         return hl == -2 ? ZI_RV_UNSUPPORTED : ZI_RV_DATA;
     }
     const std::vector<uint8_t> defl(src.begin() + hl, src.begin() + hl + sn);     // exactly the DEFLATE bytes
-    // plan
-    std::vector<zi_mr_read> reads(nranges);
-    std::vector<int32_t> diff(entries, 0);
-    for (uint64_t r = 0; r < nranges; ++r) {
-        reads[r] = zi_mr_plan(idx, entries, firsts[r], nbytes[r], caps[r]);
-        if (reads[r].any) { ++diff.at(reads[r].j0); --diff.at((uint64_t)reads[r].j1 + 1); }
-    }
-    // touched
-    std::vector<uint32_t> cnt(entries, 0), tlist, G;
-    std::vector<uint64_t> S;
-    int64_t cov = 0; uint64_t room_sum = 0; uint32_t nbig = 0;
-    for (uint64_t j = 0; j < segments; ++j) {
-        cov += diff[j];
-        cnt[j] = (uint32_t)tlist.size();
-        const uint64_t room = zi_mr_room(idx, j);
-        const uint32_t k = zi_mr_touch(room, cov > 0 ? 1 : 0);
-        if (!k) continue;
-        tlist.push_back((uint32_t)j | (k == 2 ? ZI_MR_BIG : 0u));
-        S.push_back(room_sum); G.push_back(nbig);
-        if (k == 2) ++nbig; else room_sum += room;
-    }
-    const uint64_t T = tlist.size();
-    cnt[segments] = (uint32_t)T;
-    S.push_back(room_sum); G.push_back(nbig);
-    std::vector<uint32_t> F(T + 1, 0);
-    const zi_mr_tables tab{ idx, view_of(cnt), view_of(tlist), view_of(S), view_of(F), view_of(G) };
-    // waves
-    if (T) {
-        const uint64_t nwaves = zi_mr_wave(S[T - 1]) + 1;
-        std::vector<uint64_t> first_rank(nwaves + 1, T);
-        for (uint64_t w = 0; w < nwaves; ++w) first_rank[w] = zi_mr_wave_first(view_of(S), T, w * ZZ_MR_STAGE);
-        std::vector<zi_tables> tables(1);
-        one_lane one;
-        for (uint64_t w = 0; w < nwaves; ++w) {
-            const uint64_t t0 = first_rank[w], t1 = first_rank[w + 1];
-            if (t1 <= t0) continue;
-            ++*waves;
-            std::vector<uint8_t> stage(S[t1] - S[t0], 0xCD);                      // exactly the wave's rooms
-            if (stage.size() >= 2 * ZZ_MR_STAGE) { fprintf(stderr, "inflate_points_ranges_harness: a wave of two stages\n"); abort(); }
-            for (uint64_t t = t0; t < t1; ++t) {
-                const zi_pr_slot d = zi_pr_desc(tab, entries, t, t0);
-                int st = ZI_ITEM_DATA;
-                uint64_t out = ~0ull;
-                if (!d.skip) {
-                    const zi_view<uint8_t> whole{ stage.data(), stage.size() };
-                    if (d.room) (void)whole[d.stage_off + d.room - 1];           // the slot lies inside the stage
-                    (void)view_of(windows)[d.seg * ZI_PR_WINDOW + ZI_PR_WINDOW - 1];     // the window slot lies inside the windows
-                    g_seg.view = view_of(defl);
-                    g_seg.d = d;
-                    g_seg.slot = zi_view<uint8_t>{ stage.data() + d.stage_off, d.room };
-                    g_seg.win = zi_view<const uint8_t>{ windows.data() + d.seg * ZI_PR_WINDOW, ZI_PR_WINDOW };
-                    g_seg.S = &tables[0];
-                    if (!run_segment(lanes)) return -100;
-                    const zi_result& R = g_seg.res[0];
-                    uint32_t sum = 0;
-                    if (!R.err) {
-                        if (g_seg.end_bit[0] != d.b1 || R.out != d.room) return -100;    // (ZI_RUN_POINT's own promise)
-                        const zi_view<const uint8_t> slot{ stage.data() + d.stage_off, d.room };
-                        sum = kind == ZI_CKS_ADLER ? zi_adler_lanes(one, slot, d.room, 0, 1) : zi_crc_lanes(one, slot, d.room, 0, 1);
-                    }
-                    st = zi_pr_segment_status(R.err, R.out, d.room, sum, view_of(sums)[d.seg]);
-                    if (st == ZI_ITEM_OK) out = R.out;
-                    if (win_copied) for (uint32_t l = 0; l < lanes; ++l) win_copied[d.seg] += g_seg.from_win[l];
-                    ++*segments_decoded;
-                }
-                F[t + 1] = F[t] + (zi_mr_member_bad(tlist[t], st, out, d.room) ? 1u : 0u);
+    // the rest is harness_reads.h's; per touched segment: its rows, ZI_RUN_POINT onto its slot against its window slot, its sum
+    std::vector<zi_tables> tables(1);
+    const host_lanes one{ 0 };                                                    // zi_adler_lanes / zi_crc_lanes with one lane
+    return reads_through_index(idx, entries, nranges, firsts, nbytes, dsts, caps, out_lens, status, waves,
+        [&](const zi_mr_tables& tab, uint64_t t, uint64_t t0, std::vector<uint8_t>& stage, unit_result* u) {
+            const zi_pr_slot d = zi_pr_desc(tab, entries, t, t0);
+            *u = unit_result{ ZI_ITEM_DATA, ~0ull, d.room };
+            if (d.skip) return true;
+            const zi_view<uint8_t> whole{ stage.data(), stage.size() };
+            if (d.room) (void)whole[d.stage_off + d.room - 1];                   // the slot lies inside the stage
+            (void)view_of(windows)[d.seg * ZI_PR_WINDOW + ZI_PR_WINDOW - 1];     // the window slot lies inside the windows
+            g_seg.view = view_of(defl);
+            g_seg.d = d;
+            g_seg.slot = zi_view<uint8_t>{ stage.data() + d.stage_off, d.room };
+            g_seg.win = zi_view<const uint8_t>{ windows.data() + d.seg * ZI_PR_WINDOW, ZI_PR_WINDOW };
+            g_seg.S = &tables[0];
+            if (!run_segment(lanes)) return false;
+            const zi_result& R = g_seg.res[0];
+            uint32_t sum = 0;
+            if (!R.err) {
+                if (g_seg.end_bit[0] != d.b1 || R.out != d.room) return false;   // (ZI_RUN_POINT's own promise)
+                const zi_view<const uint8_t> slot{ stage.data() + d.stage_off, d.room };
+                sum = kind == ZI_CKS_ADLER ? zi_adler_lanes(one, slot, d.room, 0, 1) : zi_crc_lanes(one, slot, d.room, 0, 1);
             }
-            // cut and copy, chunk by chunk
-            for (uint64_t r = 0; r < nranges; ++r) {
-                const zi_mr_piece p = zi_mr_cut(reads[r], firsts[r], tab, t0, t1);
-                const uint64_t room = reads[r].m < caps[r] ? reads[r].m : caps[r];
-                const zi_view<uint8_t> d{ dsts[r], room };
-                const zi_view<const uint8_t> st{ stage.data(), stage.size() };
-                for (uint64_t k = 0; k < zi_mr_chunks(p.len); ++k) {
-                    const uint64_t at = k * ZZ_MR_CHUNK, n = p.len - at < ZZ_MR_CHUNK ? p.len - at : ZZ_MR_CHUNK;
-                    for (uint64_t i = 0; i < n; ++i) d[p.dst_off + at + i] = st[p.stage_off + at + i];
-                }
-            }
-        }
-    }
-    // verdict
-    uint64_t n_data = 0, n_unsupported = 0, n_arg = 0, n_nospace = 0;
-    for (uint64_t r = 0; r < nranges; ++r) {
-        const int v = zi_mr_verdict(reads[r], tab);
-        out_lens[r] = v == ZI_RV_OK ? reads[r].m : ~0ull;
-        if (status) status[r] = v;
-        n_data += v == ZI_RV_DATA; n_unsupported += v == ZI_RV_UNSUPPORTED; n_arg += v == ZI_RV_ARG; n_nospace += v == ZI_RV_NOSPACE;
-    }
-    return n_data ? ZI_RV_DATA : n_unsupported ? ZI_RV_UNSUPPORTED : n_arg ? ZI_RV_ARG : n_nospace ? ZI_RV_NOSPACE : ZI_RV_OK;
+            u->status = zi_pr_segment_status(R.err, R.out, d.room, sum, view_of(sums)[d.seg]);
+            if (u->status == ZI_ITEM_OK) u->out = R.out;
+            if (win_copied) for (uint32_t l = 0; l < lanes; ++l) win_copied[d.seg] += g_seg.from_win[l];
+            ++*segments_decoded;
+            return true;
+        });
 }

@@ -5,24 +5,13 @@
 // -fsanitize=undefined -DZZ_INFLATE_CHECKED and calls it through ctypes.
 //
 //   zrh_range : one call; `batch_packets` (0: the device's batch) lets a test send a few KiB through several batches
-#include <cstdint>
-#include <cstring>
-#include <vector>
-#include "../../zzflate_amd/csrc/zz_inflate_core.h"
+#define HARNESS_NAME "inflate_range_harness"
+#include "harness_lanes.h"
 
 using namespace zz;
 
 namespace {
 
-struct host_in {
-    zi_view<const uint8_t> v;
-    uint64_t peek8(uint64_t pos) const
-    {
-        uint64_t r = 0;
-        for (uint32_t i = 0; i < 8; ++i) if (pos + i < v.n) r |= (uint64_t)v[pos + i] << (8 * i);
-        return r;
-    }
-};
 int tlen(int format) { return format == 0 ? 4 : format == 1 ? 8 : 0; }
 
 struct attempt_result { int rc; uint64_t ext, pending, L; bool saw_last; };

@@ -7,24 +7,13 @@
 //
 //   zrs_ranges : one call; `wave_packets` (0: the device's batch) and `limit_packets` (0: the device's batch) let a test send a
 //                few reads through several waves and meet the per-read limit with a few KiB
-#include <cstdint>
-#include <cstring>
-#include <vector>
-#include "../../zzflate_amd/csrc/zz_inflate_core.h"
+#define HARNESS_NAME "inflate_ranges_harness"
+#include "harness_lanes.h"
 
 using namespace zz;
 
 namespace {
 
-struct host_in {
-    zi_view<const uint8_t> v;
-    uint64_t peek8(uint64_t pos) const
-    {
-        uint64_t r = 0;
-        for (uint32_t i = 0; i < 8; ++i) if (pos + i < v.n) r |= (uint64_t)v[pos + i] << (8 * i);
-        return r;
-    }
-};
 int tlen(int format) { return format == 0 ? 4 : format == 1 ? 8 : 0; }
 uint32_t ceil_log2(uint64_t x) { uint32_t r = 0; while ((1ull << r) < x) ++r; return r; }
 

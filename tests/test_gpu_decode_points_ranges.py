@@ -340,6 +340,45 @@ def test_the_encoders_and_the_other_decoders_last_state_is_left_alone(torch, ctx
     assert gzip.decompress(mdst[:mw].cpu().numpy().tobytes()) == d
 
 
+def test_member_reads_and_point_reads_take_turns_on_one_context(torch, sidecars):
+    """The two calls share one workspace. A member call with an index of a few entries and four reads, a point call whose index
+    and reads are more and whose rooms are more (every buffer sized by entries, reads, a wave's units or a wave's bytes grows
+    between the calls), the member call again: bytes, lengths, statuses and codes are those of fresh contexts, and the member
+    reads' stats outlive the point call."""
+    d = pc.data_of("alice")
+    src = dev(torch, d)
+    mcap = zz.members_bound(len(d))
+    mdst = torch.zeros(mcap, dtype=torch.uint8, device="cuda")
+    mw = zz.Context(0).encode_members(src, len(d), mdst, mcap, level=1)
+    index = zz.Context(0).members_index(mdst, mw)
+    mreads, mcaps = [(10, 100), (100, 50), (len(d) - 20, 100), (5000, 300)], [100, 50, 100, 299]     # (the first and the last member)
+    s, fmt, data = pc.case("alice_mem1")
+    rows, windows, sums = sidecars("alice_mem1", 4096)
+    preads = prc.reads_for(rows)
+    assert len(rows) > index.shape[0] and len(preads) > len(mreads) and len(prc.touched(rows, 0, len(data))) > index.shape[0] - 1
+
+    def members(c):
+        outs = [torch.full((n,), 0xEE, dtype=torch.uint8, device="cuda") for _, n in mreads]
+        lens, status = c.decode_members_ranges(mdst, mw, index, [f for f, _ in mreads], [n for _, n in mreads], outs, mcaps)
+        code = next((v for v in (prc.DATA, prc.UNSUPPORTED, prc.ARG, prc.NOSPACE) if v in status), prc.OK)
+        return lens, status, code, [o.cpu().numpy().tobytes() for o in outs], c.last_decode_members_ranges_stats()
+
+    def points(c):
+        g = run(torch, c, s, fmt, rows, windows, sums, preads)
+        return g.lens, g.status, g.code, g.outs, (g.segments_decoded, g.waves)
+
+    fresh_m, fresh_p = members(zz.Context(0)), points(zz.Context(0))
+    assert fresh_m[:3] == ([100, 50, 20, None], [prc.OK, prc.OK, prc.OK, prc.NOSPACE], prc.NOSPACE)
+    assert [o[:m] for o, m, (f, _) in zip(fresh_m[3], fresh_m[0], mreads) if m is not None] == [d[f: f + m] for (f, _), m in zip(mreads, fresh_m[0]) if m is not None]
+    assert fresh_m[4][0] >= 2 and fresh_p[4][0] > fresh_m[4][0] and prc.OK in fresh_p[1]
+    one = zz.Context(0)
+    assert members(one) == fresh_m
+    assert points(one) == fresh_p
+    assert one.last_decode_members_ranges_stats() == fresh_m[4]
+    assert members(one) == fresh_m
+    assert one.last_decode_points_ranges_stats() == fresh_p[4]
+
+
 @pytest.fixture(scope="module")
 def big():
     """96 MiB across a real wave edge (64 MiB of rooms): the periodic pattern with alice29.txt spliced in every 8 MiB, zlib level 1"""

@@ -210,9 +210,9 @@ struct zz_ctx {
             zz_buf<zz_inf_members_out> sres; zz_pin<zz_inf_members_out> h_sres;
             uint64_t members = 0, candidates = 0; int path = 0;
         } mem;
-        // zz_decode_members_ranges_device (zz_inflate_members_ranges.h): the stage, per read (record, chunk scan), per member
-        // (differences, counts), per touched member (list, S, F, G), per item of a wave its status, per wave two words, what the
-        // host reads; k_inflate_items' descriptors are mem's
+        // the reads through an index (dec_reads; zz_inflate_members_ranges.h): the stage, per read (record, chunk scan), per unit
+        // (differences, counts), per touched unit (list, S, F, G), per unit of a wave its status, per wave two words, what the
+        // host reads; a wave's rooms and lengths (and k_inflate_items' descriptors) are mem's
         struct {
             zz_buf<uint8_t> stage;
             zz_buf<zi_mr_read> reads; zz_buf<uint64_t> chunk0;
@@ -220,12 +220,13 @@ struct zz_ctx {
             zz_buf<int32_t> status;
             zz_buf<uint64_t> waves; zz_pin<uint64_t> h_waves;
             zz_buf<zz_mr_state> st; zz_pin<zz_mr_state> h_st;
-            uint64_t members_decoded = 0; uint32_t waves_run = 0;
-        } mr;
-        // zz_decode_points_ranges_device (zz_inflate_points_ranges.h): what its front leaves; everything else is mr's and mem's
+        } rd;
+        // what the last zz_decode_members_ranges_device did
+        struct { uint64_t decoded = 0; uint32_t waves_run = 0; } mr;
+        // zz_decode_points_ranges_device (zz_inflate_points_ranges.h): what its front leaves, and what the last call did
         struct {
             zz_buf<zz_pr_state> st; zz_pin<zz_pr_state> h_st;
-            uint64_t segments_decoded = 0; uint32_t waves_run = 0;
+            uint64_t decoded = 0; uint32_t waves_run = 0;
         } pr;
     } dec;
 };
@@ -2552,6 +2553,101 @@ extern "C" int zz_members_index_device(zz_ctx* c, const void* d_src_v, uint64_t 
     return ZZ_OK;
 }
 
+// ---- reads through an index: the one procedure of zz_decode_members_ranges_device and zz_decode_points_ranges_device ------------
+// What a call says of itself: its unit's name, the tail of the "not what ... say" message, the text when the index is refused (a
+// front may replace it in RD_JUDGE), and where its stats go.
+struct rd_call {
+    const char* unit; const char* not_what; const char* index_bad;
+    uint64_t* decoded; uint32_t* waves_run;
+};
+// A call's front keeps a state of its own beside the shared one (rd.st) and goes where that goes: grown, cleared, filled between
+// check and plan, read back in front of the one wait, judged behind it -- in front of the index's own verdict.
+enum rd_step { RD_GROW, RD_CLEAR, RD_ENQUEUE, RD_READ, RD_JUDGE };
+static dim3 rd_grid(uint64_t n) { return dim3((uint32_t)std::min<uint64_t>((n + 255) / 256, 4096)); }
+
+// Q holds the caller's side (source and its bound, index, reads); the workspace's side is filled here. front(step, Q) -> code;
+// wave(Q, t0, t1, enqueue) -> code: the decode of the touched ranks [t0, t1) onto the stage, rooms and lengths into mem.caps /
+// mem.out_lens, statuses into rd.status; enqueue == false: only grow what a wave of t1 - t0 ranks needs.
+template <class Front, class Wave>
+static int dec_reads(zz_ctx* c, hipStream_t st, zz_mr_params Q, rd_call& N, Front front, Wave wave)
+{
+    auto& R = c->dec.rd;
+    auto& M = c->dec.mem;
+    *N.decoded = 0; *N.waves_run = 0;
+    const uint64_t entries = Q.entries, nranges = Q.nranges;
+    if (int rc = R.st.grow(1)) return rc;
+    if (int rc = R.h_st.grow(1)) return rc;
+    if (int rc = front(RD_GROW, Q)) return rc;
+    if (int rc = R.reads.grow(nranges)) return rc;
+    if (int rc = R.chunk0.grow(nranges + 1)) return rc;
+    if (int rc = R.diff.grow(entries)) return rc;
+    if (int rc = R.cnt.grow(entries)) return rc;
+    if (int rc = R.tlist.grow(entries)) return rc;
+    if (int rc = R.S.grow(entries)) return rc;
+    if (int rc = R.F.grow(entries)) return rc;
+    if (int rc = R.G.grow(entries)) return rc;
+    Q.reads = R.reads; Q.chunk0 = R.chunk0; Q.diff = R.diff; Q.cnt = R.cnt; Q.tlist = R.tlist; Q.S = R.S; Q.F = R.F; Q.G = R.G;
+    Q.stage = nullptr; Q.st = R.st;
+
+    // check, front, plan, touched: one readback
+    HIPCHK(hipMemsetAsync(R.st, 0, sizeof(zz_mr_state), st));
+    if (int rc = front(RD_CLEAR, Q)) return rc;
+    HIPCHK(hipMemsetAsync(R.diff, 0, entries * sizeof(int32_t), st));
+    hipLaunchKernelGGL(k_mr_check, rd_grid(entries), dim3(256), 0, st, Q);
+    if (int rc = front(RD_ENQUEUE, Q)) return rc;
+    hipLaunchKernelGGL(k_mr_plan, rd_grid(nranges), dim3(256), 0, st, Q);
+    hipLaunchKernelGGL(k_mr_touched, dim3(1), dim3(ZZ_MR_SCAN_THREADS), 0, st, Q);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(R.h_st, R.st, sizeof(zz_mr_state), hipMemcpyDeviceToHost, st));
+    if (int rc = front(RD_READ, Q)) return rc;
+    HIPCHK(hipStreamSynchronize(st));
+    if (int rc = front(RD_JUDGE, Q)) return rc;
+    if (R.h_st->index_bad) { set_err(N.index_bad); return ZZ_E_DATA; }
+    const uint64_t touched = R.h_st->touched, nwaves = R.h_st->nwaves;
+    if (touched) {
+        // the waves' first ranks and S there: one readback
+        if (int rc = R.waves.grow(2 * (nwaves + 1))) return rc;
+        if (int rc = R.h_waves.grow(2 * (nwaves + 1))) return rc;
+        hipLaunchKernelGGL(k_mr_waves, rd_grid(nwaves + 1), dim3(256), 0, st, Q, nwaves, (uint64_t*)R.waves);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(R.h_waves, R.waves, 2 * (nwaves + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        const uint64_t* W = R.h_waves.p;
+        uint64_t big_items = 0, big_bytes = 0;
+        for (uint64_t w = 0; w < nwaves; ++w) {
+            big_items = std::max(big_items, W[2 * w + 2] - W[2 * w]);
+            big_bytes = std::max(big_bytes, W[2 * w + 3] - W[2 * w + 1]);
+        }
+        if (int rc = R.stage.grow(big_bytes + 16)) return rc;
+        if (int rc = wave(Q, 0, big_items, false)) return rc;
+        if (int rc = R.status.grow(big_items)) return rc;
+        Q.stage = R.stage;
+        for (uint64_t w = 0; w < nwaves; ++w) {
+            const uint64_t t0 = W[2 * w], t1 = W[2 * w + 2];
+            if (t1 <= t0) continue;                                     // (cannot happen: a room is at most one wave's)
+            ++*N.waves_run;
+            if (int rc = wave(Q, t0, t1, true)) return rc;
+            hipLaunchKernelGGL(k_mr_judge, dim3(1), dim3(ZZ_MR_SCAN_THREADS), 0, st, Q, t0, t1, (const uint64_t*)M.caps, (const uint64_t*)M.out_lens,
+                               (const int32_t*)R.status);
+            hipLaunchKernelGGL(k_mr_cut, dim3(1), dim3(ZZ_MR_SCAN_THREADS), 0, st, Q, t0, t1);
+            hipLaunchKernelGGL(k_mr_copy, dim3(ZZ_MR_COPY_GRID), dim3(256), 0, st, Q, t0, t1);
+            HIPCHK(hipGetLastError());
+        }
+        *N.decoded = touched - R.h_st->big;
+    }
+    hipLaunchKernelGGL(k_mr_verdict, rd_grid(nranges), dim3(256), 0, st, Q);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(R.h_st, R.st, sizeof(zz_mr_state), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    const zz_mr_state& T = *R.h_st.p;
+    const std::string touch = std::string(" touch a ") + N.unit;
+    if (T.n_data) { set_err("reads: " + std::to_string(T.n_data) + touch + " that is not what " + N.not_what); return ZZ_E_DATA; }
+    if (T.n_unsupported) { set_err("reads: " + std::to_string(T.n_unsupported) + touch + " whose room exceeds the stage (64 MiB)"); return ZZ_E_UNSUPPORTED; }
+    if (T.n_arg) { set_err("reads: " + std::to_string(T.n_arg) + " start behind the decoded length or overflow"); return ZZ_E_ARG; }
+    if (T.n_nospace) { set_err("reads: " + std::to_string(T.n_nospace) + " do not fit their destinations"); return ZZ_E_NOSPACE; }
+    return ZZ_OK;
+}
+
 extern "C" int zz_decode_members_ranges_device(zz_ctx* c, const void* d_src_v, uint64_t src_len, const uint64_t* d_index, uint64_t entries,
                                                uint64_t nranges, const uint64_t* d_firsts, const uint64_t* d_nbytes,
                                                void* const* d_dsts, const uint64_t* d_caps,
@@ -2565,92 +2661,28 @@ extern "C" int zz_decode_members_ranges_device(zz_ctx* c, const void* d_src_v, u
     if (call_pending(c)) return ZZ_E_ARG;
     HIPCHK(hipSetDevice(c->device));
     hipStream_t st = (hipStream_t)hip_stream;
-    auto& R = c->dec.mr;
     auto& M = c->dec.mem;
-    R.members_decoded = 0; R.waves_run = 0;
-    const uint64_t members = entries - 1;
-    if (int rc = R.st.grow(1)) return rc;
-    if (int rc = R.h_st.grow(1)) return rc;
-    if (int rc = R.reads.grow(nranges)) return rc;
-    if (int rc = R.chunk0.grow(nranges + 1)) return rc;
-    if (int rc = R.diff.grow(entries)) return rc;
-    if (int rc = R.cnt.grow(entries)) return rc;
-    if (int rc = R.tlist.grow(entries)) return rc;
-    if (int rc = R.S.grow(entries)) return rc;
-    if (int rc = R.F.grow(entries)) return rc;
-    if (int rc = R.G.grow(entries)) return rc;
     zz_mr_params Q;
     Q.src = (const uint8_t*)d_src_v; Q.src_len = src_len; Q.idx = d_index; Q.entries = entries;
     Q.nranges = nranges; Q.firsts = d_firsts; Q.nbytes = d_nbytes; Q.dsts = (uint8_t* const*)d_dsts; Q.caps = d_caps;
     Q.out_lens = d_out_lens; Q.status = d_status;
-    Q.reads = R.reads; Q.chunk0 = R.chunk0; Q.diff = R.diff; Q.cnt = R.cnt; Q.tlist = R.tlist; Q.S = R.S; Q.F = R.F; Q.G = R.G;
-    Q.stage = nullptr; Q.st = R.st;
-    const auto grid = [](uint64_t n) { return dim3((uint32_t)std::min<uint64_t>((n + 255) / 256, 4096)); };
-
-    // check, plan, touched: one readback
-    HIPCHK(hipMemsetAsync(R.st, 0, sizeof(zz_mr_state), st));
-    HIPCHK(hipMemsetAsync(R.diff, 0, entries * sizeof(int32_t), st));
-    hipLaunchKernelGGL(k_mr_check, grid(entries), dim3(256), 0, st, Q);
-    hipLaunchKernelGGL(k_mr_plan, grid(nranges), dim3(256), 0, st, Q);
-    hipLaunchKernelGGL(k_mr_touched, dim3(1), dim3(ZZ_MR_SCAN_THREADS), 0, st, Q);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(R.h_st, R.st, sizeof(zz_mr_state), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    if (R.h_st->index_bad) {
-        set_err("reads: all fail, the index is not an index of this file (decoded offsets from 0 ascending, file offsets strictly ascending and inside the source)");
-        return ZZ_E_DATA;
-    }
-    const uint64_t touched = R.h_st->touched, nwaves = R.h_st->nwaves;
-    if (touched) {
-        // the waves' first ranks and S there: one readback
-        if (int rc = R.waves.grow(2 * (nwaves + 1))) return rc;
-        if (int rc = R.h_waves.grow(2 * (nwaves + 1))) return rc;
-        hipLaunchKernelGGL(k_mr_waves, grid(nwaves + 1), dim3(256), 0, st, Q, nwaves, (uint64_t*)R.waves);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(R.h_waves, R.waves, 2 * (nwaves + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        const uint64_t* W = R.h_waves.p;
-        uint64_t big_items = 0, big_bytes = 0;
-        for (uint64_t w = 0; w < nwaves; ++w) {
-            big_items = std::max(big_items, W[2 * w + 2] - W[2 * w]);
-            big_bytes = std::max(big_bytes, W[2 * w + 3] - W[2 * w + 1]);
-        }
-        if (int rc = R.stage.grow(big_bytes + 16)) return rc;
-        if (int rc = ensure_member_items(c, big_items)) return rc;
-        if (int rc = R.status.grow(big_items)) return rc;
-        Q.stage = R.stage;
-        for (uint64_t w = 0; w < nwaves; ++w) {
-            const uint64_t t0 = W[2 * w], t1 = W[2 * w + 2];
-            if (t1 <= t0) continue;                                     // (cannot happen: a room is at most one wave's)
-            ++R.waves_run;
-            hipLaunchKernelGGL(k_mr_desc, grid(t1 - t0), dim3(256), 0, st, Q, t0, t1, (const uint8_t**)M.srcs.p, (uint64_t*)M.src_lens,
+    rd_call N{ "member", "the index says",
+               "reads: all fail, the index is not an index of this file (decoded offsets from 0 ascending, file offsets strictly ascending and inside the source)",
+               &c->dec.mr.decoded, &c->dec.mr.waves_run };
+    return dec_reads(c, st, Q, N, [](rd_step, const zz_mr_params&) { return ZZ_OK; },               // (no front)
+        [&](const zz_mr_params& Q, uint64_t t0, uint64_t t1, bool enqueue) -> int {
+            if (!enqueue) return ensure_member_items(c, t1 - t0);
+            // descriptors from the index, then k_inflate_items as zz_decode_batch_device launches it
+            hipLaunchKernelGGL(k_mr_desc, rd_grid(t1 - t0), dim3(256), 0, st, Q, t0, t1, (const uint8_t**)M.srcs.p, (uint64_t*)M.src_lens,
                                (uint8_t**)M.dsts.p, (uint64_t*)M.caps);
             HIPCHK(hipGetLastError());
-            if (int rc = dec_items(c, member_items_params(c, (uint32_t)(t1 - t0), R.status), st)) return rc;
-            hipLaunchKernelGGL(k_mr_judge, dim3(1), dim3(ZZ_MR_SCAN_THREADS), 0, st, Q, t0, t1, (const uint64_t*)M.caps, (const uint64_t*)M.out_lens,
-                               (const int32_t*)R.status);
-            hipLaunchKernelGGL(k_mr_cut, dim3(1), dim3(ZZ_MR_SCAN_THREADS), 0, st, Q, t0, t1);
-            hipLaunchKernelGGL(k_mr_copy, dim3(ZZ_MR_COPY_GRID), dim3(256), 0, st, Q, t0, t1);
-            HIPCHK(hipGetLastError());
-        }
-        R.members_decoded = touched - R.h_st->big;
-    }
-    hipLaunchKernelGGL(k_mr_verdict, grid(nranges), dim3(256), 0, st, Q);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(R.h_st, R.st, sizeof(zz_mr_state), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    const zz_mr_state& T = *R.h_st.p;
-    if (T.n_data) { set_err("reads: " + std::to_string(T.n_data) + " touch a member that is not what the index says"); return ZZ_E_DATA; }
-    if (T.n_unsupported) { set_err("reads: " + std::to_string(T.n_unsupported) + " touch a member whose room exceeds the stage (64 MiB)"); return ZZ_E_UNSUPPORTED; }
-    if (T.n_arg) { set_err("reads: " + std::to_string(T.n_arg) + " start behind the decoded length or overflow"); return ZZ_E_ARG; }
-    if (T.n_nospace) { set_err("reads: " + std::to_string(T.n_nospace) + " do not fit their destinations"); return ZZ_E_NOSPACE; }
-    return ZZ_OK;
+            return dec_items(c, member_items_params(c, (uint32_t)(t1 - t0), c->dec.rd.status), st);
+        });
 }
-
 extern "C" int zz_ctx_last_decode_members_ranges_stats(const zz_ctx* c, uint64_t* members_decoded, uint32_t* waves)
 {
     if (!c) { set_err("null context"); return ZZ_E_ARG; }
-    if (members_decoded) *members_decoded = c->dec.mr.members_decoded;
+    if (members_decoded) *members_decoded = c->dec.mr.decoded;
     if (waves) *waves = c->dec.mr.waves_run;
     return ZZ_OK;
 }
@@ -2687,104 +2719,56 @@ extern "C" int zz_decode_points_ranges_device(zz_ctx* c, const void* d_src_v, ui
     if (call_pending(c)) return ZZ_E_ARG;
     HIPCHK(hipSetDevice(c->device));
     hipStream_t st = (hipStream_t)hip_stream;
-    auto& R = c->dec.mr;                                            // (its buffers; its stats are the member reads' and stay)
+    auto& R = c->dec.rd;
     auto& M = c->dec.mem;
     auto& X = c->dec.pr;
-    X.segments_decoded = 0; X.waves_run = 0;
-    if (int rc = R.st.grow(1)) return rc;
-    if (int rc = R.h_st.grow(1)) return rc;
-    if (int rc = X.st.grow(1)) return rc;
-    if (int rc = X.h_st.grow(1)) return rc;
-    if (int rc = R.reads.grow(nranges)) return rc;
-    if (int rc = R.chunk0.grow(nranges + 1)) return rc;
-    if (int rc = R.diff.grow(entries)) return rc;
-    if (int rc = R.cnt.grow(entries)) return rc;
-    if (int rc = R.tlist.grow(entries)) return rc;
-    if (int rc = R.S.grow(entries)) return rc;
-    if (int rc = R.F.grow(entries)) return rc;
-    if (int rc = R.G.grow(entries)) return rc;
     zz_mr_params Q;
     Q.src = (const uint8_t*)d_src_v; Q.idx = d_points; Q.entries = entries;
     Q.src_len = src_len > (~0ull >> 3) ? ~0ull : 8 * src_len;       // k_mr_check's bound on the last row: a bit inside the source (k_pr_front is exact)
     Q.nranges = nranges; Q.firsts = d_firsts; Q.nbytes = d_nbytes; Q.dsts = (uint8_t* const*)d_dsts; Q.caps = d_caps;
     Q.out_lens = d_out_lens; Q.status = d_status;
-    Q.reads = R.reads; Q.chunk0 = R.chunk0; Q.diff = R.diff; Q.cnt = R.cnt; Q.tlist = R.tlist; Q.S = R.S; Q.F = R.F; Q.G = R.G;
-    Q.stage = nullptr; Q.st = R.st;
     zz_pr_params P;
     P.src = (const uint8_t*)d_src_v; P.src_len = src_len; P.format = format; P.windows = (const uint8_t*)d_windows; P.sums = d_sums;
-    P.ps = X.st; P.rooms = nullptr; P.out_lens = nullptr; P.status = nullptr;
-    const auto grid = [](uint64_t n) { return dim3((uint32_t)std::min<uint64_t>((n + 255) / 256, 4096)); };
-
-    // check, front, plan, touched: one readback
-    HIPCHK(hipMemsetAsync(R.st, 0, sizeof(zz_mr_state), st));
-    HIPCHK(hipMemsetAsync(X.st, 0, sizeof(zz_pr_state), st));
-    HIPCHK(hipMemsetAsync(R.diff, 0, entries * sizeof(int32_t), st));
-    hipLaunchKernelGGL(k_mr_check, grid(entries), dim3(256), 0, st, Q);
-    hipLaunchKernelGGL(k_pr_front, dim3(1), dim3(ZZ_PR_FRONT_THREADS), 0, st, Q, P);
-    hipLaunchKernelGGL(k_mr_plan, grid(nranges), dim3(256), 0, st, Q);
-    hipLaunchKernelGGL(k_mr_touched, dim3(1), dim3(ZZ_MR_SCAN_THREADS), 0, st, Q);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(R.h_st, R.st, sizeof(zz_mr_state), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(X.h_st, X.st, sizeof(zz_pr_state), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    if (X.h_st->dict) { set_err("the stream needs a preset dictionary (FDICT): not supported"); return ZZ_E_UNSUPPORTED; }
-    if (R.h_st->index_bad) {
-        set_err(X.h_st->refused ? "reads: all fail, the container header is invalid, the last row does not end where the trailer begins, or the sums do not fold to the trailer"
-                                : "reads: all fail, the rows are not a point index (row 0 = (0, 0), bits strictly ascending, bytes ascending)");
-        return ZZ_E_DATA;
-    }
-    const uint64_t touched = R.h_st->touched, nwaves = R.h_st->nwaves;
-    if (touched) {
-        // the waves' first ranks and S there: one readback
-        if (int rc = R.waves.grow(2 * (nwaves + 1))) return rc;
-        if (int rc = R.h_waves.grow(2 * (nwaves + 1))) return rc;
-        hipLaunchKernelGGL(k_mr_waves, grid(nwaves + 1), dim3(256), 0, st, Q, nwaves, (uint64_t*)R.waves);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(R.h_waves, R.waves, 2 * (nwaves + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        const uint64_t* W = R.h_waves.p;
-        uint64_t big_items = 0, big_bytes = 0;
-        for (uint64_t w = 0; w < nwaves; ++w) {
-            big_items = std::max(big_items, W[2 * w + 2] - W[2 * w]);
-            big_bytes = std::max(big_bytes, W[2 * w + 3] - W[2 * w + 1]);
-        }
-        if (int rc = R.stage.grow(big_bytes + 16)) return rc;
-        if (int rc = M.caps.grow(big_items)) return rc;
-        if (int rc = M.out_lens.grow(big_items)) return rc;
-        if (int rc = R.status.grow(big_items)) return rc;
-        Q.stage = R.stage;
-        P.rooms = M.caps; P.out_lens = M.out_lens; P.status = R.status;
-        const uint64_t resident = 256ull * ZZ_PT_WG_PER_CU;         // persistent wavefronts: what the CUs hold at once
-        for (uint64_t w = 0; w < nwaves; ++w) {
-            const uint64_t t0 = W[2 * w], t1 = W[2 * w + 2];
-            if (t1 <= t0) continue;                                     // (cannot happen: a room is at most one wave's)
-            ++X.waves_run;
+    P.ps = nullptr; P.rooms = nullptr; P.out_lens = nullptr; P.status = nullptr;
+    rd_call N{ "segment", "index and sidecar say",
+               "reads: all fail, the rows are not a point index (row 0 = (0, 0), bits strictly ascending, bytes ascending)",
+               &X.decoded, &X.waves_run };
+    return dec_reads(c, st, Q, N,
+        [&](rd_step step, const zz_mr_params& Q) -> int {
+            switch (step) {
+            case RD_GROW:
+                if (int rc = X.st.grow(1)) return rc;
+                if (int rc = X.h_st.grow(1)) return rc;
+                P.ps = X.st;
+                break;
+            case RD_CLEAR: HIPCHK(hipMemsetAsync(X.st, 0, sizeof(zz_pr_state), st)); break;
+            case RD_ENQUEUE: hipLaunchKernelGGL(k_pr_front, dim3(1), dim3(ZZ_PR_FRONT_THREADS), 0, st, Q, P); break;
+            case RD_READ: HIPCHK(hipMemcpyAsync(X.h_st, X.st, sizeof(zz_pr_state), hipMemcpyDeviceToHost, st)); break;
+            case RD_JUDGE:
+                if (X.h_st->dict) { set_err("the stream needs a preset dictionary (FDICT): not supported"); return ZZ_E_UNSUPPORTED; }
+                if (X.h_st->refused)
+                    N.index_bad = "reads: all fail, the container header is invalid, the last row does not end where the trailer begins, or the sums do not fold to the trailer";
+                break;
+            }
+            return ZZ_OK;
+        },
+        [&](const zz_mr_params& Q, uint64_t t0, uint64_t t1, bool enqueue) -> int {
+            if (!enqueue) {
+                if (int rc = M.caps.grow(t1 - t0)) return rc;
+                return M.out_lens.grow(t1 - t0);
+            }
+            // persistent wavefronts, at most what the CUs hold at once, deal the ranks from a counter
+            P.rooms = M.caps; P.out_lens = M.out_lens; P.status = R.status;
             HIPCHK(hipMemsetAsync(&X.st.p->next, 0, sizeof(unsigned int), st));
-            hipLaunchKernelGGL(k_inflate_segments_win, dim3((uint32_t)std::min<uint64_t>(t1 - t0, resident)), dim3(ZZ_INF_THREADS), 0, st, Q, P, t0, t1);
-            hipLaunchKernelGGL(k_mr_judge, dim3(1), dim3(ZZ_MR_SCAN_THREADS), 0, st, Q, t0, t1, (const uint64_t*)M.caps, (const uint64_t*)M.out_lens,
-                               (const int32_t*)R.status);
-            hipLaunchKernelGGL(k_mr_cut, dim3(1), dim3(ZZ_MR_SCAN_THREADS), 0, st, Q, t0, t1);
-            hipLaunchKernelGGL(k_mr_copy, dim3(ZZ_MR_COPY_GRID), dim3(256), 0, st, Q, t0, t1);
-            HIPCHK(hipGetLastError());
-        }
-        X.segments_decoded = touched - R.h_st->big;
-    }
-    hipLaunchKernelGGL(k_mr_verdict, grid(nranges), dim3(256), 0, st, Q);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(R.h_st, R.st, sizeof(zz_mr_state), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    const zz_mr_state& T = *R.h_st.p;
-    if (T.n_data) { set_err("reads: " + std::to_string(T.n_data) + " touch a segment that is not what index and sidecar say"); return ZZ_E_DATA; }
-    if (T.n_unsupported) { set_err("reads: " + std::to_string(T.n_unsupported) + " touch a segment whose room exceeds the stage (64 MiB)"); return ZZ_E_UNSUPPORTED; }
-    if (T.n_arg) { set_err("reads: " + std::to_string(T.n_arg) + " start behind the decoded length or overflow"); return ZZ_E_ARG; }
-    if (T.n_nospace) { set_err("reads: " + std::to_string(T.n_nospace) + " do not fit their destinations"); return ZZ_E_NOSPACE; }
-    return ZZ_OK;
+            hipLaunchKernelGGL(k_inflate_segments_win, dim3((uint32_t)std::min<uint64_t>(t1 - t0, 256ull * ZZ_PT_WG_PER_CU)), dim3(ZZ_INF_THREADS), 0, st,
+                               Q, P, t0, t1);
+            return ZZ_OK;
+        });
 }
-
 extern "C" int zz_ctx_last_decode_points_ranges_stats(const zz_ctx* c, uint64_t* segments_decoded, uint32_t* waves)
 {
     if (!c) { set_err("null context"); return ZZ_E_ARG; }
-    if (segments_decoded) *segments_decoded = c->dec.pr.segments_decoded;
+    if (segments_decoded) *segments_decoded = c->dec.pr.decoded;
     if (waves) *waves = c->dec.pr.waves_run;
     return ZZ_OK;
 }
