@@ -80,6 +80,43 @@ def test_five_thousand_members_of_4_kib(torch, ctx):
     assert len(f) > 200 * mc.STRETCH
 
 
+def test_one_crowded_stretch_among_empty_ones(torch, ctx):
+    # the mark pass ranks a stretch's candidates by a scan over its four wavefronts: 120 tiny members fill stretch 16 and its
+    # neighbours with headers in every wavefront, between two stored members of 65,280 random bytes whose stretches hold none
+    rng = random.Random(33)
+    big = [bytes(rng.getrandbits(8) for _ in range(65280)) for _ in range(2)]
+    assert all(b"\x1f\x8b\x08" not in b for b in big)
+    tiny = [mc.text(20 + k % 13, k) for k in range(120)]
+    ms = [mc.bgzf(big[0], 0)] + [mc.bgzf(t) for t in tiny] + [mc.bgzf(big[1], 0), mc.EOF_BLOCK]
+    f, want = b"".join(ms), big[0] + b"".join(tiny) + big[1]
+    starts = [sum(len(x) for x in ms[:k]) for k in range(len(ms))]
+    per_wave = {}
+    for s in starts:
+        per_wave.setdefault(s // mc.STRETCH, set()).add(s % mc.STRETCH // 1024)
+    assert per_wave[16] == {0, 1, 2, 3} and len(per_wave) <= 6 and len(f) > 32 * mc.STRETCH
+    assert mc.checked(f) == want
+    rc, out, stats = run(torch, ctx, f, len(want))
+    assert rc == 0 and out == want
+    assert stats == (len(ms), len(ms), mc.BLOCKED)
+
+
+def test_more_stretches_than_one_round_of_the_scan(torch, ctx):
+    # k_members_scan takes 4096 stretches a round: a stored file of a little over 16 MiB, written, read back and compared on the
+    # device; the members behind stretch 4095 lie where the first round's count says
+    n = (16 << 20) + 3 * zz.MEMBERS_BLOCK + 5
+    data = torch.empty(n, dtype=torch.uint8, device="cuda")
+    ctx.generate(zz.GEN_TEXT, 9, 0, data, n)
+    cap = zz.members_bound(n)
+    file = torch.empty(cap, dtype=torch.uint8, device="cuda")
+    w = ctx.encode_members(data, n, file, cap, level=0)
+    members = -(-n // zz.MEMBERS_BLOCK) + 1
+    assert w > 4097 * mc.STRETCH and (w - 28 - 2 * zz.MEMBERS_BLOCK) > 4096 * mc.STRETCH      # two members begin in the second round
+    back = torch.zeros(n, dtype=torch.uint8, device="cuda")
+    assert ctx.decode_members(file, w, back, n) == n
+    assert torch.equal(back, data)
+    assert ctx.last_decode_members_stats() == (members, members, mc.BLOCKED)
+
+
 def test_member_boundaries_on_every_residue_of_the_stretch(torch, ctx):
     # the second member's header starts at every offset of one stretch of the mark pass and 20 bytes beyond: inside a lane's
     # bytes, across two lanes, across two wavefronts and across two workgroups

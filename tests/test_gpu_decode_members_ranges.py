@@ -225,6 +225,32 @@ def test_one_decode_per_member(torch, ctx):
     assert bool((buf.view(4096, L) == want).all())
 
 
+@pytest.mark.parametrize("m", [1023, 1024, 1025])
+def test_round_edges_of_the_planning_scans(torch, ctx, m):
+    # k_mr_touched, k_mr_judge, k_mr_cut and k_members_pairs take 1024 members, ranks or reads a round: m tiny members, every one
+    # touched, one read per member and three more, so that each carry is in use at the edge -- coverage (a read lies across member
+    # 1023 | 1024), counts and rooms (every member), chunks (every read), and the damaged members in front of a rank (two members
+    # with a flipped CRC: one in the first round, one that is the file's last member, which m = 1025 puts into the second)
+    kinds = [rc.mem(mc.text(30 + 7 * k, k)) for k in range(16)]
+    members = [kinds[(5 * j) % 16] for j in range(m)]
+    for j in (5, m - 1):
+        b = bytearray(members[j][0])
+        b[-8] ^= 1
+        members[j] = (bytes(b), members[j][1])
+    file, idx = rc.build(members)
+    u = [p[1] for p in idx]
+    reads = [(u[j] + 3, 10, None) for j in range(m)] + [(u[1020], u[m] - u[1020], None), (u[6], u[m - 1] - u[6], None), (0, u[m], None)]
+    J = rc.Judge(file, idx)
+    want_code, want = J.call(reads)
+    assert want_code == rc.E_DATA and [r for r, (s, _) in enumerate(want) if s != 0] == [5, m - 1, m, m + 2]
+    code, got, (dec, waves) = call(torch, ctx, file, idx, reads)
+    assert code == want_code and got == want
+    assert (dec, waves) == (m, 1)
+    # the index from the file alone: ISIZE is summed over the round edge (a flipped CRC does not change what a header announces)
+    index = ctx.members_index(dev(torch, file), len(file))
+    assert [tuple(p) for p in index.cpu().tolist()] == idx
+
+
 def test_three_waves(torch, ctx):
     # the smallest shape with three waves: 3 x 64 MiB + 1 MiB of text, generated, written and compared on the device
     n = 3 * (64 << 20) + (1 << 20)

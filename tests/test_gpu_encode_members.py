@@ -80,6 +80,22 @@ def test_a_blocked_file_inside_a_blocked_file(torch, ctx, oracle):
     assert mc.yardstick(back) == mw.text(20000, 3)
 
 
+@pytest.mark.parametrize("level", [0, 1])
+def test_more_members_than_one_round_of_the_size_scan(torch, ctx, oracle, level):
+    # k_mw_sizes places 4096 members a round: 4097 members of the smallest block there is, one byte, so that the last member and
+    # the file's end lie where the first round's bytes say (a member of one byte has 32 bytes stored and 29 compressed)
+    B, P = 1, mw.PACKET
+    data = mw.text(4097, 11)
+    want, offsets, stored = mw.expected(oracle, data, level, B, P, True)
+    assert offsets == [(29 if level else 32) * i for i in range(4098)]
+    file, behind, offs, stats = write(torch, ctx, data, level, B, P, True)
+    assert file == want and behind == bytes(len(behind))
+    assert offs == offsets
+    assert stats == (4097, sum(stored))
+    assert decoded(torch, ctx, file, len(data)) == (data, zz.MEMBERS_BLOCKED)
+    assert gzip.decompress(file) == data
+
+
 @pytest.mark.parametrize("level", [1, 2])
 def test_pieces_concatenate(torch, ctx, oracle, level):
     B, P = 4096, 4096

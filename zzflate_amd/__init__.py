@@ -132,6 +132,7 @@ def _load():
         "zz_debug_last_pulls": (None, [ctypes.POINTER(i32), ctypes.POINTER(i32)]),
         "zz_debug_lds_order_verdict": (i32, [i32]),
         "zz_debug_code_lengths": (i32, [vp, u32, vp, vp, vp, vp, vp, vp]),
+        "zz_debug_wg_scan": (i32, [vp, i32, u32, u64, vp, vp, vp]),
         "zz_last_error": (ctypes.c_char_p, []),
         "zz_version": (ctypes.c_char_p, []),
         "zz_build_flags": (ctypes.c_char_p, []),
@@ -141,7 +142,8 @@ def _load():
         "zz_debug_l2_kernel": (i32, [vp]),
     }
     # (diagnostic hooks an older experimental build named by ZZFLATE_AMD_LIB may lack: A/B runs of tools/abn.sh)
-    optional = {"zz_build_flags", "zz_debug_force_lds_violation", "zz_debug_reset_lds_order", "zz_debug_l1_kernel", "zz_debug_l2_kernel"}
+    optional = {"zz_build_flags", "zz_debug_force_lds_violation", "zz_debug_reset_lds_order", "zz_debug_l1_kernel", "zz_debug_l2_kernel",
+                "zz_debug_wg_scan"}
     for name, (res, args) in sig.items():
         if name in optional and not hasattr(L, name):
             continue

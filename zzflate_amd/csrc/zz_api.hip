@@ -496,6 +496,72 @@ extern "C" int zz_debug_code_lengths(zz_ctx* c, uint32_t ncases, const uint32_t*
     HIPCHK(hipMemcpy(meta, d_meta, 20ull * ncases * sizeof(uint32_t), hipMemcpyDeviceToHost));
     return ZZ_OK;
 }
+// diagnostic (not part of the public header): the planning kernels' workgroup scan alone (wg_scan_excl, wg_scan_excl2: zz_wave.h),
+// as they use it -- one workgroup of `threads` (256 or 1024), one value per thread and round, a carry from round to round, the
+// round's closing barrier. All pointers are host memory. form 0: n uint32_t, form 1: n uint64_t, form 2: n pairs { a, b } of
+// uint64_t scanned together, a in 32 bits (its upper half is ignored and comes back zero), b in 64. out[i] = the sum of in[0 .. i)
+// in the form's width (32-bit sums wrap), total = the sum of all; out and total have in's layout.
+template <int THREADS, class V> __global__ __launch_bounds__(THREADS) void k_debug_wg_scan(const V* in, uint64_t n, V* out, V* total)
+{
+    __shared__ V wtot[THREADS / ZZ_WAVE];
+    const uint32_t t = threadIdx.x;
+    V carry = 0;
+    for (uint64_t r0 = 0; r0 < n; r0 += THREADS) {
+        const uint64_t i = r0 + t;
+        const wg_prefix<V> s = wg_scan_excl<THREADS>(i < n ? in[i] : (V)0, wtot);
+        if (i < n) out[i] = carry + s.excl;
+        carry += s.total;
+        __syncthreads();
+    }
+    if (t == 0) *total = carry;
+}
+template <int THREADS> __global__ __launch_bounds__(THREADS) void k_debug_wg_scan2(const uint64_t* in, uint64_t n, uint64_t* out, uint64_t* total)
+{
+    __shared__ uint32_t wa[THREADS / ZZ_WAVE];
+    __shared__ uint64_t wb[THREADS / ZZ_WAVE];
+    const uint32_t t = threadIdx.x;
+    uint32_t ca = 0; uint64_t cb = 0;
+    for (uint64_t r0 = 0; r0 < n; r0 += THREADS) {
+        const uint64_t i = r0 + t;
+        const uint32_t a = i < n ? (uint32_t)in[2 * i] : 0;
+        const uint64_t b = i < n ? in[2 * i + 1] : 0;
+        const wg_prefix2<uint32_t, uint64_t> s = wg_scan_excl2<THREADS>(a, wa, b, wb);
+        if (i < n) { out[2 * i] = ca + s.a.excl; out[2 * i + 1] = cb + s.b.excl; }
+        ca += s.a.total; cb += s.b.total;
+        __syncthreads();
+    }
+    if (t == 0) { total[0] = ca; total[1] = cb; }
+}
+extern "C" int zz_debug_wg_scan(zz_ctx* c, int form, uint32_t threads, uint64_t n, const void* in, void* out, void* total)
+{
+    if (!c || !total || (n && (!in || !out))) { set_err("null argument"); return ZZ_E_ARG; }
+    if (form < 0 || form > 2 || (threads != 256 && threads != 1024) || n > (1ull << 24)) { set_err("bad form, threads or n"); return ZZ_E_ARG; }
+    HIPCHK(hipSetDevice(c->device));
+    const uint64_t words = form == 0 ? (n + 1) / 2 : form == 1 ? n : 2 * n;       // of 8 bytes; the last 32-bit value may share one
+    const uint64_t bytes = (form == 0 ? 4 : form == 1 ? 8 : 16) * n, tbytes = form == 0 ? 4 : form == 1 ? 8 : 16;
+    zz_buf<uint64_t> d_in, d_out, d_total;
+    int rc;
+    if ((rc = d_in.grow(words + 1)) || (rc = d_out.grow(words + 1)) || (rc = d_total.grow(2))) return rc;
+    if (n) HIPCHK(hipMemcpy(d_in, in, bytes, hipMemcpyHostToDevice));
+    HIPCHK(hipMemset(d_out, 0xFF, (words + 1) * sizeof(uint64_t)));
+    HIPCHK(hipMemset(d_total, 0xFF, 2 * sizeof(uint64_t)));
+    const bool big = threads == 1024;
+    if (form == 0) {
+        if (big) hipLaunchKernelGGL((k_debug_wg_scan<1024, uint32_t>), dim3(1), dim3(1024), 0, 0, (const uint32_t*)d_in.p, n, (uint32_t*)d_out.p, (uint32_t*)d_total.p);
+        else hipLaunchKernelGGL((k_debug_wg_scan<256, uint32_t>), dim3(1), dim3(256), 0, 0, (const uint32_t*)d_in.p, n, (uint32_t*)d_out.p, (uint32_t*)d_total.p);
+    } else if (form == 1) {
+        if (big) hipLaunchKernelGGL((k_debug_wg_scan<1024, uint64_t>), dim3(1), dim3(1024), 0, 0, (const uint64_t*)d_in.p, n, d_out.p, d_total.p);
+        else hipLaunchKernelGGL((k_debug_wg_scan<256, uint64_t>), dim3(1), dim3(256), 0, 0, (const uint64_t*)d_in.p, n, d_out.p, d_total.p);
+    } else {
+        if (big) hipLaunchKernelGGL((k_debug_wg_scan2<1024>), dim3(1), dim3(1024), 0, 0, (const uint64_t*)d_in.p, n, d_out.p, d_total.p);
+        else hipLaunchKernelGGL((k_debug_wg_scan2<256>), dim3(1), dim3(256), 0, 0, (const uint64_t*)d_in.p, n, d_out.p, d_total.p);
+    }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipDeviceSynchronize());
+    if (n) HIPCHK(hipMemcpy(out, d_out, bytes, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(total, d_total, tbytes, hipMemcpyDeviceToHost));
+    return ZZ_OK;
+}
 // ---- the run-time guard for that property ---------------------------------------------------------------------------------
 // Three things in this library are only correct where the LDS serves equal addresses of one instruction in ascending lane order
 // and one wavefront's instructions in issue order -- which gfx950 does and its ISA manual does not promise: the warm window's

@@ -40,7 +40,7 @@ __global__ __launch_bounds__(ZZ_SCAN_THREADS) void k_batch_plan(const uint64_t* 
                                                                 uint32_t* first, uint64_t* slotbase, zz_batch_totals* out)
 {
     __shared__ uint64_t wc[ZZ_SCAN_THREADS / ZZ_WAVE], wb[ZZ_SCAN_THREADS / ZZ_WAVE];
-    const uint32_t t = threadIdx.x, lane = t & 63, wv = t >> 6;
+    const uint32_t t = threadIdx.x;
     const uint32_t full = level ? zz_slot_stride(level, P) : 0;
     uint64_t carry_c = 0, carry_b = 0;
     for (uint64_t r0 = 0; r0 < nitems; r0 += (uint64_t)ZZ_BATCH_PLAN_PER * ZZ_SCAN_THREADS) {
@@ -54,26 +54,14 @@ __global__ __launch_bounds__(ZZ_SCAN_THREADS) void k_batch_plan(const uint64_t* 
             sb[u] = (npk && level) ? (npk - 1) * full + zz_slot_stride(level, (uint32_t)(n - (npk - 1) * P)) : 0;
             tc += cnt[u]; tb += sb[u];
         }
-        uint64_t ic = tc, ib = tb;                       // inclusive scans over the wavefront
-#pragma unroll
-        for (int o = 1; o < ZZ_WAVE; o <<= 1) {
-            const uint64_t xc = __shfl_up(ic, o), xb = __shfl_up(ib, o);
-            if (lane >= (uint32_t)o) { ic += xc; ib += xb; }
-        }
-        if (lane == 63) { wc[wv] = ic; wb[wv] = ib; }
-        __syncthreads();
-        uint64_t bc = carry_c, bb = carry_b, rc = 0, rb = 0;
-        for (uint32_t w = 0; w < ZZ_SCAN_THREADS / ZZ_WAVE; ++w) {
-            if (w < wv) { bc += wc[w]; bb += wb[w]; }
-            rc += wc[w]; rb += wb[w];
-        }
-        bc += ic - tc; bb += ib - tb;
+        const wg_prefix2<uint64_t, uint64_t> s = wg_scan_excl2<ZZ_SCAN_THREADS>(tc, wc, tb, wb, carry_c, carry_b);      // packets, slot bytes
+        uint64_t bc = s.a.excl, bb = s.b.excl;
 #pragma unroll
         for (int u = 0; u < ZZ_BATCH_PLAN_PER; ++u) {
             if (i0 + u < nitems) { first[i0 + u] = (uint32_t)bc; slotbase[i0 + u] = bb; }
             bc += cnt[u]; bb += sb[u];
         }
-        carry_c += rc; carry_b += rb;
+        carry_c += s.a.total; carry_b += s.b.total;
         __syncthreads();
     }
     if (t == 0) {

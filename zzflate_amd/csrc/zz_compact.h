@@ -22,7 +22,7 @@ __global__ __launch_bounds__(ZZ_SCAN_THREADS) void k_scan_sizes(const uint32_t* 
                                                                 uint64_t* offsets, zz_result* res)
 {
     __shared__ uint32_t wtot[ZZ_SCAN_THREADS / ZZ_WAVE];
-    const uint32_t t = threadIdx.x, lane = t & 63, wv = t >> 6;
+    const uint32_t t = threadIdx.x;
     uint64_t carry = 0;
     for (uint32_t r0 = 0; r0 < npk; r0 += 4 * ZZ_SCAN_THREADS) {
         const uint32_t k = r0 + 4 * t;
@@ -30,14 +30,10 @@ __global__ __launch_bounds__(ZZ_SCAN_THREADS) void k_scan_sizes(const uint32_t* 
         if (k + 4 <= npk) { const uint4 q = *(const uint4*)(sizes + k); v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w; }
         else for (uint32_t i = 0; i < 4; ++i) if (k + i < npk) v[i] = sizes[k + i];
         const uint32_t mine = v[0] + v[1] + v[2] + v[3];          // < 2^18 each: a round stays far below 2^32
-        const uint32_t incl = wave_scan_incl(mine);
-        if (lane == 63) wtot[wv] = incl;
-        __syncthreads();
-        uint32_t wbase = 0, total = 0;
-        for (uint32_t i = 0; i < ZZ_SCAN_THREADS / ZZ_WAVE; ++i) { const uint32_t x = wtot[i]; if (i < wv) wbase += x; total += x; }
-        uint64_t o = carry + wbase + (incl - mine);
+        const wg_prefix<uint32_t> s = wg_scan_excl<ZZ_SCAN_THREADS>(mine, wtot);
+        uint64_t o = carry + s.excl;
         for (uint32_t i = 0; i < 4; ++i) { if (k + i < npk) offsets[k + i] = o; o += v[i]; }
-        carry += total;
+        carry += s.total;
         __syncthreads();
     }
     if (t == 0) res->stream_bytes = carry;

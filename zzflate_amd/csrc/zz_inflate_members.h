@@ -92,19 +92,15 @@ __global__ __launch_bounds__(ZZ_MEM_THREADS) void k_members_mark(const uint8_t* 
                                                                  uint64_t* offs, uint32_t* lens)
 {
     __shared__ uint32_t wtot[ZZ_MEM_THREADS / ZZ_WAVE];
-    const uint32_t t = threadIdx.x, lane = t & 63, wv = t >> 6;
+    const uint32_t t = threadIdx.x;
     const uint64_t b = blockIdx.x;
     if (FILL && blk_cnt[b] == 0) return;                     // uniform: most stretches hold no header
     const uint64_t i = b * ZZ_MEM_STRETCH + (uint64_t)t * ZZ_MEM_PER_LANE;
     const uint32_t cand = members_mark_lane(src, n, i);
     const uint32_t mine = (uint32_t)__builtin_popcount(cand);
-    const uint32_t incl = wave_scan_incl(mine);
-    if (lane == 63) wtot[wv] = incl;
-    __syncthreads();
-    uint32_t base = 0, total = 0;
-    for (uint32_t w = 0; w < ZZ_MEM_THREADS / ZZ_WAVE; ++w) { const uint32_t x = wtot[w]; if (w < wv) base += x; total += x; }
-    if (!FILL) { if (t == 0) blk_cnt[b] = total; return; }
-    uint64_t at = blk_base[b] + base + (incl - mine);
+    const wg_prefix<uint32_t> s = wg_scan_excl<ZZ_MEM_THREADS>(mine, wtot);      // one scan: wtot is not written again
+    if (!FILL) { if (t == 0) blk_cnt[b] = s.total; return; }
+    uint64_t at = blk_base[b] + s.excl;
     for (uint32_t h = cand; h; h &= h - 1, ++at) {
         const uint32_t k = (uint32_t)__builtin_ctz(h);
         offs[at] = i + k; lens[at] = zi_members_candidate(src, n, i + k);
@@ -115,21 +111,17 @@ __global__ __launch_bounds__(ZZ_MEM_THREADS) void k_members_mark(const uint8_t* 
 __global__ __launch_bounds__(ZZ_MEM_SCAN_THREADS) void k_members_scan(const uint32_t* blk_cnt, uint64_t nblk, uint64_t* blk_base, zz_mem_state* st)
 {
     __shared__ uint32_t wtot[ZZ_MEM_SCAN_THREADS / ZZ_WAVE];
-    const uint32_t t = threadIdx.x, lane = t & 63, wv = t >> 6;
+    const uint32_t t = threadIdx.x;
     uint64_t carry = 0;
     for (uint64_t r0 = 0; r0 < nblk; r0 += 4 * ZZ_MEM_SCAN_THREADS) {
         const uint64_t k = r0 + 4 * t;
         uint32_t v[4] = { 0, 0, 0, 0 };
         for (uint32_t u = 0; u < 4; ++u) if (k + u < nblk) v[u] = blk_cnt[k + u];
         const uint32_t mine = v[0] + v[1] + v[2] + v[3];      // at most a third of 4 * ZZ_MEM_STRETCH each: far below 2^32 a round
-        const uint32_t incl = wave_scan_incl(mine);
-        if (lane == 63) wtot[wv] = incl;
-        __syncthreads();
-        uint32_t wbase = 0, total = 0;
-        for (uint32_t w = 0; w < ZZ_MEM_SCAN_THREADS / ZZ_WAVE; ++w) { const uint32_t x = wtot[w]; if (w < wv) wbase += x; total += x; }
-        uint64_t o = carry + wbase + (incl - mine);
+        const wg_prefix<uint32_t> s = wg_scan_excl<ZZ_MEM_SCAN_THREADS>(mine, wtot);
+        uint64_t o = carry + s.excl;
         for (uint32_t u = 0; u < 4; ++u) { if (k + u < nblk) blk_base[k + u] = o; o += v[u]; }
-        carry += total;
+        carry += s.total;
         __syncthreads();
     }
     if (t == 0) st->candidates = carry;
@@ -167,30 +159,21 @@ __global__ __launch_bounds__(ZZ_MEM_SCAN_THREADS) void k_members_slots(zz_mem_sl
     __shared__ uint64_t wtot[ZZ_MEM_SCAN_THREADS / ZZ_WAVE];
     if (!Q.st->blocked) return;                              // uniform
     const uint64_t m = Q.st->members;
-    const uint32_t t = threadIdx.x, lane = t & 63, wv = t >> 6;
+    const uint32_t t = threadIdx.x;
     uint64_t carry = 0;
     for (uint64_t r0 = 0; r0 < m; r0 += ZZ_MEM_SCAN_THREADS) {
         const uint64_t j = r0 + t;
         uint64_t c = 0; uint32_t len = 0, isize = 0;
         if (j < m) { c = Q.offs[j]; len = Q.lens[j]; isize = zi_members_isize(zi_view<const uint8_t>{ Q.src, Q.n }, c, len); }
-        uint64_t incl = isize;                               // inclusive scan over the wavefront
-#pragma unroll
-        for (int o = 1; o < ZZ_WAVE; o <<= 1) {
-            const uint64_t x = __shfl_up(incl, o);
-            if (lane >= (uint32_t)o) incl += x;
-        }
-        if (lane == 63) wtot[wv] = incl;
-        __syncthreads();
-        uint64_t off = carry, total = 0;
-        for (uint32_t w = 0; w < ZZ_MEM_SCAN_THREADS / ZZ_WAVE; ++w) { const uint64_t x = wtot[w]; if (w < wv) off += x; total += x; }
-        off += incl - isize;
+        const wg_prefix<uint64_t> s = wg_scan_excl<ZZ_MEM_SCAN_THREADS>((uint64_t)isize, wtot, carry);      // 64 bits: the sum of ISIZE has no bound
+        const uint64_t off = s.excl;
         if (j < m && off <= Q.cap) {
             Q.srcs[j] = Q.src + c; Q.src_lens[j] = len;
             Q.dsts[j] = Q.dst + off; Q.caps[j] = zi_members_slot_cap(isize, off, Q.cap);
             // (one member at most gets here and passes cap: those behind m* begin behind cap)
             if (zi_members_is_mstar(isize, off, Q.cap)) { Q.st->mstar = j; Q.st->mstar_src = c; Q.st->mstar_dst = off; }
         }
-        carry += total;
+        carry += s.total;
         __syncthreads();
     }
     if (t == 0) Q.st->total = carry;

@@ -63,8 +63,6 @@ __device__ __forceinline__ zi_mr_tables mr_tables(const zz_mr_params& Q)
     return zi_mr_tables{ { Q.idx, 2 * Q.entries }, { Q.cnt, Q.entries }, { Q.tlist, T }, { Q.S, T + 1 }, { Q.F, T + 1 }, { Q.G, T + 1 } };
 }
 
-__device__ __forceinline__ uint64_t uniform64(uint64_t v) { return ((uint64_t)uniform((uint32_t)(v >> 32)) << 32) | uniform((uint32_t)v); }
-
 // one pass, one flag (every writer stores the same value)
 __global__ __launch_bounds__(256) void k_mr_check(zz_mr_params Q)
 {
@@ -100,37 +98,20 @@ __global__ __launch_bounds__(ZZ_MR_SCAN_THREADS) void k_mr_touched(zz_mr_params 
     __shared__ uint64_t wroom[ZZ_MR_SCAN_THREADS / ZZ_WAVE];
     const zi_view<const uint64_t> idx{ Q.idx, 2 * Q.entries };
     const uint64_t members = Q.entries - 1;
-    const uint32_t t = threadIdx.x, lane = t & 63, wv = t >> 6;
+    const uint32_t t = threadIdx.x;
     if (Q.st->index_bad) return;                             // uniform: k_mr_plan settled every read
     uint32_t ccov = 0; uint64_t ccnt = 0, cbig = 0, croom = 0;
     for (uint64_t r0 = 0; r0 < members; r0 += ZZ_MR_SCAN_THREADS) {
         const uint64_t j = r0 + t;
-        uint32_t cov = wave_scan_incl(j < members ? (uint32_t)Q.diff[j] : 0u);      // the reads that cover member j
-        if (lane == 63) wcov[wv] = cov;
-        __syncthreads();
-        uint32_t tcov = 0;
-        for (uint32_t w = 0; w < ZZ_MR_SCAN_THREADS / ZZ_WAVE; ++w) { const uint32_t x = wcov[w]; if (w < wv) cov += x; tcov += x; }
-        cov += ccov;
+        const uint32_t d = j < members ? (uint32_t)Q.diff[j] : 0u;
+        const wg_prefix<uint32_t> sc = wg_scan_excl<ZZ_MR_SCAN_THREADS>(d, wcov, ccov);
+        const uint32_t cov = sc.excl + d;                      // the reads that cover member j (inclusive; wraps to the true sum)
         const uint64_t room = j < members ? zi_mr_room(idx, j) : 0;
         const uint32_t kind = j < members ? zi_mr_touch(room, (int32_t)cov) : 0u;
         const uint32_t one = (kind ? 1u : 0u) | (kind == 2 ? 0x10000u : 0u);
         const uint64_t myroom = kind == 1 ? room : 0;
-        const uint32_t icnt = wave_scan_incl(one);
-        uint64_t iroom = myroom;
-#pragma unroll
-        for (int o = 1; o < ZZ_WAVE; o <<= 1) {
-            const uint64_t x = __shfl_up(iroom, o);
-            if (lane >= (uint32_t)o) iroom += x;
-        }
-        if (lane == 63) { wcnt[wv] = icnt; wroom[wv] = iroom; }
-        __syncthreads();
-        uint32_t bc = icnt - one, tcnt = 0; uint64_t broom = croom + iroom - myroom, troom = 0;      // exclusive
-        for (uint32_t w = 0; w < ZZ_MR_SCAN_THREADS / ZZ_WAVE; ++w) {
-            const uint32_t x = wcnt[w]; const uint64_t y = wroom[w];
-            if (w < wv) { bc += x; broom += y; }
-            tcnt += x; troom += y;
-        }
-        const uint64_t bcnt = ccnt + (bc & 0xFFFFu), bbig = cbig + (bc >> 16);
+        const wg_prefix2<uint32_t, uint64_t> s = wg_scan_excl2<ZZ_MR_SCAN_THREADS>(one, wcnt, myroom, wroom, 0u, croom);
+        const uint64_t bcnt = ccnt + (s.a.excl & 0xFFFFu), bbig = cbig + (s.a.excl >> 16), broom = s.b.excl;
         if (j < members) {
             Q.cnt[j] = (uint32_t)bcnt;
             if (kind) {
@@ -138,7 +119,7 @@ __global__ __launch_bounds__(ZZ_MR_SCAN_THREADS) void k_mr_touched(zz_mr_params 
                 Q.S[bcnt] = broom; Q.G[bcnt] = (uint32_t)bbig;
             }
         }
-        ccov += tcov; ccnt += tcnt & 0xFFFFu; cbig += tcnt >> 16; croom += troom;
+        ccov += sc.total; ccnt += s.a.total & 0xFFFFu; cbig += s.a.total >> 16; croom += s.b.total;
         __syncthreads();                                     // (and what this round wrote is the workgroup's to read)
     }
     if (t == 0) {
@@ -177,18 +158,14 @@ __global__ __launch_bounds__(ZZ_MR_SCAN_THREADS) void k_mr_judge(zz_mr_params Q,
                                                                  const uint64_t* out_lens, const int32_t* status)
 {
     __shared__ uint32_t wtot[ZZ_MR_SCAN_THREADS / ZZ_WAVE];
-    const uint32_t t = threadIdx.x, lane = t & 63, wv = t >> 6;
+    const uint32_t t = threadIdx.x;
     uint32_t carry = Q.F[t0];
     for (uint64_t r0 = t0; r0 < t1; r0 += ZZ_MR_SCAN_THREADS) {
         const uint64_t k = r0 + t;
         const uint32_t bad = k < t1 && zi_mr_member_bad(Q.tlist[k], status[k - t0], out_lens[k - t0], caps[k - t0]) ? 1u : 0u;
-        const uint32_t incl = wave_scan_incl(bad);
-        if (lane == 63) wtot[wv] = incl;
-        __syncthreads();
-        uint32_t base = carry, total = 0;
-        for (uint32_t w = 0; w < ZZ_MR_SCAN_THREADS / ZZ_WAVE; ++w) { const uint32_t x = wtot[w]; if (w < wv) base += x; total += x; }
-        if (k < t1) Q.F[k + 1] = base + incl;
-        carry += total;
+        const wg_prefix<uint32_t> s = wg_scan_excl<ZZ_MR_SCAN_THREADS>(bad, wtot, carry);
+        if (k < t1) Q.F[k + 1] = s.excl + bad;           // inclusive: the bad members up to and with rank k
+        carry += s.total;
         __syncthreads();
     }
 }
@@ -198,23 +175,14 @@ __global__ __launch_bounds__(ZZ_MR_SCAN_THREADS) void k_mr_cut(zz_mr_params Q, u
 {
     __shared__ uint64_t wtot[ZZ_MR_SCAN_THREADS / ZZ_WAVE];
     const zi_mr_tables T = mr_tables(Q);
-    const uint32_t t = threadIdx.x, lane = t & 63, wv = t >> 6;
+    const uint32_t t = threadIdx.x;
     uint64_t carry = 0;
     for (uint64_t r0 = 0; r0 < Q.nranges; r0 += ZZ_MR_SCAN_THREADS) {
         const uint64_t r = r0 + t;
         const uint64_t mine = r < Q.nranges ? zi_mr_chunks(zi_mr_cut(Q.reads[r], Q.firsts[r], T, t0, t1).len) : 0;
-        uint64_t incl = mine;
-#pragma unroll
-        for (int o = 1; o < ZZ_WAVE; o <<= 1) {
-            const uint64_t x = __shfl_up(incl, o);
-            if (lane >= (uint32_t)o) incl += x;
-        }
-        if (lane == 63) wtot[wv] = incl;
-        __syncthreads();
-        uint64_t base = carry, total = 0;
-        for (uint32_t w = 0; w < ZZ_MR_SCAN_THREADS / ZZ_WAVE; ++w) { const uint64_t x = wtot[w]; if (w < wv) base += x; total += x; }
-        if (r < Q.nranges) Q.chunk0[r] = base + incl - mine;
-        carry += total;
+        const wg_prefix<uint64_t> s = wg_scan_excl<ZZ_MR_SCAN_THREADS>(mine, wtot, carry);
+        if (r < Q.nranges) Q.chunk0[r] = s.excl;
+        carry += s.total;
         __syncthreads();
     }
     if (t == 0) Q.chunk0[Q.nranges] = carry;
@@ -265,27 +233,19 @@ __global__ __launch_bounds__(ZZ_MR_SCAN_THREADS) void k_members_pairs(const uint
                                                                       uint64_t m, uint64_t* idx)
 {
     __shared__ uint64_t wtot[ZZ_MR_SCAN_THREADS / ZZ_WAVE];
-    const uint32_t t = threadIdx.x, lane = t & 63, wv = t >> 6;
+    const uint32_t t = threadIdx.x;
     uint64_t carry = 0;
     for (uint64_t r0 = 0; r0 < m; r0 += ZZ_MR_SCAN_THREADS) {
         const uint64_t j = r0 + t;
         uint64_t c = 0; uint32_t len = 0, isize = 0;
         if (j < m) { c = offs[j]; len = lens[j]; isize = zi_members_isize(zi_view<const uint8_t>{ src, n }, c, len); }
-        uint64_t incl = isize;
-#pragma unroll
-        for (int o = 1; o < ZZ_WAVE; o <<= 1) {
-            const uint64_t x = __shfl_up(incl, o);
-            if (lane >= (uint32_t)o) incl += x;
-        }
-        if (lane == 63) wtot[wv] = incl;
-        __syncthreads();
-        uint64_t off = carry, total = 0;
-        for (uint32_t w = 0; w < ZZ_MR_SCAN_THREADS / ZZ_WAVE; ++w) { const uint64_t x = wtot[w]; if (w < wv) off += x; total += x; }
+        const wg_prefix<uint64_t> s = wg_scan_excl<ZZ_MR_SCAN_THREADS>((uint64_t)isize, wtot, carry);
+        const uint64_t off = s.excl;
         if (j < m) {
-            idx[2 * j] = c; idx[2 * j + 1] = off + incl - isize;
-            if (j + 1 == m) { idx[2 * m] = c + len; idx[2 * m + 1] = off + incl; }
+            idx[2 * j] = c; idx[2 * j + 1] = off;
+            if (j + 1 == m) { idx[2 * m] = c + len; idx[2 * m + 1] = off + isize; }
         }
-        carry += total;
+        carry += s.total;
         __syncthreads();
     }
 }

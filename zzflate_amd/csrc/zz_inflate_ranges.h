@@ -66,7 +66,7 @@ __device__ __forceinline__ void ranges_settle(const zz_rng_params& Q, uint64_t r
 __global__ __launch_bounds__(ZZ_RNG_PLAN_THREADS) void k_ranges_plan(zz_rng_params Q, int fresh)
 {
     __shared__ uint64_t wsum[ZZ_RNG_PLAN_THREADS / ZZ_WAVE];
-    const uint32_t t = threadIdx.x, lane = t & 63, wv = t >> 6;
+    const uint32_t t = threadIdx.x;
     for (uint32_t i = t; i <= ZZ_RNG_MAX_WAVES; i += ZZ_RNG_PLAN_THREADS) { Q.tot->wave_first[i] = ~0ull; Q.tot->wave_read[i] = ~0ull; }
     if (t == 0) {
         Q.tot->nwaves = 0; Q.tot->stage_end = 0; Q.tot->longest = 0; Q.tot->deferred = 0;
@@ -92,17 +92,8 @@ __global__ __launch_bounds__(ZZ_RNG_PLAN_THREADS) void k_ranges_plan(zz_rng_para
             if (open && R.state == ZI_RS_DONE) ranges_settle(Q, r, R);
             mine += len[u];
         }
-        uint64_t inc = mine;                             // inclusive scan over the wavefront
-#pragma unroll
-        for (int o = 1; o < ZZ_WAVE; o <<= 1) {
-            const uint64_t x = __shfl_up(inc, o);
-            if (lane >= (uint32_t)o) inc += x;
-        }
-        if (lane == 63) wsum[wv] = inc;
-        __syncthreads();
-        uint64_t base = carry, all = 0;
-        for (uint32_t w = 0; w < ZZ_RNG_PLAN_THREADS / ZZ_WAVE; ++w) { if (w < wv) base += wsum[w]; all += wsum[w]; }
-        base += inc - mine;
+        const wg_prefix<uint64_t> s = wg_scan_excl<ZZ_RNG_PLAN_THREADS>(mine, wsum, carry);      // segment lengths: the first stage packet
+        uint64_t base = s.excl;
 #pragma unroll
         for (int u = 0; u < ZZ_RNG_PLAN_PER; ++u) {
             const uint64_t r = i0 + u;
@@ -122,7 +113,7 @@ __global__ __launch_bounds__(ZZ_RNG_PLAN_THREADS) void k_ranges_plan(zz_rng_para
             }
             base += len[u];
         }
-        carry += all;
+        carry += s.total;
         __syncthreads();
     }
 }

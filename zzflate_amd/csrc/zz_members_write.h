@@ -115,7 +115,7 @@ __global__ __launch_bounds__(ZZ_SCAN_THREADS) void k_mw_sizes(zz_mw_params Q)
 {
     __shared__ uint32_t wtot[ZZ_SCAN_THREADS / ZZ_WAVE];
     __shared__ uint32_t nstored;
-    const uint32_t t = threadIdx.x, lane = t & 63, wv = t >> 6;
+    const uint32_t t = threadIdx.x;
     if (t == 0) nstored = 0;
     uint64_t carry = 0;
     uint32_t mine_stored = 0;
@@ -140,12 +140,8 @@ __global__ __launch_bounds__(ZZ_SCAN_THREADS) void k_mw_sizes(zz_mw_params Q)
             v[u] = ZZ_MW_HEADER + body + ZZ_MW_TRAILER;
         }
         const uint32_t mine = v[0] + v[1] + v[2] + v[3];
-        const uint32_t incl = wave_scan_incl(mine);
-        if (lane == 63) wtot[wv] = incl;
-        __syncthreads();
-        uint32_t wbase = 0, total = 0;
-        for (uint32_t w = 0; w < ZZ_SCAN_THREADS / ZZ_WAVE; ++w) { const uint32_t x = wtot[w]; if (w < wv) wbase += x; total += x; }
-        uint64_t o = carry + wbase + (incl - mine);
+        const wg_prefix<uint32_t> s = wg_scan_excl<ZZ_SCAN_THREADS>(mine, wtot);
+        uint64_t o = carry + s.excl;
         for (uint32_t u = 0; u < 4; ++u) {
             if (i0 + u < Q.members) {
                 Q.moff[i0 + u] = o;
@@ -153,7 +149,7 @@ __global__ __launch_bounds__(ZZ_SCAN_THREADS) void k_mw_sizes(zz_mw_params Q)
             }
             o += v[u];
         }
-        carry += total;
+        carry += s.total;
         __syncthreads();
     }
     if (mine_stored) atomicAdd(&nstored, mine_stored);

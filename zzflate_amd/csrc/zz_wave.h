@@ -1,5 +1,5 @@
 // zz_wave.h -- wavefront (64-lane) primitives for gfx950: ballots, DPP prefix scans, uniform reads,
-// bounds-safe unaligned loads, and a wave-cooperative byte copy.
+// bounds-safe unaligned loads, and a wave-cooperative byte copy; and the one-workgroup prefix sum built on the scans.
 #pragma once
 #include "zz_common.h"
 
@@ -29,6 +29,7 @@ __device__ __forceinline__ uint64_t readlane64(uint64_t v, int l)
     return ((uint64_t)hi << 32) | lo;
 }
 __device__ __forceinline__ uint32_t uniform(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
+__device__ __forceinline__ uint64_t uniform64(uint64_t v) { return ((uint64_t)uniform((uint32_t)(v >> 32)) << 32) | uniform((uint32_t)v); }
 
 // ---- DPP scans --------------------------------------------------------------------------------
 // update_dpp(old, src, ctrl, row_mask, bank_mask, bound_ctrl): lanes whose source lane is outside
@@ -60,6 +61,63 @@ __device__ __forceinline__ uint64_t wave_sum64(uint64_t x)
 #pragma unroll
     for (int o = 32; o >= 1; o >>= 1) x += __shfl_xor(x, o);
     return x;
+}
+
+// inclusive prefix sum of 64-bit values across the 64 lanes (DPP moves 32 bits: six shuffles of both halves)
+__device__ __forceinline__ uint64_t wave_scan_incl64(uint64_t x)
+{
+    const uint32_t lane = (uint32_t)lane_id();
+#pragma unroll
+    for (int o = 1; o < ZZ_WAVE; o <<= 1) {
+        const uint64_t y = __shfl_up(x, o);
+        if (lane >= (uint32_t)o) x += y;
+    }
+    return x;
+}
+__device__ __forceinline__ uint32_t wave_scan_incl_of(uint32_t x) { return wave_scan_incl(x); }
+__device__ __forceinline__ uint64_t wave_scan_incl_of(uint64_t x) { return wave_scan_incl64(x); }
+
+// ---- workgroup scan ---------------------------------------------------------------------------
+// The prefix sum the planning kernels run over one workgroup of THREADS threads (all of them call it): the wavefront scan, lane
+// 63 publishes its wavefront's sum in wtot[THREADS / ZZ_WAVE] (the caller's LDS: two scans of one kernel need two arrays), ONE
+// barrier, and every thread adds up the wavefronts in front of its own. excl = front + the values of threads 0 .. t - 1, total
+// = the sum of all values (without front); sums wrap in V's width (k_mr_touched relies on it). `front` is what lies in front
+// of the workgroup: a caller that scans in rounds passes its carry where that has V's width, adds total to it, and ends the round
+// with __syncthreads() -- wtot may be written again only behind a barrier; one that scans once (k_members_mark) needs none.
+// What a round's threads hold (1, 4 or 8 items each) is the caller's. The sum starts from front and the wavefront's own prefix
+// and takes the wavefront totals one by one: in this order the compiler keeps the totals in flight no longer than it did in the
+// kernels' own loops.
+template <class V> struct wg_prefix { V excl, total; };
+
+template <int THREADS, class V> __device__ __forceinline__ wg_prefix<V> wg_scan_excl(V mine, V* wtot, V front = 0)
+{
+    const uint32_t lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const V incl = wave_scan_incl_of(mine);
+    if (lane == 63) wtot[wv] = incl;
+    __syncthreads();
+    V excl = front + (incl - mine), total = 0;
+    for (uint32_t w = 0; w < THREADS / ZZ_WAVE; ++w) { const V x = wtot[w]; if (w < wv) excl += x; total += x; }
+    return { excl, total };
+}
+
+// two quantities between one pair of barriers (k_batch_plan, k_mr_touched): two arrays, one barrier, one loop
+template <class A, class B> struct wg_prefix2 { wg_prefix<A> a; wg_prefix<B> b; };
+
+template <int THREADS, class A, class B>
+__device__ __forceinline__ wg_prefix2<A, B> wg_scan_excl2(A mine_a, A* wa, B mine_b, B* wb, A front_a = 0, B front_b = 0)
+{
+    const uint32_t lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const A ia = wave_scan_incl_of(mine_a);
+    const B ib = wave_scan_incl_of(mine_b);
+    if (lane == 63) { wa[wv] = ia; wb[wv] = ib; }
+    __syncthreads();
+    A ea = front_a + (ia - mine_a), ta = 0; B eb = front_b + (ib - mine_b), tb = 0;
+    for (uint32_t w = 0; w < THREADS / ZZ_WAVE; ++w) {
+        const A x = wa[w]; const B y = wb[w];
+        if (w < wv) { ea += x; eb += y; }
+        ta += x; tb += y;
+    }
+    return { { ea, ta }, { eb, tb } };
 }
 
 // Lanes holding the same 6-bit key as this lane (keys are lane ids, so six ballots decide it for all lanes at once).
