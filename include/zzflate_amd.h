@@ -130,7 +130,8 @@ int zz_encode_device(zz_ctx* ctx, const void* d_src, uint64_t n, void* d_dst, ui
  * an empty item gets one empty final block, an item of at most one packet the reference's single-encoder stream, and no
  * match reaches in front of an item. All five arrays live in device memory. Returns ZZ_OK, ZZ_E_NOSPACE if at least one
  * item did not fit, or the usual errors; nitems == 0 returns ZZ_OK at once, null arrays give ZZ_E_ARG. Levels 0..3, cold
- * packets: ZZ_E_UNSUPPORTED when the context has a warm window or the extended levels switched on. At most 2^31 - 1
+ * packets: ZZ_E_UNSUPPORTED when the context has a warm window or the extended levels switched on (levels 4..6 come through
+ * zz_encode_batch_flags_device's own switch, below). At most 2^31 - 1
  * items and 2^31 - 1 packets in all. Synchronous; the host reads back two totals of the plan, whatever nitems is.
  * zz_ctx_last_kernel_ms reports the batch's encode kernels. A batch is not a "last call" for zz_verify_last_device,
  * zz_packet_extent_device and zz_packet_index_device: they return ZZ_E_ARG after it. Workspace: about what a single call
@@ -138,6 +139,23 @@ int zz_encode_device(zz_ctx* ctx, const void* d_src, uint64_t n, void* d_dst, ui
 int zz_encode_batch_device(zz_ctx* ctx, uint64_t nitems, const void* const* d_srcs, const uint64_t* d_ns,
                            void* const* d_dsts, const uint64_t* d_caps, uint64_t* d_out_lens,
                            int format, int level, uint32_t packet_size, void* hip_stream);
+/* The same call with flags; zz_encode_batch_device is this call with flags = 0. Unknown bits give ZZ_E_ARG.
+ * ZZ_BATCH_EXTENDED is the call's own switch for the extended levels 4, 5, 6 (hash chains of depth 2 / 4 / 8, lazy matching,
+ * package-merge code lengths): item i becomes exactly the stream zz_encode_device writes for it alone on a context with
+ * zz_ctx_set_extended_levels on, at the same format, level and packet size; an empty item gets the empty final block of
+ * level 2. The window rule: packet k of an item sees the min(k * packet_size, 8192) bytes in front of it at level 4, and
+ * min(k * packet_size, 32768) bytes at levels 5 and 6, all of its own item -- no position in front of an item belongs to
+ * its window, whatever lies there in memory. With the switch set, in this order: a warm window on the context gives
+ * ZZ_E_UNSUPPORTED; the context's extended switch does not matter (it stays the switch of the single-stream calls); a level
+ * outside 0..6 gives ZZ_E_LEVEL; levels 4..6 on a device whose LDS does not serve equal addresses in lane order give
+ * ZZ_E_UNSUPPORTED (as zz_ctx_set_extended_levels does); levels 0..3 are the calls as they are without the switch.
+ * zz_ctx_last_kernel_ms covers both kernels of the extended levels. Workspace at levels 4..6: a single extended call's over
+ * the batch's packets, which counts 4 * packet_size bytes of match words for every packet of a round, however short the
+ * packet is, and one CU-owning workgroup per packet -- a batch of very small items pays for full packets. */
+enum { ZZ_BATCH_EXTENDED = 1 };
+int zz_encode_batch_flags_device(zz_ctx* ctx, uint64_t nitems, const void* const* d_srcs, const uint64_t* d_ns,
+                                 void* const* d_dsts, const uint64_t* d_caps, uint64_t* d_out_lens,
+                                 int format, int level, uint32_t packet_size, int flags, void* hip_stream);
 
 /* One buffer to one blocked gzip (BGZF) file: what bgzip -d, samtools, tabix, gzip(1) and zz_decode_members_device (its
  * parallel path, no index needed) read, a random-access format (member offset + offset inside the member), and one that
@@ -161,12 +179,21 @@ int zz_encode_batch_device(zz_ctx* ctx, uint64_t nitems, const void* const* d_sr
  *     (65,280 with packets of 32,768 or 4,096 is accepted, with packets of 1,000 it is not); max_offsets < members + 1; more
  *     than 2^31 - 1 members or packets.
  *   ZZ_E_LEVEL: level outside 0..3.   ZZ_E_UNSUPPORTED: the context has a warm window or the extended levels switched on.
+ *   With ZZ_MEMBERS_EXTENDED in flags (the call's own switch, as ZZ_BATCH_EXTENDED of zz_encode_batch_flags_device): levels 0..6.
+ *     A member's body at level 4, 5 or 6 is the raw-deflate stream of its block alone at that extended level -- packet k sees
+ *     the min(k * packet_size, 8192) bytes (level 4) or min(k * packet_size, 32768) bytes (levels 5, 6) of its own block in
+ *     front of it and nothing in front of the block -- or the block's level-0 stream where that is shorter: the rule above
+ *     with "levels 0..3" widened. In this order: a warm window on the context gives ZZ_E_UNSUPPORTED; the context's extended
+ *     switch does not matter; a level outside 0..6 gives ZZ_E_LEVEL; levels 4..6 on a device with a negative LDS-order verdict
+ *     give ZZ_E_UNSUPPORTED. zz_encode_members_bound does not depend on the level or on this bit.
  *   ZZ_E_NOSPACE: the file does not fit cap; *out_len = ~0 and no byte of d_dst is written (decided on the device from the
  *     scanned sizes before any pass stores).
  * Synchronous: the host reads one small record, whatever the member count, and device-side consumers of d_dst wait for the
  * call. Like a batch it is not a "last call" for zz_verify_last_device, zz_packet_extent_device and zz_packet_index_device,
- * and it leaves the decode state alone. Workspace: a batch's over the same blocks, plus 25 bytes per member. */
+ * and it leaves the decode state alone. Workspace: a batch's over the same blocks, plus 25 bytes per member (levels 4..6:
+ * an extended batch's, 4 * packet_size bytes of match words per packet of a round included). */
 enum { ZZ_MEMBERS_NO_EOF = 1 };
+enum { ZZ_MEMBERS_EXTENDED = 2 };
 #define ZZ_MEMBERS_BLOCK 65280u
 int zz_encode_members_device(zz_ctx* ctx, const void* d_src, uint64_t n, void* d_dst, uint64_t cap, uint64_t* out_len,
                              int level, uint32_t block_size, uint32_t packet_size, int flags,

@@ -24,6 +24,8 @@ DEFAULT_PACKET = 32768
 POINTS_SPACING = 131072          # decoded bytes between two points of a point index (ZZ_POINTS_SPACING_DEFAULT)
 MEMBERS_BLOCK = 65280            # input bytes per member of a blocked gzip file (bgzip's)
 MEMBERS_NO_EOF = 1
+MEMBERS_EXTENDED = 2                 # zz_encode_members_device's flags: levels 4..6 through the call's own switch
+BATCH_EXTENDED = 1                   # zz_encode_batch_flags_device's flags: the same for batches
 _ERR = (1 << 64) - 1
 
 
@@ -79,6 +81,7 @@ def _load():
         "zz_encode_device": (i32, [vp, vp, u64, vp, u64, pu64, i32, i32, u32, vp]),
         "zz_encode_device_async": (i32, [vp, vp, u64, vp, u64, i32, i32, u32, vp]),
         "zz_encode_batch_device": (i32, [vp, u64, vp, vp, vp, vp, vp, i32, i32, u32, vp]),
+        "zz_encode_batch_flags_device": (i32, [vp, u64, vp, vp, vp, vp, vp, i32, i32, u32, i32, vp]),
         "zz_encode_members_device": (i32, [vp, vp, u64, vp, u64, pu64, i32, u32, u32, i32, vp, u64, vp]),
         "zz_encode_members_bound": (u64, [u64, u32, u32, i32]),
         "zz_members_header": (i32, [u32, vp]),
@@ -436,7 +439,18 @@ class Context:
         """Many independent streams in one call: item i = ``srcs[i]`` becomes its own complete stream in ``dsts[i]``, the bytes
         ``encode`` would write for it alone. Items are uint8 tensors on this context's device (their whole length) or
         ``(data_ptr, nbytes)`` pairs; ``caps`` defaults to each destination's size. Returns the list of lengths, ``None``
-        for an item that did not fit its destination (the others are complete). Levels 0..3, cold packets."""
+        for an item that did not fit its destination (the others are complete). Levels 0..3, cold packets; levels 4..6:
+        ``encode_batch_extended``."""
+        return self._encode_batch(srcs, dsts, format, level, packet_size, caps, stream, 0)
+
+    def encode_batch_extended(self, srcs, dsts, format=Format.Zlib, level=6, packet_size=DEFAULT_PACKET, caps=None, stream=None):
+        """``encode_batch`` with the call's own switch for the extended levels set (``BATCH_EXTENDED``): levels 0..6, whatever
+        ``set_extended_levels`` says -- that stays ``encode``'s switch. At levels 4..6 an item is the stream ``encode`` writes
+        for it alone with the extended levels on; a packet's window is the bytes of its own item in front of it (at most
+        8 KiB at level 4, 32 KiB at levels 5 and 6) and never reaches in front of the item. Levels 0..3 are ``encode_batch``."""
+        return self._encode_batch(srcs, dsts, format, level, packet_size, caps, stream, BATCH_EXTENDED)
+
+    def _encode_batch(self, srcs, dsts, format, level, packet_size, caps, stream, flags):
         import torch
         if len(srcs) != len(dsts):
             raise ValueError(f"{len(srcs)} sources but {len(dsts)} destinations")
@@ -455,8 +469,8 @@ class Context:
         table = torch.tensor([[p for p, _ in s], [nb for _, nb in s], [p for p, _ in d], cp], dtype=torch.int64).to(dev)
         out = torch.empty(k, dtype=torch.int64, device=dev)
         st = self._stream() if stream is None else stream
-        rc = lib.zz_encode_batch_device(self._h, k, table[0].data_ptr(), table[1].data_ptr(), table[2].data_ptr(),
-                                        table[3].data_ptr(), out.data_ptr(), int(format), int(level), packet_size, st)
+        rc = lib.zz_encode_batch_flags_device(self._h, k, table[0].data_ptr(), table[1].data_ptr(), table[2].data_ptr(),
+                                              table[3].data_ptr(), out.data_ptr(), int(format), int(level), packet_size, flags, st)
         if rc not in (0, E_NOSPACE):
             _check(rc)
         return [None if v == -1 else v for v in out.cpu().tolist()]
@@ -496,7 +510,18 @@ class Context:
         ``gzip.decompress`` and ``decode_members`` (in parallel) read it. A member is the raw-deflate stream ``encode_batch``
         writes for its block, or the block's level-0 stream where that is shorter. ``offsets``: an int64 tensor on this
         context's device that receives members + 1 file offsets (``gzi_bytes`` turns its host copy into a ``.gzi`` index).
-        Returns the file's length; raises ZzFlateError (E_NOSPACE: it does not fit ``cap``, nothing is written). Levels 0..3."""
+        Returns the file's length; raises ZzFlateError (E_NOSPACE: it does not fit ``cap``, nothing is written). Levels 0..3;
+        levels 4..6 (bgzip's default is 6): ``encode_members_extended``."""
+        return self._encode_members(src, n, dst, cap, level, block_size, packet_size, eof, offsets, stream, 0)
+
+    def encode_members_extended(self, src, n, dst, cap, level=6, block_size=MEMBERS_BLOCK, packet_size=DEFAULT_PACKET, eof=True,
+                                offsets=None, stream=None):
+        """``encode_members`` with the call's own switch for the extended levels set (``MEMBERS_EXTENDED``): levels 0..6, whatever
+        ``set_extended_levels`` says. At levels 4..6 a member's body is its block's raw-deflate stream at that level -- no match
+        reaches in front of the block -- or the block's level-0 stream where that is shorter. The same readers read the file."""
+        return self._encode_members(src, n, dst, cap, level, block_size, packet_size, eof, offsets, stream, MEMBERS_EXTENDED)
+
+    def _encode_members(self, src, n, dst, cap, level, block_size, packet_size, eof, offsets, stream, flags):
         out = ctypes.c_uint64(0)
         st = self._stream() if stream is None else stream
         op, on = None, 0
@@ -508,7 +533,7 @@ class Context:
                 raise ValueError(f"offsets must live on this context's device (cuda:{self.device}), not {offsets.device}")
             op, on = offsets.data_ptr(), offsets.numel()
         _check(lib.zz_encode_members_device(self._h, self._ptr(src), n, self._ptr(dst), cap, ctypes.byref(out), int(level), block_size,
-                                            packet_size, 0 if eof else MEMBERS_NO_EOF, op, on, st))
+                                            packet_size, (0 if eof else MEMBERS_NO_EOF) | flags, op, on, st))
         return out.value
 
     def last_encode_members_stats(self):

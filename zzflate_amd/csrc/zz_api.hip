@@ -694,12 +694,12 @@ static int ensure_items(zz_ctx* c, uint64_t items_plus_one)
     return c->bat.tails.grow(items_plus_one * 128);
 }
 // batches and members, per packet: sizes, offsets and checksum partials, the items' slots end to end (slot_bytes == 0: none),
-// level 2's scratch, the descriptors
-static int ensure_batch_workspace(zz_ctx* c, int level, uint32_t npk, uint64_t slot_bytes, uint32_t P)
+// level 2's scratch (xdepth: with the extended levels' words and chains), the descriptors
+static int ensure_batch_workspace(zz_ctx* c, int level, uint32_t npk, uint64_t slot_bytes, uint32_t P, int xdepth)
 {
     if (int rc = ensure_workspace(c, 0, npk, 0)) return rc;
     if (int rc = c->slots.grow(slot_bytes)) return rc;
-    if (level >= 2) if (int rc = c->l2_scratch.grow(l2_scratch_bytes(npk, 0, P))) return rc;
+    if (level >= 2) if (int rc = c->l2_scratch.grow(l2_scratch_bytes(npk, xdepth, P))) return rc;
     return c->bat.desc.grow(npk);
 }
 // staging of the host-buffer entry points and of zz_encode_multi_device's pulls (64 bytes of room behind what was asked for)
@@ -728,6 +728,7 @@ static bool l2_classic()
 // k_encode_l2p (its insert is an ordered exchange: zz_level2p.h, ZZ_L2P_XCHG) instead of k_encode_l2_t<0, false>; both want cold packets,
 // a positive LDS-order verdict and no ZZFLATE_L?_KERNEL=classic, and one_parser (the rerun behind a violation) rules them out.
 // order_checked: the launch relies on the LDS's lane order and checks it as it goes (error value 4): those two, and the warm window's pre-hash.
+// (The extended levels, a batch's or a member file's too, come as level 2 with their window and xdepth: neither form, no check.)
 struct launch_plan { bool l1p, l2p, order_checked; };
 static launch_plan plan_launch(const zz_ctx* c, int level, uint32_t warm, int xdepth, bool one_parser)
 {
@@ -2180,9 +2181,40 @@ extern "C" int zz_encode_shard_finish(zz_ctx* c, uint64_t* out_len, uint32_t* ck
 }
 
 // ---- many independent streams in one call (zz_batch.h) --------------------------------------------------------------------
-static int encode_batch(zz_ctx* c, uint32_t nitems, const uint8_t* const* d_srcs, const uint64_t* d_ns, uint8_t* const* d_dsts,
-                        const uint64_t* d_caps, uint64_t* d_out_lens, int format, int level, uint32_t P, hipStream_t st, bool one_parser)
+// What a batch or a member file runs at: the level of its frame (slots, strides, the join), and for the extended levels the chain
+// depth and the window they bring.
+struct batch_level { int level, xdepth; uint32_t warm; };
+// Batches and members accept a level. Without the call's own extended switch: as ever -- cold packets of levels 0..3, and a context with a
+// warm window or the extended levels on is refused. With it: the context's extended switch does not matter (it stays the single-stream
+// calls'), a warm window still refuses, levels 0..3 are the same calls, and levels 4..6 run in level 2's frame where the device's
+// LDS-order verdict is positive (as zz_ctx_set_extended_levels asks).
+static int accept_batch_level(zz_ctx* c, int level, bool extended, const char* what, batch_level* out)
 {
+    if (c->warm || (c->extended && !extended)) {
+        set_err(std::string(what) + " take cold packets of levels 0..3: switch the warm window and the extended levels off on this context");
+        return ZZ_E_UNSUPPORTED;
+    }
+    out->level = level; out->xdepth = 0; out->warm = 0;
+    if (extended && level >= 4 && level <= 6) {
+        if (!lds_order_ok(c->device)) {
+            set_err("extended levels refused: this device's LDS does not serve equal addresses in lane order (probe k_lds_order_probe failed)");
+            return ZZ_E_UNSUPPORTED;
+        }
+        out->xdepth = level == 4 ? 2 : level == 5 ? 4 : 8;
+        out->warm = level == 4 ? 8192u : 32768u;
+        out->level = 2;
+        return ZZ_OK;
+    }
+    if (level < 0 || level > 3) {
+        set_err(extended ? "level must be 0..6" : "level must be 0..3 (zzflate.cpp:201,230)");
+        return ZZ_E_LEVEL;
+    }
+    return ZZ_OK;
+}
+static int encode_batch(zz_ctx* c, uint32_t nitems, const uint8_t* const* d_srcs, const uint64_t* d_ns, uint8_t* const* d_dsts,
+                        const uint64_t* d_caps, uint64_t* d_out_lens, int format, batch_level lv, uint32_t P, hipStream_t st, bool one_parser)
+{
+    const int level = lv.level;
     const int cks_kind = cks_kind_for(format);
     begin_encode_call(c);
     if (int rc = ensure_items(c, (uint64_t)nitems + 1)) return rc;
@@ -2198,8 +2230,8 @@ static int encode_batch(zz_ctx* c, uint32_t nitems, const uint8_t* const* d_srcs
     if (npk64 > 0x7FFFFFFFull) { set_err("too many packets for one call"); return ZZ_E_ARG; }
     const uint32_t npk = (uint32_t)npk64;
     // the same kernel choice as a single call, and the same run-time check behind the LDS-order verdict
-    const launch_plan plan = plan_launch(c, level, 0, 0, one_parser);
-    if (npk) if (int rc = ensure_batch_workspace(c, level, npk, slot_bytes, P)) return rc;
+    const launch_plan plan = plan_launch(c, level, lv.warm, lv.xdepth, one_parser);     // (the extended levels: no two-parser kernel, no order check, no rerun)
+    if (npk) if (int rc = ensure_batch_workspace(c, level, npk, slot_bytes, P, lv.xdepth)) return rc;
     zz_batch_map M;
     M.desc = c->bat.desc; M.srcs = d_srcs; M.ns = d_ns; M.first = c->bat.first; M.tails = c->bat.tails; M.npk = npk; M.level = level;
     if (npk) {
@@ -2207,7 +2239,8 @@ static int encode_batch(zz_ctx* c, uint32_t nitems, const uint8_t* const* d_srcs
         if (level >= 1)
             hipLaunchKernelGGL(k_batch_tails, dim3(nitems < 65536 ? nitems : 65536), dim3(128), 0, st, d_srcs, d_ns, nitems, c->bat.tails);
         zz_packet_params pp = packet_params(c, npk, P, cks_kind, plan);
-        if (int rc = launch_packet_encoders(c, pp, &M, level, 0, plan, st)) return rc;
+        pp.warm = lv.warm;
+        if (int rc = launch_packet_encoders(c, pp, &M, level, lv.xdepth, plan, st)) return rc;
         if (level == 0) {
             zz_l0_batch_params q; q.pk = pp; q.dsts = d_dsts; q.caps = d_caps; q.format = format;
             hipLaunchKernelGGL(k_encode_l0_batch, dim3(npk < 16384 ? npk : 16384), dim3(256), 0, st, q, M);
@@ -2228,7 +2261,7 @@ static int encode_batch(zz_ctx* c, uint32_t nitems, const uint8_t* const* d_srcs
     HIPCHK(hipMemcpyAsync(c->bat.h_tot, c->bat.d_tot, sizeof(zz_batch_totals), hipMemcpyDeviceToHost, st));
     const int ew = finish_err_word(c, plan.order_checked, st);
     if (ew == ERR_RERUN)                 // as encode_finish: the whole batch runs again on the one-parser kernels
-        return encode_batch(c, nitems, d_srcs, d_ns, d_dsts, d_caps, d_out_lens, format, level, P, st, true);
+        return encode_batch(c, nitems, d_srcs, d_ns, d_dsts, d_caps, d_out_lens, format, lv, P, st, true);
     if (ew) return ew;
     if (c->bat.h_tot->nospace) {
         set_err(std::to_string(c->bat.h_tot->nospace) + " of " + std::to_string(nitems) + " items did not fit their destination");
@@ -2237,26 +2270,30 @@ static int encode_batch(zz_ctx* c, uint32_t nitems, const uint8_t* const* d_srcs
     return ZZ_OK;
 }
 
-extern "C" int zz_encode_batch_device(zz_ctx* c, uint64_t nitems, const void* const* d_srcs, const uint64_t* d_ns,
-                                      void* const* d_dsts, const uint64_t* d_caps, uint64_t* d_out_lens,
-                                      int format, int level, uint32_t P, void* hip_stream)
+extern "C" int zz_encode_batch_flags_device(zz_ctx* c, uint64_t nitems, const void* const* d_srcs, const uint64_t* d_ns,
+                                            void* const* d_dsts, const uint64_t* d_caps, uint64_t* d_out_lens,
+                                            int format, int level, uint32_t P, int flags, void* hip_stream)
 {
     if (!c) { set_err("null ctx"); return ZZ_E_ARG; }
+    if (flags & ~ZZ_BATCH_EXTENDED) { set_err("unknown flags"); return ZZ_E_ARG; }
     if (nitems == 0) return ZZ_OK;
     if (!d_srcs || !d_ns || !d_dsts || !d_caps || !d_out_lens) { set_err("null array"); return ZZ_E_ARG; }
     if (nitems > 0x7FFFFFFFull) { set_err("too many items for one call"); return ZZ_E_ARG; }
     if (call_pending(c)) return ZZ_E_ARG;
-    if (c->warm || c->extended) {
-        set_err("batches take cold packets of levels 0..3: switch the warm window and the extended levels off on this context");
-        return ZZ_E_UNSUPPORTED;
-    }
-    if (level < 0 || level > 3) { set_err("level must be 0..3 (zzflate.cpp:201,230)"); return ZZ_E_LEVEL; }
+    batch_level lv;
+    if (int rc = accept_batch_level(c, level, (flags & ZZ_BATCH_EXTENDED) != 0, "batches", &lv)) return rc;
     if (format < 0 || format > 2) format = ZZ_DEFLATE;   // zzflate.cpp:39-48 default branch
     if (P == 0) P = ZZ_DEFAULT_PACKET;
     if (P > ZZ_MAX_PACKET_SIZE) { set_err("packet size must be 1..32768"); return ZZ_E_ARG; }
     HIPCHK(hipSetDevice(c->device));
     return encode_batch(c, (uint32_t)nitems, (const uint8_t* const*)d_srcs, d_ns, (uint8_t* const*)d_dsts, d_caps, d_out_lens, format,
-                        level, P, (hipStream_t)hip_stream, false);
+                        lv, P, (hipStream_t)hip_stream, false);
+}
+extern "C" int zz_encode_batch_device(zz_ctx* c, uint64_t nitems, const void* const* d_srcs, const uint64_t* d_ns,
+                                      void* const* d_dsts, const uint64_t* d_caps, uint64_t* d_out_lens,
+                                      int format, int level, uint32_t P, void* hip_stream)
+{
+    return zz_encode_batch_flags_device(c, nitems, d_srcs, d_ns, d_dsts, d_caps, d_out_lens, format, level, P, 0, hip_stream);
 }
 
 // ---- one buffer to a blocked gzip (BGZF) file (zz_members_write.h) ----------------------------------------------------------
@@ -2285,10 +2322,11 @@ extern "C" int zz_members_header(uint32_t member_bytes, uint8_t out[18])
     return ZZ_MW_HEADER;
 }
 
-static int encode_members(zz_ctx* c, const uint8_t* d_src, uint64_t n, uint8_t* d_dst, uint64_t cap, uint64_t* out_len, int level,
+static int encode_members(zz_ctx* c, const uint8_t* d_src, uint64_t n, uint8_t* d_dst, uint64_t cap, uint64_t* out_len, batch_level lv,
                           uint32_t B, uint32_t P, int flags, uint64_t* d_member_offsets, hipStream_t st, bool one_parser)
 {
     auto& W = c->mw;
+    const int level = lv.level;
     begin_encode_call(c);
     // members, packets and slot bytes in closed form: the host reads nothing back before the launches
     const uint32_t m = (uint32_t)((n + B - 1) / B), ppm = (B + P - 1) / P;
@@ -2308,9 +2346,9 @@ static int encode_members(zz_ctx* c, const uint8_t* d_src, uint64_t n, uint8_t* 
     if (int rc = W.stored.grow(mm)) return rc;
     if (int rc = W.d_st.grow(1)) return rc;
     if (int rc = W.h_st.grow(1)) return rc;
-    if (npk) if (int rc = ensure_batch_workspace(c, level, npk, level ? slot_bytes : 0, P)) return rc;      // (level 0 has no slots)
+    if (npk) if (int rc = ensure_batch_workspace(c, level, npk, level ? slot_bytes : 0, P, lv.xdepth)) return rc;      // (level 0 has no slots)
     HIPCHK(hipMemsetAsync(c->d_err, 0, sizeof(uint32_t), st));
-    const launch_plan plan = plan_launch(c, level, 0, 0, one_parser);
+    const launch_plan plan = plan_launch(c, level, lv.warm, lv.xdepth, one_parser);
     zz_mw_params Q;
     Q.src = d_src; Q.n = n; Q.dst = d_dst; Q.cap = cap; Q.B = B; Q.P = P; Q.members = m; Q.ppm = ppm;
     Q.eof = (flags & ZZ_MEMBERS_NO_EOF) ? 0 : ZZ_MW_EOF; Q.level = level; Q.full_slots = full_slots;
@@ -2326,7 +2364,8 @@ static int encode_members(zz_ctx* c, const uint8_t* d_src, uint64_t n, uint8_t* 
             hipLaunchKernelGGL(k_batch_tails, dim3(m < 65536 ? m : 65536), dim3(128), 0, st, (const uint8_t* const*)W.srcs.p, (const uint64_t*)W.ns, m,
                                (uint8_t*)c->bat.tails);
         zz_packet_params pp = packet_params(c, npk, P, ZZ_CKS_CRC, plan);
-        if (int rc = launch_packet_encoders(c, pp, &M, level, 0, plan, st)) return rc;      // (level 0: the CRC pass alone; k_mw_stored writes the blocks)
+        pp.warm = lv.warm;
+        if (int rc = launch_packet_encoders(c, pp, &M, level, lv.xdepth, plan, st)) return rc;      // (level 0: the CRC pass alone; k_mw_stored writes the blocks)
         if (int rc = end_packet_encoders(c, level, npk, st)) return rc;
     }
     // the members' sizes and places, and the room check: nothing below stores a byte unless the file fits
@@ -2342,7 +2381,7 @@ static int encode_members(zz_ctx* c, const uint8_t* d_src, uint64_t n, uint8_t* 
     HIPCHK(hipMemcpyAsync(W.h_st, W.d_st, sizeof(zz_mw_state), hipMemcpyDeviceToHost, st));
     const int ew = finish_err_word(c, plan.order_checked, st);
     if (ew == ERR_RERUN)                 // as encode_batch: the whole call runs again on the one-parser kernels
-        return encode_members(c, d_src, n, d_dst, cap, out_len, level, B, P, flags, d_member_offsets, st, true);
+        return encode_members(c, d_src, n, d_dst, cap, out_len, lv, B, P, flags, d_member_offsets, st, true);
     if (ew) return ew;
     if (!W.h_st->fits) {
         set_err("the file (" + std::to_string(W.h_st->total + Q.eof) + " bytes) does not fit the destination");
@@ -2364,11 +2403,8 @@ extern "C" int zz_encode_members_device(zz_ctx* c, const void* d_src, uint64_t n
     if (!d_src && n) { set_err("null source"); return ZZ_E_ARG; }
     if (!d_dst && cap) { set_err("null destination"); return ZZ_E_ARG; }
     if (call_pending(c)) return ZZ_E_ARG;
-    if (c->warm || c->extended) {
-        set_err("members take cold packets of levels 0..3: switch the warm window and the extended levels off on this context");
-        return ZZ_E_UNSUPPORTED;
-    }
-    if (level < 0 || level > 3) { set_err("level must be 0..3 (zzflate.cpp:201,230)"); return ZZ_E_LEVEL; }
+    batch_level lv;
+    if (int rc = accept_batch_level(c, level, (flags & ZZ_MEMBERS_EXTENDED) != 0, "members", &lv)) return rc;
     uint32_t B = block_size, P = packet_size;
     if (!members_sizes(B, P)) {
         set_err("block size must be 1..65536, packet size 1..32768, and a block's stored member (26 bytes + its level-0 stream) at most 65536 bytes");
@@ -2378,7 +2414,7 @@ extern "C" int zz_encode_members_device(zz_ctx* c, const void* d_src, uint64_t n
     if (m > 0x7FFFFFFFull || m * ((B + P - 1) / P) > 0x7FFFFFFFull) { set_err("too many members or packets for one call"); return ZZ_E_ARG; }
     if (d_member_offsets && max_offsets < m + 1) { set_err("the offsets array takes members + 1 entries"); return ZZ_E_ARG; }
     HIPCHK(hipSetDevice(c->device));
-    return encode_members(c, (const uint8_t*)d_src, n, (uint8_t*)d_dst, cap, out_len, level, B, P, flags, d_member_offsets,
+    return encode_members(c, (const uint8_t*)d_src, n, (uint8_t*)d_dst, cap, out_len, lv, B, P, flags, d_member_offsets,
                           (hipStream_t)hip_stream, false);
 }
 extern "C" int zz_ctx_last_encode_members_stats(const zz_ctx* c, uint64_t* members, uint64_t* stored_members)

@@ -5,7 +5,9 @@
 //             k_batch_desc     per packet: {item, packet within the item, slot offset} (binary search over first[])
 //             k_batch_tails    per item: its 128-byte tail (k_fill_tail of one shard)
 //   encode    the batch forms of the packet kernels: the single-stream bodies, each packet seeing its item through
-//             zz_packet_view (zz_common.h) -- its src, end, tail, final flag, slot, size and checksum entries
+//             zz_packet_view (zz_common.h) -- its src, end, tail, final flag, slot, size and checksum entries; with the
+//             call's extended switch, levels 4..6 on k_l6_matches_batch (zz_level6.h) and k_encode_l2x_batch, the window
+//             of a packet being the bytes of its own item in front of it and nothing else
 //   join      k_scan_sizes     one exclusive scan over all packets: a packet's offset in its item is the difference to the
 //                              item's first packet (a segmented scan by subtraction)
 //             k_batch_finalize one wavefront per item: stream bytes, the checksum fold over its packets, room check, header,
@@ -160,6 +162,12 @@ template <bool PP>
 __global__ __launch_bounds__(PP ? ZZ_L2P_THREADS : ZZ_L2_THREADS, PP ? ZZ_L2P_WPE : 5) void k_encode_l2_batch_t(zz_l2_params Q, zz_batch_map M)
 {
     l2_encode_run<0u, false, PP>(Q, M);
+}
+
+// the extended levels 4..6: the parser reads k_l6_matches_batch's words (the row of m is the batch's packet number's), package-merge codes
+__global__ __launch_bounds__(ZZ_L2_THREADS, 6) void k_encode_l2x_batch(zz_l2_params Q, zz_batch_map M)
+{
+    l2_encode_run<32768u, true, false>(Q, M);
 }
 
 __global__ __launch_bounds__(ZZ_CRC_THREADS) void k_crc32_packets_batch(zz_packet_params B, zz_batch_map M) { crc32_packets_run(B, M); }

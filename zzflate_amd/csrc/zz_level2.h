@@ -1106,8 +1106,8 @@ struct zz_l2_params {
 // PP (levels 2,3 with cold packets: "k_encode_l2p"): THREE wavefronts -- the token pass on two parsers that take alternate
 // blocks (zz_level2p.h), wavefront 1 stays the helper, wavefront 2 is the second parser and sits out the rest of the packet at
 // the barriers. 27 wavefronts per CU: seven on one SIMD => at most 72 VGPRs.
-// MAP: zz_no_batch (one shard: the packets of Q.pk) or zz_batch_map (a batch, k_encode_l2_batch_t: Q.k0 .. Q.k1 number the batch's
-// packets, and every packet sees its own item through zz_packet_view).
+// MAP: zz_no_batch (one shard: the packets of Q.pk) or zz_batch_map (a batch, k_encode_l2_batch_t and k_encode_l2x_batch: Q.k0 .. Q.k1
+// number the batch's packets, and every packet sees its own item through zz_packet_view).
 // The code construction's part of that carve-up, in one place: the packet kernels and k_debug_code_lengths (below) lay the
 // Huffman scratch, the package-merge scratch, the lengths, the run-length records, the counts and the code tables out alike.
 #define ZZ_L2_LDS_LENS 6912u          // 320: lit/len lengths, then dist lengths at [288..318)
@@ -1236,7 +1236,7 @@ __device__ __forceinline__ void l2_encode_run(const zz_l2_params Q, const MAP M)
             if (XD) {
                 // the extended levels: every position's match is in Q.m already (k_l6_matches, zz_level6.h)
                 if (W0) {
-                    const uint32_t* mrow = Q.m + (uint64_t)(k - Q.k0) * P.packet_size;
+                    const uint32_t* mrow = Q.m + (uint64_t)(g - Q.k0) * P.packet_size;      // (the launch's packet number: a batch's k is its item's)
                     l6_parse_pass(hb, src, end, l1p_make_src(P, src, end), n, mrow);
                 }
             } else if (PP) {
@@ -1679,7 +1679,9 @@ static inline uint64_t l2_scratch_bytes(uint32_t npk, int xdepth, uint32_t P)
 template <bool PP> __global__ __launch_bounds__(PP ? ZZ_L2P_THREADS : ZZ_L2_THREADS, PP ? ZZ_L2P_WPE : 5) void k_encode_l2_batch_t(zz_l2_params Q, zz_batch_map M);   // zz_batch.h
 // two_parser: levels 2,3 with cold packets on k_encode_l2p (the caller decides: not behind ZZFLATE_L2_KERNEL=classic, and -- its insert
 // is an ordered LDS exchange -- only where the device's LDS-order verdict is positive)
-// M: a batch -- the batch forms of the two cold kernels over its pp.npk packets (no window, no extended levels)
+__global__ __launch_bounds__(ZZ_L2_THREADS, 6) void k_encode_l2x_batch(zz_l2_params Q, zz_batch_map M);   // zz_batch.h
+// M: a batch -- the batch forms of the two cold kernels over its pp.npk packets, or, with xdepth, of the extended levels' two kernels
+// (the same rounds, grids and workspace as a single stream's; every packet's window lies inside its own item)
 static inline void launch_level2(const zz_packet_params& pp, uint8_t* scratch, uint32_t* work, hipStream_t st, int xdepth, bool two_parser,
                                  const zz_batch_map* M)
 {
@@ -1702,12 +1704,17 @@ static inline void launch_level2(const zz_packet_params& pp, uint8_t* scratch, u
             (void)hipMemsetAsync(work, 0, 2 * sizeof(uint32_t), st);
             zz_l6m_params qm; qm.pk = pp; qm.m = m; qm.chains = chains; qm.work = work + 1; qm.k0 = k0; qm.k1 = k1;
             const dim3 gm((k1 - k0) < mgrid ? (k1 - k0) : mgrid), bm(ZZ_L6M_THREADS);
-            if (xdepth == 2) hipLaunchKernelGGL((k_l6_matches<2>), gm, bm, 0, st, qm);
+            if (M) {
+                if (xdepth == 2) hipLaunchKernelGGL((k_l6_matches_batch<2>), gm, bm, 0, st, qm, *M);
+                else if (xdepth == 4) hipLaunchKernelGGL((k_l6_matches_batch<4>), gm, bm, 0, st, qm, *M);
+                else hipLaunchKernelGGL((k_l6_matches_batch<8>), gm, bm, 0, st, qm, *M);
+            } else if (xdepth == 2) hipLaunchKernelGGL((k_l6_matches<2>), gm, bm, 0, st, qm);
             else if (xdepth == 4) hipLaunchKernelGGL((k_l6_matches<4>), gm, bm, 0, st, qm);
             else hipLaunchKernelGGL((k_l6_matches<8>), gm, bm, 0, st, qm);
             q.m = m; q.k0 = k0; q.k1 = k1;
             const dim3 g(l2_grid(k1 - k0, true)), b(ZZ_L2_THREADS);
-            hipLaunchKernelGGL((k_encode_l2_t<32768u, true>), g, b, 0, st, q);
+            if (M) hipLaunchKernelGGL(k_encode_l2x_batch, g, b, 0, st, q, *M);
+            else hipLaunchKernelGGL((k_encode_l2_t<32768u, true>), g, b, 0, st, q);
         }
         return;
     }

@@ -163,10 +163,12 @@ __device__ __forceinline__ uint32_t lds_match16(zz_lds_bytes base, uint32_t off,
 #endif
 }
 
-template <int DEPTH>
-__global__ __launch_bounds__(ZZ_L6M_THREADS) void k_l6_matches(zz_l6m_params Q)
+// MAP: zz_no_batch (one shard: the packets of Q.pk) or zz_batch_map (k_l6_matches_batch: Q.k0 .. Q.k1 number the batch's packets; every
+// packet sees its own item through zz_packet_view -- src, n, no halo, the last packet final -- so the window never leaves the item).
+// The row of m belongs to the launch's packet number g, which is the shard's k for a single stream.
+template <int DEPTH, class MAP>
+__device__ __forceinline__ void l6_matches_run(const zz_l6m_params Q, const MAP M)
 {
-    const zz_packet_params& P = Q.pk;
     __shared__ __attribute__((aligned(16))) uint16_t sorted[ZZ_L6_SORT_ENTRIES];     // step 3: the window and the packet, as bytes
     __shared__ __attribute__((aligned(16))) uint32_t Tw[ZZ_HASH_SIZE / 2 + 4];      // 8192 16-bit counters, two per word (+ the one lanes without a position use)
     __shared__ __attribute__((aligned(16))) uint32_t ring[2][ZZ_L6M_ROUND][ZZ_WAVE];
@@ -178,8 +180,12 @@ __global__ __launch_bounds__(ZZ_L6M_THREADS) void k_l6_matches(zz_l6m_params Q)
     uint16_t* const chains = Q.chains + (uint64_t)blockIdx.x * (32768u * DEPTH);
     ZZ_PROF_DECL
 
-    uint32_t k = Q.k0 + blockIdx.x;
-    while (k < Q.k1) {
+    uint32_t g = Q.k0 + blockIdx.x;
+    while (g < Q.k1) {
+        uint32_t k;
+        // this packet's view of its shard, by value in both forms (the single stream's is a copy of Q.pk: with the body behind a call,
+        // this is the form in which k_l6_matches<DEPTH> keeps the resource lines it had -- tests/test_encode_extended_batch_resources.py)
+        const zz_packet_params P = zz_packet_view(Q.pk, M, g, k);
         const uint64_t off = (uint64_t)k * P.packet_size;
         const uint32_t len = (uint32_t)((P.n - off) < P.packet_size ? (P.n - off) : P.packet_size);
         const bool is_final = P.last_is_final && k == P.npk - 1;
@@ -188,7 +194,7 @@ __global__ __launch_bounds__(ZZ_L6M_THREADS) void k_l6_matches(zz_l6m_params Q)
         const uint64_t before = P.halo + off;
         const int32_t W = (int32_t)(before < P.warm ? before : P.warm);
         const uint32_t target = l6_target(n);
-        uint32_t* const mrow = Q.m + (uint64_t)(k - Q.k0) * P.packet_size;
+        uint32_t* const mrow = Q.m + (uint64_t)(g - Q.k0) * P.packet_size;
         if (target) {
             const int32_t lo = -W, hi = (int32_t)target;
             ZZ_T(13);
@@ -404,9 +410,20 @@ __global__ __launch_bounds__(ZZ_L6M_THREADS) void k_l6_matches(zz_l6m_params Q)
         __syncthreads();
         if (tid == 0) nextk = Q.k0 + gridDim.x + atomicAdd(Q.work, 1u);
         __syncthreads();
-        k = nextk;
+        g = nextk;
     }
-    ZZ_PROF_FLUSH(P);
+    ZZ_PROF_FLUSH(Q.pk);
+}
+template <int DEPTH>
+__global__ __launch_bounds__(ZZ_L6M_THREADS) void k_l6_matches(zz_l6m_params Q)
+{
+    l6_matches_run<DEPTH>(Q, zz_no_batch());
+}
+// the batch form (zz_encode_batch_device and zz_encode_members_device with their extended switch): packets of many items in one launch
+template <int DEPTH>
+__global__ __launch_bounds__(ZZ_L6M_THREADS) void k_l6_matches_batch(zz_l6m_params Q, zz_batch_map M)
+{
+    l6_matches_run<DEPTH>(Q, M);
 }
 
 // ===== kernel 2's parser: the greedy parse over those words; hands every block's matches to the helper wavefront in the

@@ -11,6 +11,10 @@
 // would pass 65,536 bytes (mw_geometry_ok). Behind the last member comes bgzip's empty member of 28 bytes (mw_eof) unless
 // ZZ_MEMBERS_NO_EOF is set.
 //
+// With ZZ_MEMBERS_EXTENDED the level may be 4, 5 or 6: the body is then what the batch call with ZZ_BATCH_EXTENDED writes for the
+// block -- the rule above with "levels 0..3" widened, a packet's window being the block's own bytes in front of it. Everything in
+// this file sees such a call as level 2 (slots, strides, the stored fallback).
+//
 // The packet kernels are the batch's (zz_batch.h), with block i as item i. The passes of this file:
 //   plan      k_mw_items       per member: srcs[i] = src + i * B, ns[i], first[i] = i * ppm (closed forms: nothing is read back)
 //             k_mw_desc        per packet: {member, packet within it, slot offset}
