@@ -105,9 +105,9 @@ def test_lds_order_guard_hook_answers_without_a_device():
 
 
 def test_shipped_library_carries_no_experiment_switch():
-    """zz_level1.h / zz_level1p.h hold timing experiments behind macros that write WRONG streams (ZZ_L1_PIPE_PROBE, ZZ_L1P_X_*),
-    cycle stamps (ZZ_PROF) and the test build's ZZ_ST_ALWAYS_CAREFUL: the library the package loads must be built without any
-    of them, and the test build must own up to its one."""
+    """zz_build_flags() names the switches that change what a build computes or records: cycle stamps (ZZ_PROF) and the test
+    build's ZZ_ST_ALWAYS_CAREFUL (the wrong-stream timing experiments it once guarded against are gone from the source). The library
+    the package loads must be built without either, and the test build must own up to its one."""
     L = ctypes.CDLL(zz._build.LIB)
     L.zz_build_flags.restype = ctypes.c_char_p
     assert L.zz_build_flags() == b"", L.zz_build_flags()
@@ -117,6 +117,42 @@ def test_shipped_library_carries_no_experiment_switch():
         C = ctypes.CDLL(careful)
         C.zz_build_flags.restype = ctypes.c_char_p
         assert C.zz_build_flags().split() == [b"ZZ_ST_ALWAYS_CAREFUL"]
+
+
+def macros_in_conditionals():
+    """the macro names that a #if / #ifdef / #ifndef / #elif of zzflate_amd/csrc/* tests (the compiler's own __... ones left out)"""
+    names = set()
+    csrc = os.path.join(ROOT, "zzflate_amd", "csrc")
+    for f in sorted(os.listdir(csrc)):
+        text = open(os.path.join(csrc, f)).read().replace("\\\n", " ")
+        for m in re.finditer(r"^[ \t]*#[ \t]*(?:if|ifdef|ifndef|elif)\b(.*)$", text, flags=re.M):
+            expr = re.sub(r"//.*|/\*.*?\*/", "", m.group(1))
+            names.update(n for n in re.findall(r"[A-Za-z_]\w*", expr) if n != "defined" and not n.startswith("__"))
+    return names
+
+
+def switches_in_design_md():
+    """the names in the first column of DESIGN.md's "Compile-time switches" table; every row also has a default and a builder"""
+    text = open(os.path.join(ROOT, "DESIGN.md")).read()
+    section = re.search(r"^### Compile-time switches\n(.*?)(?=^#)", text, flags=re.M | re.S).group(1)
+    rows = [r for r in section.splitlines() if r.startswith("|")][2:]        # (behind the head and its rule)
+    names = []
+    for r in rows:
+        cells = [c.strip() for c in r.strip().strip("|").split("|")]
+        assert len(cells) == 3 and all(cells), r
+        found = re.findall(r"`([A-Za-z_]\w*)`", cells[0])
+        assert found, r
+        names += found
+    assert len(names) == len(set(names)), names
+    return set(names)
+
+
+def test_compile_time_switches_are_the_documented_ones():
+    """Every macro the sources test in a conditional is in DESIGN.md's "Compile-time switches" table (name, default, who builds
+    it), and the table lists nothing else: an experiment switch is written down or does not go in, and a retired one leaves both."""
+    tested, listed = macros_in_conditionals(), switches_in_design_md()
+    assert len(tested) >= 10
+    assert tested == listed, {"not in DESIGN.md": sorted(tested - listed), "not in the source": sorted(listed - tested)}
 
 
 def test_product_does_not_touch_oracle():

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Build variants of the library with one macro set to each given value and bench them (run on a GPU box):
-#   tools/sweep_define.sh ZZ_L1_PREFETCH 128 384 1024 -- --steps 10 --no-cpu --no-extra
+#   tools/sweep_define.sh ZZ_L1P_ADLER_U 2 4 6 8 -- --steps 10 --no-cpu --no-extra
 set -e
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 M=$1; shift

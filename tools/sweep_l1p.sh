@@ -1,6 +1,7 @@
 #!/bin/bash
 # Build variants of the library with sets of -D flags and bench them on one box (run on a GPU box):
-#   tools/sweep_l1p.sh "-DZZ_L1P_LEN_LATE=0 -DZZ_L1P_TOK_EARLY=0" "-DZZ_L1P_LEN_LATE=1 -DZZ_L1P_TOK_EARLY=0" ... [-- gens]
+#   tools/sweep_l1p.sh "-DZZ_L1P_PRIO_W=3 -DZZ_L1P_PRIO_F=1" "-DZZ_L1P_PRIO_W=2 -DZZ_L1P_PRIO_F=0 -DZZ_L1P_ADLER_U=4" ... [-- gens]
+# (several numeric knobs at once, two alternating rounds; one knob over several values: tools/sweep_define.sh)
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 VARS=()
 while [ "$1" != "--" ] && [ $# -gt 0 ]; do VARS+=("$1"); shift; done

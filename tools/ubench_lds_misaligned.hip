@@ -1,5 +1,5 @@
 // Probe: what does a byte-addressed (misaligned) LDS read cost on gfx950? The compiler emits ds_read_b64 / ds_read_b32 for align-1
-// accesses, and the results are right (k_l6_matches with -DZZ_L6_WORDS4=2 is bit-exact) -- but level 6 lost 22 % with them
+// accesses, and the results are right (k_l6_matches with -DZZ_L6_WORDS4=2, a switch of the tree at 603f283, is bit-exact) -- but level 6 lost 22 % with them
 // (profiles/r05_ab_l6_unaligned_reads_and_packed_key.txt). Here: 64 lanes gather at pseudo-random offsets of a 64 KiB image, as
 // the candidates of k_l6_matches do, with the offset's low bits forced to a given misalignment; throughput form (32 independent
 // reads in flight per measurement), one wavefront and sixteen wavefronts per workgroup; cycles per read instruction from s_memtime.

@@ -45,38 +45,14 @@ static thread_local std::string g_err;
 static void set_err(const std::string& s) { g_err = s; }
 extern "C" const char* zz_last_error(void) { return g_err.c_str(); }
 extern "C" const char* zz_version(void) { return "zzflate_amd 0.1 (gfx950)"; }
-// Compile-time switches this binary was built with, as a space-separated list; "" for the product build. The ZZ_*_X_* ones and the probe write
-// WRONG STREAMS (timing experiments: tools/pipe_probe.sh, tools/units_probe.sh); ZZ_PROF adds cycle stamps; the last one is the
-// test build libzzflate_amd_careful.so. tests/test_abi.py holds the shipped library to "".
+// Compile-time switches this binary was built with that change what it computes or records, as a space-separated list; "" for the
+// product build. ZZ_PROF adds cycle stamps (tools/prof_l1p.py, tools/prof_phases.py); ZZ_ST_ALWAYS_CAREFUL is the test build
+// libzzflate_amd_careful.so. tests/test_abi.py holds the shipped library to "".
 extern "C" const char* zz_build_flags(void)
 {
     return ""
-#ifdef ZZ_L1_PIPE_PROBE
-        " ZZ_L1_PIPE_PROBE"
-#endif
-#ifdef ZZ_L1P_X_NOCROSS
-        " ZZ_L1P_X_NOCROSS"
-#endif
-#ifdef ZZ_L1P_X_NOEMIT
-        " ZZ_L1P_X_NOEMIT"
-#endif
-#ifdef ZZ_L1P_X_NOEXT
-        " ZZ_L1P_X_NOEXT"
-#endif
-#ifdef ZZ_L2P_X_NOEXT
-        " ZZ_L2P_X_NOEXT"
-#endif
-#if ZZ_L2P_FLAGS
-        " ZZ_L2P_FLAGS"
-#endif
-#if !ZZ_L2P_XCHG
-        " ZZ_L2P_XCHG=0"
-#endif
 #ifdef ZZ_PROF
         " ZZ_PROF"
-#endif
-#ifdef ZZ_L1_EMIT_PRIO
-        " ZZ_L1_EMIT_PRIO"
 #endif
 #ifdef ZZ_ST_ALWAYS_CAREFUL
         " ZZ_ST_ALWAYS_CAREFUL"
@@ -725,7 +701,7 @@ static bool l2_classic()
 }
 // Which kernel form a packet-mode launch takes -- the one place that decides it, for single calls, batches (warm = 0, xdepth = 0) and the
 // zz_debug_l?_kernel queries. l1p: level 1 on k_encode_l1p (two parsing wavefronts) instead of k_encode_l1; l2p: levels 2,3 on
-// k_encode_l2p (its insert is an ordered exchange: zz_level2p.h, ZZ_L2P_XCHG) instead of k_encode_l2_t<0, false>; both want cold packets,
+// k_encode_l2p (its insert is an ordered exchange: zz_level2p.h) instead of k_encode_l2_t<0, false>; both want cold packets,
 // a positive LDS-order verdict and no ZZFLATE_L?_KERNEL=classic, and one_parser (the rerun behind a violation) rules them out.
 // order_checked: the launch relies on the LDS's lane order and checks it as it goes (error value 4): those two, and the warm window's pre-hash.
 // (The extended levels, a batch's or a member file's too, come as level 2 with their window and xdepth: neither form, no check.)
@@ -734,8 +710,8 @@ static launch_plan plan_launch(const zz_ctx* c, int level, uint32_t warm, int xd
 {
     launch_plan p;
     p.l1p = level == 1 && !warm && !one_parser && !l1_classic() && lds_order_cached(c->device);
-    p.l2p = level >= 2 && !warm && xdepth == 0 && !one_parser && !l2_classic() && (!ZZ_L2P_XCHG || lds_order_cached(c->device));
-    p.order_checked = p.l1p || (warm != 0 && xdepth == 0) || (p.l2p && ZZ_L2P_XCHG);
+    p.l2p = level >= 2 && !warm && xdepth == 0 && !one_parser && !l2_classic() && lds_order_cached(c->device);
+    p.order_checked = p.l1p || (warm != 0 && xdepth == 0) || p.l2p;
     return p;
 }
 // tests (zz_debug_force_lds_violation): one of the launches that were to report a violated order is this one
@@ -751,7 +727,6 @@ static bool take_forced_violation()
 //     too (zz_level1p.h P2; zz_level1.h warm_prehash; zz_level2p.h's exchange). What it wrote is a valid stream, but not necessarily the
 //     reference's: the device loses its verdict and the caller runs the call again on the one-parser kernels (ERR_RERUN), which ask the
 //     LDS for nothing of the kind (same bytes where the two-parser ones are right);
-//   value 8: a wavefront of k_encode_l2p gave up waiting for its neighbour;
 //   anything else (ZZ_ERR_SLOT_OVERFLOW): a packet did not fit its slot.
 enum { ERR_RERUN = 1 };              // (the ZZ_E_* codes are negative)
 static int read_err_word(zz_ctx* c, bool order_checked)
@@ -762,7 +737,6 @@ static int read_err_word(zz_ctx* c, bool order_checked)
         if (!order_checked) { set_err("internal: LDS-order violation reported by a kernel that does not check it"); return ZZ_E_HIP; }
         return ERR_RERUN;
     }
-    if (e & 8u) { set_err("internal: a wavefront of the level-2 kernel waited for its neighbour longer than a packet can take (zz_level2p.h, l2p_wait_ge)"); return ZZ_E_HIP; }
     if (e) { set_err("internal: packet slot overflow"); return ZZ_E_NOSPACE; }
     return ZZ_OK;
 }

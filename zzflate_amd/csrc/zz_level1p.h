@@ -4,7 +4,7 @@
 // (zzflate.cpp:101-125), bit for bit. What changes is who does what when. In k_encode_l1 ONE wavefront runs a packet's
 // whole dependency chain: probe / compare (about 200 instructions per 64 positions), then the serial walk (about 100), then
 // repair and tokens, then the next group -- and only nine such chains fit a CU (the 16 KiB table), which leaves the CU's
-// issue slots two-thirds empty (profiles/README.md, round 4: tools/ceiling_probe.sh, tools/pipe_probe.sh). Here the packet
+// issue slots two-thirds empty (profiles/README.md, round 4: tools/ceiling_probe.sh and the pipe probe of 603f283). Here the packet
 // is cut into fixed blocks of 64 positions and two wavefronts take alternate blocks:
 //
 //      wave A:  [probe 0] B0 [walk 0] B1 [repair 0, probe 2] B2 [walk 2] B3 [repair 2, probe 4] ...
@@ -35,7 +35,7 @@
 // LDS: 16,384 table + 512 ring + 512 token slots + 468 = 17,876 bytes <= 17,920: nine workgroups per CU, 27 wavefronts
 // (61 VGPRs, 62 SGPRs: the 27 fit whatever SIMDs the workgroups' wavefronts land on).
 // Measured (profiles/README.md, round 4; DESIGN.md 4 has the steps): 1 GiB text 119 -> 140 GB/s, log lines in gzip 96 -> 116,
-// the twelve-family mix 102.5 -> 116; the optimistic bound of this shape (tools/pipe_probe.sh: no cross lanes, no
+// the twelve-family mix 102.5 -> 116; the optimistic bound of this shape (ZZ_L1_PIPE_PROBE in the tree at 603f283: no cross lanes, no
 // exchange) was 159 before the kernel existed, and the first exact form ran at 124: most of the way from there to 140 was
 // taking instructions out between the barriers, one A/B at a time.
 #pragma once
@@ -70,19 +70,18 @@ namespace zz {
 // profiles/r05_ab_l1p_ext32.txt): text +0.4 %, mix -2.3 %, log lines in gzip -9 %, database dump 102 -> 81 GB/s -- at level 1 the
 // prober's interval is as critical as the walker's, and a second memory round trip in it costs more than the one it saves the
 // walk (at level 2, where the prober has slack on such data, the same idea is worth +4 % on the mix and +9 % on log lines). Off.
+// (The one settled switch still in these kernels: its `ext` placeholder is an empty asm statement, and taking that out moves
+// instructions of the -DZZ_PROF build of k_encode_l1p -- DESIGN.md 19.)
 #ifndef ZZ_L1P_EXT32
 #define ZZ_L1P_EXT32 0
 #endif
-// the emitter's completed words leave the bit ring in batches of 32..64 (zz_emit.h ring_append_lazy) instead of after every block
-#ifndef ZZ_L1P_ADLER3
-#define ZZ_L1P_ADLER3 1          // cold packets: the Adler-32 sums in three parts, one per wavefront, in front of the first barrier (0: the emitter alone, behind it)
-#endif
+// cold packets: the Adler-32 sums in three parts, one per wavefront, in front of the first barrier ...
 #ifndef ZZ_L1P_ADLER_U
 #define ZZ_L1P_ADLER_U 6        // ... with this many 16-byte loads in flight per lane
 #endif
-#ifndef ZZ_L1P_LAZY_FLUSH
-#define ZZ_L1P_LAZY_FLUSH 1
-#endif
+// Tried and set aside (DESIGN.md 19 has the list; source: the tree at 603f283): the emitter summing the Adler-32 alone behind the
+// first barrier (ZZ_L1P_ADLER3=0, profiles/r05_ab_l1p_adler_in_three_parts_*.txt); the emitter's words leaving the bit ring after
+// every block instead of in batches of 32..64 (ZZ_L1P_LAZY_FLUSH=0, profiles/r05_ab_l1p_lazy_flush.txt).
 typedef __attribute__((address_space(3))) uint16_t lds_u16;
 
 #define ZZ_L1P_NONE 64u          // win[]: no lane of the block with that hash was visited
@@ -188,11 +187,7 @@ __device__ __forceinline__ void l1p_parse(const zz_packet_params& P, const l1_pk
             // (xlo: base - 63, and for the packet's first block a value no entry can reach -- carried, one addition per block)
             const uint32_t qx = oldraw - xlo;                            // its lane there
             const bool xd = active && qx < ZZ_WAVE;
-#ifdef ZZ_L1P_X_NOCROSS
-            const uint64_t XD = 0;                                       // TIMING EXPERIMENT: no cross lanes at all (wrong streams)
-#else
             const uint64_t XD = ballot(xd);
-#endif
             // (what the lanes that are not cross lanes hold in these is never looked at: no zeroing)
             uint32_t talt;
             uint64_t wa, wa2;
@@ -365,17 +360,12 @@ __device__ __forceinline__ void l1p_parse(const zz_packet_params& P, const l1_pk
                     if (mlen >= 4) {
                         if (inf & (useB ? ZZ_WI_EXTB : ZZ_WI_EXTA)) {     // remain(), encoder.cpp:64-90
                             const int32_t cand = useB ? (int32_t)(base + ZZ_WI_QLANE(inf)) : (int32_t)(readlane(told, e) - 1u - BIAS);
-#ifdef ZZ_L1P_X_NOEXT
-                            (void)cand;                                  // TIMING EXPERIMENT (valid but WRONG streams): "16 or more" is 16, no extension loads
-                            mlen = maxlen < ZZ_WI_CAP ? maxlen : ZZ_WI_CAP;
-#else
                             // (the prober's sixteen further bytes hold for the entry as this lane read it: not for a candidate inside
                             // the block, not where the walk of the block in front moved it)
                             const uint32_t e16 = (gate && !useB && !((MV >> e) & 1)) ? readlane(ext, e) : 0xFFu;
                             if (e16 < 16u) mlen = 16u + e16;             // (an interior block: 32 bytes lie inside the packet)
                             else mlen = l1p_extend_match(SRC, pe, cand, maxlen, e16 == 16u ? 32u : ZZ_WI_CAP);
                             if (ZZ_L1P_EXT32) hot_until = g + 8u;
-#endif
                             if (lane == e) ovlen = mlen | 0x8000u;
                             ovmL |= 1ull << e;
                         }
@@ -400,11 +390,7 @@ __device__ __forceinline__ void l1p_parse(const zz_packet_params& P, const l1_pk
                     mlen = 0;
                     if ((uint32_t)xe == 0 && maxlen >= 4) {
                         if (xe != 0) mlen = (uint32_t)__builtin_ctzll(xe) >> 3;
-#ifdef ZZ_L1P_X_NOEXT
-                        else mlen = 8;
-#else
                         else mlen = l1p_extend_match(SRC, pe, (int32_t)(cand1 - 1u - BIAS), maxlen);
-#endif
                         if (mlen > maxlen) mlen = maxlen;
                     }
                     if (lane == e) { ovlen = mlen | 0x8000u; ovcand1 = cand1; }
@@ -496,7 +482,7 @@ __device__ __forceinline__ void l1p_packet_parser(const zz_packet_params& P, uin
     if (pw == 0) X->scal[lane] = 0;                                      // block 0: nothing carried in
     if (pw == 0) X->told[lane] = 0;                                      // (tag 0: no block's)
     if (pw == 1 && lane == 0) X->win[ZZ_L1P_SELF] = (uint8_t)ZZ_L1P_SELF; // the sentinel (zz_level1p.h, R)
-    if (!BIAS && ZZ_L1P_ADLER3 && P.cks_kind == ZZ_CKS_ADLER) {
+    if (!BIAS && P.cks_kind == ZZ_CKS_ADLER) {
         // a third of the packet's Adler-32 sums (the emitter takes the last third and puts them together behind the barrier): summed by
         // the emitter alone, the packet began with both parsers waiting for it -- 48 K cycles of a packet's 1.4 M (instrumented)
         uint32_t A = 0;
@@ -530,15 +516,15 @@ __device__ __forceinline__ void l1p_packet_emitter(const zz_packet_params& P, ui
     const int lane = lane_id();
     const l1_pk q = l1_packet_of(P, k);
     bitring ring;
-    // (every append of this wavefront goes the same way: the batched flush must not meet the unbatched one's "at most 64 words wait")
+    // (the emitter's completed words leave the bit ring in batches of 32..64, zz_emit.h ring_append_lazy; every append of this
+    // wavefront goes that way: the batched flush must not meet the unbatched one's "at most 64 words wait")
     auto append_uniform = [&](uint32_t bits, uint32_t nbits) {
-        if (ZZ_L1P_LAZY_FLUSH) ring_append_lazy(ring, lane == 0 ? bits : 0u, lane == 0 ? nbits : 0u);
-        else ring_append_uniform(ring, bits, nbits);
+        ring_append_lazy(ring, lane == 0 ? bits : 0u, lane == 0 ? nbits : 0u);
     };
     if (ZZ_L1P_PRIO_E) __builtin_amdgcn_s_setprio(ZZ_L1P_PRIO_E);
     ZZ_PROF_DECL                                                         // (diagnostic builds: [2..6] per packet, [0], [1] per block, tools/prof_l1p.py)
     ring_init(ring, ring_words, q.out);
-    const bool adler3 = !BIAS && ZZ_L1P_ADLER3 && P.cks_kind == ZZ_CKS_ADLER;
+    const bool adler3 = !BIAS && P.cks_kind == ZZ_CKS_ADLER;
     uint64_t At = 0, Ct = 0;
     if (adler3) {
         uint32_t A = 0;
@@ -578,14 +564,9 @@ __device__ __forceinline__ void l1p_packet_emitter(const zz_packet_params& P, ui
             ZZ_T(0);
             const uint32_t tok = *slot;
             slot = lds_flip_slot((lds_u32*)slot);
-#ifdef ZZ_L1P_X_NOEMIT
-            if (g == 0)                                                  // TIMING EXPERIMENT: the emitter only keeps the barriers (wrong streams)
-#endif
-#if ZZ_L1P_LAZY_FLUSH
-            { uint32_t bits, nb; l1_token_bits(tok, bits, nb); ring_append_lazy(ring, bits, nb); }
-#else
-            l1_emit_tokens(ring, nullptr, tok);
-#endif
+            uint32_t bits, nb;
+            l1_token_bits(tok, bits, nb);
+            ring_append_lazy(ring, bits, nb);
         }
         append_uniform(0, 7);                                 // EOB: codes_f[256] (encoder.cpp:371)
     }
@@ -599,7 +580,7 @@ __device__ __forceinline__ void l1p_packet_emitter(const zz_packet_params& P, ui
         append_uniform(1u | (1u << 1), 3);                    // empty final packet: one empty fixed block (D8)
         append_uniform(0, 7);
     }
-    const uint32_t bytes = ZZ_L1P_LAZY_FLUSH ? ring_finish_lazy(ring) : ring_finish(ring);
+    const uint32_t bytes = ring_finish_lazy(ring);
     if (lane == 0) {
         P.sizes[k] = bytes;
         if (bytes > P.slot_stride) atomicOr(P.err, ZZ_ERR_SLOT_OVERFLOW);

@@ -313,10 +313,6 @@ __device__ inline int calculate_tree_w(huff_scratch& S, const uint32_t* freqs, i
     }
     ZZ_WAVE_SYNC();
     int nt = n;
-#ifndef ZZ_L2_MAKE_HEAP_W
-#define ZZ_L2_MAKE_HEAP_W 1
-#endif
-#if ZZ_L2_MAKE_HEAP_W
     // make_heap (stl_heap.h:339-360) sifts the parents down one after the other, last parent first. A sift stays inside its parent's
     // subtree, the parents of one level of the heap have disjoint subtrees, and every deeper level's parents (higher indices) come
     // before: level by level, deepest first, a lane per parent is the same sequence of moves.
@@ -331,17 +327,8 @@ __device__ inline int calculate_tree_w(huff_scratch& S, const uint32_t* freqs, i
             ZZ_WAVE_SYNC();
         }
     }
-#endif
     if (lane == 0) {
         int nr = (int)nrec;
-#if !ZZ_L2_MAKE_HEAP_W
-        if (nr >= 2) {                         // make_heap (stl_heap.h:339-360)
-            for (int parent = (nr - 2) / 2;; --parent) {
-                hkey_adjust(hk, parent, nr, hk[parent]);
-                if (parent == 0) break;
-            }
-        }
-#endif
         while (nr >= 2) {                      // :92-104, pop_heap x2 (stl_heap.h:253-265) + push_heap
             const uint32_t a = hk[0];
             nr--;
@@ -498,9 +485,6 @@ __device__ inline int rle_lengths(const uint8_t* lengths, int n, uint16_t* recs,
 // loops (:191-216) -- v == 0: c = 138 q + r gives q records (18, 138), then (17 or 18, r) if r >= 3, else r plain zeros; v != 0: the
 // length itself, then c - 1 = 6 q + r gives q records (16, 6), then (16, r) if r >= 3, else r times the length again -- so a run
 // knows how many records it writes, a prefix sum over the runs places them, and the meta frequencies take one atomic per kind.
-#ifndef ZZ_L2_RLE_W
-#define ZZ_L2_RLE_W 1
-#endif
 template <int N>
 __device__ __forceinline__ int rle_lengths_w(const uint8_t* lengths, uint16_t* recs, int nv, uint32_t* metaF)
 {
@@ -1164,7 +1148,7 @@ __device__ __forceinline__ void l2_encode_run(const zz_l2_params Q, const MAP M)
     uint64_t* covw = (uint64_t*)(lds + HB + 560);                 // 128: covered bits of the 16 blocks around the probe front
     uint64_t* mstw = covw + ZZ_L2_WIN;                            // 128: match-start bits
     uint32_t* histP = (uint32_t*)(lds + HB + 560 + 2 * ZZ_L2_WIN * 8);        // 640: packed 16-bit counters
-    __shared__ uint32_t xb[8];                                    // PP: backRefEnd, the next probe position and the hand-over counters (l2p_sync)
+    __shared__ uint32_t xb[8];                                    // PP: [0] backRefEnd, [1] the next probe position (l2p_token_pass); the rest is unused
     // Huffman scratch inside the (dead) hash table
     huff_scratch S = l2_huff_scratch(lds);
     uint8_t* lens = (uint8_t*)(lds + ZZ_L2_LDS_LENS);
@@ -1199,12 +1183,10 @@ __device__ __forceinline__ void l2_encode_run(const zz_l2_params Q, const MAP M)
         decltype(auto) P = zz_packet_view(Q.pk, M, g, k);    // (this packet's view of its shard; the single stream's is Q.pk itself)
         constexpr int ROLE = decltype(roletag)::value;       // 0: parser (+ codes, first part of the emission), 1: helper, 2 (PP): second parser
         constexpr bool W0 = ROLE == 0, PB = ROLE == 2;
-        // Behind the token pass: CODER builds the codes and emits the first part of the body, MID the second (PP: PB the third).
-        // Two wavefronts: the parser codes. PP: the HELPER codes and wavefront 0 takes the middle part -- a parser's token pass
-        // wants every register it can get, and with the code construction in the same wavefront the compiler kept 31 packet-invariant
-        // values in scratch and read eight of them back on every out-of-line token of the walk (parser 0's walk 2,541 cycles per
-        // block of the mix against parser 1's 1,793: profiles/r05_phases_l2p_mix_first.txt); the helper's token-pass loop is small.
-        constexpr bool CODER = (PP && ZZ_L2P_HELPER_CODES) ? ROLE == 1 : W0, MID = (PP && ZZ_L2P_HELPER_CODES) ? W0 : ROLE == 1;
+        // Behind the token pass wavefront 0 builds the codes and emits the first part of the body, the helper the second (PP: PB the
+        // third). (Tried and set aside, DESIGN.md 19: PP with the HELPER coding and wavefront 0 taking the middle part, so that the
+        // parser's token pass keeps its registers -- parser 0's walk on the mix 2,541 -> 1,261 cycles per block, level 2 text 1.1 %
+        // slower: profiles/r05_phases_l2p_mix_first.txt.)
         const uint64_t off = (uint64_t)k * P.packet_size;
         const uint32_t len = (uint32_t)((P.n - off) < P.packet_size ? (P.n - off) : P.packet_size);
         const bool is_final = P.last_is_final && k == P.npk - 1;
@@ -1223,12 +1205,6 @@ __device__ __forceinline__ void l2_encode_run(const zz_l2_params Q, const MAP M)
             for (int i = lane; i < 2 * ZZ_L2_WIN * 2 + ZZ_L2_HIST_WORDS; i += ZZ_WAVE) zw[i] = 0;   // window + counters
         }
         ZZ_WAVE_SYNC();
-        if (PP && ZZ_L2P_FLAGS) {
-            // the counters the wavefronts meet through during the token pass: cleared here, and one more barrier in front of their first
-            // use (which also says "the table is clear" to the second parser and "window and counters are" to both)
-            if (PB) { if (lane < 8) xb[lane] = lane < 2 ? 1u : 0u; }        // backRefEnd = 1 (:380), j = 1 (:383), nothing walked / entered / handed over
-            __syncthreads();
-        }
         ZZ_T(0);
 
         if (n > 0) {
@@ -1243,10 +1219,10 @@ __device__ __forceinline__ void l2_encode_run(const zz_l2_params Q, const MAP M)
                 // two parsers: B0 also says "the table is clear" to the second one, "window and counters are" to both
                 if (W0) {
                     if (ZZ_L2P_PRIO_P != 3) __builtin_amdgcn_s_setprio(ZZ_L2P_PRIO_P);
-                    l2p_token_pass(T, hb, xb, covw, mstw, histP, src, end, l1p_make_src(P, src, end), n, before, 0u, P.err, P.dbg_viol, P.prof);
+                    l2p_token_pass(T, hb, xb, covw, mstw, src, end, l1p_make_src(P, src, end), n, before, 0u, P.err, P.dbg_viol, P.prof);
                     if (ZZ_L2P_PRIO_P != 3) __builtin_amdgcn_s_setprio(3);
                 }
-                if (PB) l2p_token_pass(T, hb, xb, covw, mstw, histP, src, end, l1p_make_src(P, src, end), n, before, 1u, P.err, P.dbg_viol, P.prof);
+                if (PB) l2p_token_pass(T, hb, xb, covw, mstw, src, end, l1p_make_src(P, src, end), n, before, 1u, P.err, P.dbg_viol, P.prof);
             } else if (W0) {
                 if (BIAS) {
                     // warm window: every position of the last P.warm bytes in front of the packet under the hash of its
@@ -1262,7 +1238,7 @@ __device__ __forceinline__ void l2_encode_run(const zz_l2_params Q, const MAP M)
             if (!W0 && !PB) {
                 uint32_t nb = 0, adA = 0;
                 uint64_t adC = 0;
-                const uint32_t nt = PP ? l2p_helper_pass(hb, covw, mstw, histP, tokens, recs, src, n, nb, adA, adC, xb, P.err, snap, P.prof)
+                const uint32_t nt = PP ? l2p_helper_pass(hb, covw, mstw, histP, tokens, recs, src, n, nb, adA, adC, snap, P.prof)
                                        : l2_helper_pass(hb, covw, mstw, histP, tokens, recs, src, n, nb, adA, adC, XD ? l6_trips(n) : l2_probe_blocks(n));
                 if (lane == 0) { covw[0] = ((uint64_t)nt << 32) | nb; }       // the window is dead now
                 if (P.cks_kind == ZZ_CKS_ADLER) {
@@ -1287,7 +1263,7 @@ __device__ __forceinline__ void l2_encode_run(const zz_l2_params Q, const MAP M)
             // the end of the block and the end of the packet. A part's place in the bit stream follows from a dry run over the records
             // in front of it; the words two parts share are put together here at the end.
             if (n > 0) {
-                if (ZZ_L2P_DIST_ON_PB && !ZZ_L2P_HELPER_CODES) {
+                {
                     // the distance code's lengths (30 symbols) beside wavefront 0's literal / length code (286): the heap replay is one lane's
                     // chain of LDS round trips either way, and this wavefront has nothing else to do until the codes are there
                     __syncthreads();         // (D1) the counts are unpacked
@@ -1336,9 +1312,9 @@ __device__ __forceinline__ void l2_encode_run(const zz_l2_params Q, const MAP M)
             zz_cks c = wave_adler(src, len);
             if (lane == 0) P.cks[k] = c;
         }
-        if (MID) {
+        if (ROLE == 1) {
             if (n > 0) {
-                if (PP && ZZ_L2P_DIST_ON_PB && !ZZ_L2P_HELPER_CODES) { __syncthreads(); __syncthreads(); }      // (D1), (D2)
+                if (PP) { __syncthreads(); __syncthreads(); }      // (D1), (D2)
                 __syncthreads();             // (X) codes are ready, or the block went out stored
                 if (uniform(share[0]) == 2) {
                     // ... then the second part of the records, the end of the block and the end of the packet. Its
@@ -1387,7 +1363,6 @@ __device__ __forceinline__ void l2_encode_run(const zz_l2_params Q, const MAP M)
             return;
         }
         // ---- the coding wavefront alone from here to the end of the packet ---------------------------------------------
-        if (PP && ZZ_L2P_HELPER_CODES) __builtin_amdgcn_s_setprio(3);      // (the helper's token-pass priority is its own: l2p_helper_pass sets it per packet)
         bitring ring;
         ring_init(ring, ring_words, out);
         if (n > 0) {
@@ -1406,8 +1381,7 @@ __device__ __forceinline__ void l2_encode_run(const zz_l2_params Q, const MAP M)
 
             ZZ_T(2);
             // ================= code construction =================================================================
-            constexpr bool DIST_PB = PP && ZZ_L2P_DIST_ON_PB && !ZZ_L2P_HELPER_CODES;     // the second parser builds the distance code's lengths meanwhile
-            if (DIST_PB) __syncthreads();                                         // (D1) the counts are unpacked
+            if (PP) __syncthreads();                                             // (D1) the counts are unpacked: the second parser builds the distance code's lengths meanwhile
             if (lane == 0) symF[256] += 1;                                       // :470
             ZZ_WAVE_SYNC();
             if (XD) pm_lengths_w(PM, symF, 286, 15, lens); else calc_lengths_w(S, symF, 286, 15, lens);   // ComputeCodes, :171-176
@@ -1417,27 +1391,19 @@ __device__ __forceinline__ void l2_encode_run(const zz_l2_params Q, const MAP M)
                 const uint32_t eb = i < 265 || i == 285 ? 0 : (uint32_t)(i - 261) >> 2;
                 bitsum += symF[i] * (lens[i] + eb);
             }
-            if (DIST_PB) __syncthreads();                                         // (D2) the distance lengths are in place
+            if (PP) __syncthreads();                                             // (D2) the distance lengths are in place
             else if (XD) pm_lengths_w(PM, distF, 30, 15, lens + 288); else calc_lengths_w(S, distF, 30, 15, lens + 288);
             if (lane < 30) {
                 const uint32_t eb = lane < 4 ? 0 : (uint32_t)(lane - 2) >> 1;
                 bitsum += distF[lane] * (lens[288 + lane] + eb);
             }
             ZZ_T(7);
-#if ZZ_L2_RLE_W
             {
                 ZZ_WAVE_SYNC();
                 const int nr = rle_lengths_w<286>(lens, rle, 0, metaF);
                 const int nr2 = rle_lengths_w<30>(lens + 288, rle, nr, metaF);
                 if (lane == 0) { misc[1] = (uint32_t)nr; misc[2] = (uint32_t)nr2; }
             }
-#else
-            if (lane == 0) {
-                int nr = rle_lengths(lens, 286, rle, 0, metaF);
-                misc[1] = (uint32_t)nr;
-                misc[2] = (uint32_t)rle_lengths(lens + 288, 30, rle, nr, metaF);
-            }
-#endif
             ZZ_WAVE_SYNC();
             ZZ_T(8);
             if (XD) pm_lengths_w(PM, metaF, 19, 7, metaLens); else calc_lengths_w(S, metaF, 19, 7, metaLens);   // :263-265
@@ -1573,7 +1539,7 @@ __device__ __forceinline__ void l2_encode_run(const zz_l2_params Q, const MAP M)
         for (uint32_t k = Q.k0 + blockIdx.x; k < Q.k1; k = next_packet()) packet(k, std::integral_constant<int, 2>());
     }
 #ifdef ZZ_PROF
-    if (threadIdx.x == ((PP && ZZ_L2P_HELPER_CODES) ? 64u : 0u) && P.prof) for (int _i = 0; _i < 16; ++_i) atomicAdd(&P.prof[_i], prof_acc[_i]);     // the coding wavefront's stamps
+    if (threadIdx.x == 0u && P.prof) for (int _i = 0; _i < 16; ++_i) atomicAdd(&P.prof[_i], prof_acc[_i]);     // the coding wavefront's stamps
 #endif
 }
 template <uint32_t BIAS, bool XD = false, bool PP = false>

@@ -91,40 +91,17 @@ __device__ __forceinline__ void lds_gather16(zz_lds_bytes base, uint32_t off, ui
 
 // the same in two steps, for a candidate: most differ from the position within their first eight bytes, and the third read
 // and half of the shifting are only for those that do not. Returns the number of equal leading bytes, 16 = all.
-// ZZ_L6_WORDS4 = 1 (default): the candidate's words are read at FOUR-byte alignment (ds_read2_b32 + ds_read_b32, then ds_read2_b32), so
-// the five selects between the halves of 8-byte words go: the compare step is bound by the vector ALUs' issue rate (about 22 of
-// their instructions per candidate; reading LESS from the LDS -- a four-byte filter in front, no reads behind a full sixteen -- was
-// slower, fewer instructions is faster: profiles/r05_ab_l6_*.txt). 0 = round 3's form, two or three aligned 8-byte reads.
-#ifndef ZZ_L6_WORDS4
-#define ZZ_L6_WORDS4 1
-#endif
-// ZZ_L6_WORDS4 = 2: ONE byte-addressed ds_read_b64 per eight bytes and no funnel shifts (three vector instructions fewer per candidate):
-// bit-exact and 22 % SLOWER at level 6 (43.0 -> 33.5 GB/s): the LDS serves a misaligned 8-byte read at a fraction of an aligned one's rate
-// (profiles/r05_ab_l6_unaligned_reads_and_packed_key.txt). ZZ_L6_KEY = 1 (default): the chain's best as ONE max over
-// length << 16 | 32767 - distance instead of compare + max + select: + 0.4 %.
-#ifndef ZZ_L6_KEY
-#define ZZ_L6_KEY 1
-#endif
+// The candidate's words are read at FOUR-byte alignment (ds_read2_b32 + ds_read_b32, then ds_read2_b32), so the five selects between
+// the halves of 8-byte words go: the compare step is bound by the vector ALUs' issue rate (about 22 of their instructions per
+// candidate; reading LESS from the LDS -- a four-byte filter in front, no reads behind a full sixteen -- was slower, fewer
+// instructions is faster: profiles/r05_ab_l6_*.txt).
+// Tried and set aside (source: the tree at 603f283): round 3's two or three aligned 8-byte reads (ZZ_L6_WORDS4=0,
+// profiles/r05_ab_l6_words_at_four_byte_alignment.txt); ONE byte-addressed ds_read_b64 per eight bytes and no funnel shifts
+// (ZZ_L6_WORDS4=2): bit-exact and 22 % SLOWER at level 6 (43.0 -> 33.5 GB/s), the LDS serves a misaligned 8-byte read at a fraction of
+// an aligned one's rate (profiles/r05_ab_l6_unaligned_reads_and_packed_key.txt); the chain's best by compare + max + select instead
+// of one max over a packed key (ZZ_L6_KEY=0: -0.4 %).
 __device__ __forceinline__ uint32_t lds_match16(zz_lds_bytes base, uint32_t off, uint64_t w, uint64_t w2)
 {
-#if ZZ_L6_WORDS4 == 2
-    // the candidate's bytes by ONE byte-addressed 8-byte LDS read (the LDS serves unaligned reads: the compiler emits ds_read_b64 for an
-    // align-1 access on gfx950), no funnel shifts, no address arithmetic
-    typedef uint64_t __attribute__((aligned(1))) u64u;
-    typedef __attribute__((address_space(3))) const u64u* p8u;
-    const uint64_t x = *(p8u)(base + off);
-    const uint32_t d0 = (uint32_t)x ^ (uint32_t)w, d1 = (uint32_t)(x >> 32) ^ (uint32_t)(w >> 32);
-    const uint32_t f0 = ffbl_or_ones(d0), f1 = add_sat_k<32>(ffbl_or_ones(d1));
-    uint32_t bits = f0 < f1 ? f0 : f1;                                   // >= 64: the first eight bytes are equal
-    if (bits >= 64u) {
-        const uint64_t y = *(p8u)(base + off + 8u);
-        const uint32_t d2 = (uint32_t)y ^ (uint32_t)w2, d3 = (uint32_t)(y >> 32) ^ (uint32_t)(w2 >> 32);
-        const uint32_t f2 = ffbl_or_ones(d2), f3 = add_sat_k<32>(ffbl_or_ones(d3));
-        const uint32_t t = f2 < f3 ? f2 : f3;
-        bits = 64u + (t < 64u ? t : 64u);
-    }
-    return bits >> 3;
-#elif ZZ_L6_WORDS4
     typedef __attribute__((address_space(3))) const uint32_t* p4;
     const p4 p = (p4)(base + (off & ~3u));
     const uint32_t sh = (off & 3u) << 3;
@@ -140,27 +117,6 @@ __device__ __forceinline__ uint32_t lds_match16(zz_lds_bytes base, uint32_t off,
         bits = 64u + (t < 64u ? t : 64u);
     }
     return bits >> 3;
-#else
-    typedef __attribute__((address_space(3))) const uint64_t* p8;
-    const uint32_t a = off & ~7u, sh = (off & 3u) << 3;
-    const bool up = (off & 4u) != 0;
-    const uint64_t x0 = *(p8)(base + a), x1 = *(p8)(base + a + 8);
-    const uint32_t x0l = (uint32_t)x0, x0h = (uint32_t)(x0 >> 32), x1l = (uint32_t)x1, x1h = (uint32_t)(x1 >> 32);
-    const uint32_t e0 = up ? x0h : x0l, e1 = up ? x1l : x0h, e2 = up ? x1h : x1l;
-    const uint32_t d0 = __builtin_amdgcn_alignbit(e1, e0, sh) ^ (uint32_t)w, d1 = __builtin_amdgcn_alignbit(e2, e1, sh) ^ (uint32_t)(w >> 32);
-    const uint32_t f0 = ffbl_or_ones(d0), f1 = add_sat_k<32>(ffbl_or_ones(d1));
-    uint32_t bits = f0 < f1 ? f0 : f1;                                   // >= 64: the first eight bytes are equal
-    if (bits >= 64u) {
-        const uint64_t x2 = *(p8)(base + a + 16);
-        const uint32_t x2l = (uint32_t)x2, x2h = (uint32_t)(x2 >> 32);
-        const uint32_t e3 = up ? x2l : x1h, e4 = up ? x2h : x2l;
-        const uint32_t d2 = __builtin_amdgcn_alignbit(e3, e2, sh) ^ (uint32_t)w2, d3 = __builtin_amdgcn_alignbit(e4, e3, sh) ^ (uint32_t)(w2 >> 32);
-        const uint32_t f2 = ffbl_or_ones(d2), f3 = add_sat_k<32>(ffbl_or_ones(d3));
-        const uint32_t t = f2 < f3 ? f2 : f3;
-        bits = 64u + (t < 64u ? t : 64u);
-    }
-    return bits >> 3;
-#endif
 }
 
 // MAP: zz_no_batch (one shard: the packets of Q.pk) or zz_batch_map (k_l6_matches_batch: Q.k0 .. Q.k1 number the batch's packets; every
@@ -372,32 +328,20 @@ __device__ __forceinline__ void l6_matches_run(const zz_l6m_params Q, const MAP 
                     const uint16_t* c = cur.c;
                     uint64_t w, w2;
                     lds_gather16(L, ZZ_L6_BIAS + qa, w, w2);                        // q + 16 <= n: inside the data
-                    uint32_t best = 0, bdist = 0;
-#if ZZ_L6_KEY
                     // longest wins, the nearest among equals: one max over length << 16 | 32767 - distance (distances grow along the chain)
                     uint32_t key = 0;
                     const uint32_t K = 32767u - (ZZ_L6_BIAS + q);
 #pragma unroll
                     for (int i = 0; i < DEPTH; ++i) {                               // i = 0: the nearest
                         const uint32_t co = c[DEPTH - 1 - i];                      // the candidate's offset in the image
-                        const uint32_t e = co + K;                                  // 32767 - d; d < 32768 as below
+                        const uint32_t e = co + K;                                  // 32767 - d for the distance d; a candidate: 0 < d < 32768 (d != 0: the entries in front of q's place are other positions)
                         if (act && e < 32768u) {
                             const uint32_t k = (lds_match16(L, co, w, w2) << 16) | e;
                             key = k > key ? k : key;
                         }
                     }
-                    best = key >> 16; bdist = 32767u - (key & 0xFFFFu);
-#else
-#pragma unroll
-                    for (int i = 0; i < DEPTH; ++i) {                               // i = 0: the nearest
-                        const uint32_t co = c[DEPTH - 1 - i];                      // the candidate's offset in the image
-                        const uint32_t d = (ZZ_L6_BIAS + q) - co;                   // 0 < d < 32768: a candidate (d != 0: the entries
-                        if (act && d < 32768u) {                                    // in front of q's place are other positions)
-                            const uint32_t ln = lds_match16(L, co, w, w2);
-                            if (ln > best) { best = ln; bdist = d; }
-                        }
-                    }
-#endif
+                    uint32_t best = key >> 16;
+                    const uint32_t bdist = 32767u - (key & 0xFFFFu);
                     if (best < 4) best = 0;
                     // lazy: the next position's length (lane 63 never defers)
                     const uint32_t nxt = (uint32_t)__shfl_down((int)best, 1);
