@@ -350,6 +350,39 @@ int zz_points_index_host(const uint8_t* src, uint64_t src_len, int format, uint6
 int zz_decode_points_device(zz_ctx* ctx, const void* d_src, uint64_t src_len, void* d_dst, uint64_t cap, uint64_t* out_len,
                             int format, const uint64_t* points, uint64_t entries, void* hip_stream);
 
+/* The point index built ON THE DEVICE, for a stream met for the first time: block starts are found in the compressed bytes in
+ * parallel instead of being reached one after the other. D = the bytes behind the container header; it is cut into chunks of
+ * chunk_bytes. In every chunk but the first, a kernel looks for the lowest bit at which a NON-FINAL DYNAMIC block header stands
+ * that passes every check the decoder makes on one (the candidates; chunk 0's is bit 0). The stretch from every candidate to the
+ * next is then measured in one launch -- decoded and counted, no byte written -- and the stretches are chained from bit 0: only
+ * candidates reached over block boundaries from bit 0 become rows; a candidate the chain does not meet is dropped and the gap it
+ * leaves is measured in a further round. So the rows are: (0, 0); (p, decoded bytes in front of p) for every candidate p on the
+ * stream's true chain of blocks; (the bit behind the final block, the decoded length) -- thinned by zz_points_index_host's rule
+ * when spacing > 1 (an inner row is kept only if it is the first at or behind a multiple of `spacing` decoded bytes). The result
+ * depends on the stream, chunk_bytes and spacing only. Stored, fixed and final blocks are not searched for: a stream made of those
+ * gets few rows or none between the first and the last, and decodes as slowly as with any sparse index.
+ *
+ * `points` is HOST memory, exactly what zz_decode_points_device takes; zz_points_index_bound(src_len, chunk_bytes) rows always
+ * suffice (chunks + 1; 0 for chunk_bytes < 16). *entries and *out_len are set also when max_entries is too small (ZZ_E_NOSPACE,
+ * nothing written to points), as zz_points_index_host has it.
+ *
+ * What is checked: the container header as zz_decode_device reads it (ZZ_E_UNSUPPORTED for a preset dictionary); the block
+ * structure along the true chain; that exactly the trailer's length lies behind the final block; for gzip, ISIZE against the
+ * decoded length: ZZ_E_DATA. What is NOT checked: the checksum and the match distances -- no byte is produced. ZZ_OK here is NOT
+ * a verdict on the stream: zz_decode_points_device gives that, and refuses a stream that this call indexed although its checksum
+ * is wrong or a distance reaches too far back.
+ *
+ * ZZ_E_ARG before anything is launched: a null context, source, entries or out_len; chunk_bytes < 16 or spacing < 1; a format
+ * outside 0..2; an unfinished zz_encode_device_async. Workspace: 32 bytes per chunk and nothing per output byte. The context's
+ * "last decode" state is not touched. Synchronous; the host reads the chunks' records once and each round's records once. */
+#define ZZ_POINTS_CHUNK_DEFAULT 16384ull   /* compressed bytes per searched chunk; derived (32 KiB of decoded text at ratio ~0.4, the spacing DESIGN.md 17 measured best), not tuned */
+uint64_t zz_points_index_bound(uint64_t src_len, uint64_t chunk_bytes);
+int zz_points_index_device(zz_ctx* ctx, const void* d_src, uint64_t src_len, int format, uint64_t chunk_bytes, uint64_t spacing,
+                           uint64_t* points, uint64_t max_entries, uint64_t* entries, uint64_t* out_len, void* hip_stream);
+/* what the last zz_points_index_device did: the candidates (bit 0 included), those of them that were dropped, and the rounds
+ * (launches of the measuring kernel; a stream whose candidates all lie on its chain needs one) */
+int zz_ctx_last_points_index_stats(const zz_ctx* ctx, uint64_t* candidates, uint64_t* dropped, uint32_t* rounds);
+
 /* Many independent streams back to their bytes, one call: the mirror image of zz_encode_batch_device. Item i =
  * d_srcs[i][0, d_src_lens[i]) -- one complete zlib / gzip / raw stream: any single-member RFC 1950 / 1951 / 1952 stream,
  * packet-mode or not, any level, written by this library or another -- is decoded into d_dsts[i][0, d_caps[i]);

@@ -18,10 +18,12 @@ __all__ = [
     "Format", "Config", "ZzFlateError", "ZzFlateEncode", "ZzFlateEncodeToCallback", "adler32x", "combine",
     "crc32", "crc32_combine", "bound", "Context", "lib", "DEFAULT_PACKET", "generate_host", "header", "trailer",
     "MEMBERS_BLOCK", "members_bound", "members_header", "gzi_bytes", "packet_checksums_host",
+    "POINTS_CHUNK", "points_index_bound",
 ]
 
 DEFAULT_PACKET = 32768
 POINTS_SPACING = 131072          # decoded bytes between two points of a point index (ZZ_POINTS_SPACING_DEFAULT)
+POINTS_CHUNK = 16384             # compressed bytes per searched chunk of Context.points_index (ZZ_POINTS_CHUNK_DEFAULT)
 MEMBERS_BLOCK = 65280            # input bytes per member of a blocked gzip file (bgzip's)
 MEMBERS_NO_EOF = 1
 MEMBERS_EXTENDED = 2                 # zz_encode_members_device's flags: levels 4..6 through the call's own switch
@@ -100,6 +102,9 @@ def _load():
         "zz_decode_device": (i32, [vp, vp, u64, vp, u64, pu64, i32, u32, vp, u64, vp]),
         "zz_points_index_host": (i32, [vp, u64, i32, u64, vp, u64, pu64, pu64]),
         "zz_decode_points_device": (i32, [vp, vp, u64, vp, u64, pu64, i32, vp, u64, vp]),
+        "zz_points_index_bound": (u64, [u64, u64]),
+        "zz_points_index_device": (i32, [vp, vp, u64, i32, u64, u64, vp, u64, pu64, pu64, vp]),
+        "zz_ctx_last_points_index_stats": (i32, [vp, pu64, pu64, ctypes.POINTER(u32)]),
         "zz_decode_batch_device": (i32, [vp, u64, vp, vp, vp, vp, vp, vp, i32, vp]),
         "zz_decode_range_device": (i32, [vp, vp, u64, i32, u32, vp, u64, u64, u64, vp, u64, pu64, vp]),
         "zz_ctx_last_decode_range_stats": (i32, [vp, pu64, pu64, ctypes.POINTER(u32), pu64]),
@@ -270,6 +275,11 @@ def points_index_host(data, format=Format.Zlib, spacing=POINTS_SPACING):
     _check(lib.zz_points_index_host(data, len(data), int(format), spacing, points.data_ptr(), entries.value, ctypes.byref(entries),
                                     ctypes.byref(n)))
     return points, n.value
+
+
+def points_index_bound(src_len, chunk_bytes=POINTS_CHUNK):
+    """Rows that always suffice for ``Context.points_index`` of a stream of ``src_len`` bytes: its chunks plus one."""
+    return lib.zz_points_index_bound(src_len, chunk_bytes)
 
 
 POINTS_WINDOW = 32768                                   # ZZ_POINTS_WINDOW: bytes of a window slot
@@ -695,6 +705,33 @@ class Context:
         _check(lib.zz_decode_points_device(self._h, self._ptr(src), src_len, self._ptr(dst), cap, ctypes.byref(out), int(format),
                                            points.data_ptr(), points.shape[0], st))
         return out.value
+
+    def points_index(self, src, src_len, format=Format.Zlib, chunk_bytes=POINTS_CHUNK, spacing=1, stream=None):
+        """The point index of the zlib / gzip / raw stream ``src[:src_len]`` (device memory), built on the device: non-final
+        dynamic block headers are searched for in every chunk of ``chunk_bytes`` compressed bytes, the stretches between them
+        are measured without writing a byte, and those reached from the stream's first bit become rows. Returns ``(points,
+        decoded_length)`` with ``points`` an ``(entries, 2)`` int64 CPU tensor, exactly what ``decode_points`` takes. The
+        checksum is NOT checked here (no byte is produced): ``decode_points`` gives the verdict on the stream."""
+        import torch
+        st = self._stream() if stream is None else stream
+        bound = points_index_bound(src_len, chunk_bytes)
+        points = torch.zeros((max(bound, 2), 2), dtype=torch.int64)
+        entries, n = ctypes.c_uint64(0), ctypes.c_uint64(0)
+        _check(lib.zz_points_index_device(self._h, self._ptr(src), src_len, int(format), chunk_bytes, spacing, points.data_ptr(),
+                                          points.shape[0], ctypes.byref(entries), ctypes.byref(n), st))
+        return points[: entries.value].clone(), n.value
+
+    def last_points_index_stats(self):
+        """(candidates, dropped candidates, rounds) of the last ``points_index``."""
+        cand, dropped, rounds = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint32(0)
+        _check(lib.zz_ctx_last_points_index_stats(self._h, ctypes.byref(cand), ctypes.byref(dropped), ctypes.byref(rounds)))
+        return cand.value, dropped.value, rounds.value
+
+    def decode_found(self, src, src_len, dst, cap, format=Format.Zlib, chunk_bytes=POINTS_CHUNK, stream=None):
+        """``decode`` for a stream met for the first time: ``points_index`` on the device, then ``decode_points`` with it.
+        Results and path reporting are ``decode_points``'s."""
+        points, _ = self.points_index(src, src_len, format, chunk_bytes, 1, stream)
+        return self.decode_points(src, src_len, dst, cap, points, format, stream)
 
     def decode_range(self, src, src_len, dst, cap, first, nbytes, format=Format.Zlib, packet_size=DEFAULT_PACKET, index=None,
                      stream=None):

@@ -33,6 +33,7 @@
 #include "zz_inflate_ranges.h"
 #include "zz_inflate_check.h"
 #include "zz_inflate_points.h"
+#include "zz_inflate_points_find.h"
 #include "zz_inflate_members.h"
 #include "zz_inflate_members_ranges.h"
 #include "zz_inflate_points_ranges.h"
@@ -176,6 +177,12 @@ struct zz_ctx {
         std::vector<uint64_t> last_index;                     // the index discovery recovered (zz_ctx_last_decode_index_device)
         // zz_decode_points_device (zz_inflate_points.h): a batch's rows, its segments' results, the dealing counter
         struct { zz_buf<uint64_t> rows; zz_buf<zz_pt_stat> stat; zz_buf<unsigned int> next; } pts;
+        // zz_points_index_device (zz_inflate_points_find.h): one record per chunk (the candidates, then a round's jobs and their
+        // results in place), the dealing counter, and what the last call did
+        struct {
+            zz_buf<zi_find_job> job; zz_buf<unsigned int> next;
+            uint64_t candidates = 0, dropped = 0; uint32_t rounds = 0;
+        } pf;
         // zz_decode_members_device: per stretch of the mark pass (count, base), per candidate (offset, length; then the member
         // list), per member k_inflate_items' descriptors, what the host reads, the serial path's result
         struct {
@@ -1479,6 +1486,105 @@ extern "C" int zz_decode_points_device(zz_ctx* c, const void* d_src_v, uint64_t 
     }
     // the index, a segment or the checksum was refused: the serial path decides the result, as if no index had been given
     return zz_decode_device(c, d_src_v, src_len, d_dst_v, cap, out_len, format, 0, nullptr, 0, hip_stream);
+}
+
+// ---- the point index built on the device (zz_inflate_points_find.h; the rules in zz_inflate_core.h) -----------------------------
+extern "C" uint64_t zz_points_index_bound(uint64_t src_len, uint64_t chunk_bytes)
+{
+    return chunk_bytes < 16 ? 0 : zi_find_chunks(src_len, chunk_bytes) + 1;
+}
+
+// one round's jobs: up, one launch, the results back in place (want[0, n))
+static int pf_run_jobs(zz_ctx* c, const uint8_t* d, uint64_t n, zi_find_job* want, uint64_t njobs, hipStream_t st)
+{
+    auto& F = c->dec.pf;
+    HIPCHK(hipMemcpyAsync(F.job, want, njobs * sizeof(zi_find_job), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemsetAsync(F.next, 0, sizeof(unsigned int), st));
+    zz_pf_params Q = {};
+    Q.d = d; Q.n = n; Q.job = F.job; Q.njobs = (uint32_t)njobs; Q.next = F.next;
+    const uint64_t resident = 256ull * ZZ_PF_WG_PER_CU;
+    hipLaunchKernelGGL(k_points_reach, dim3((uint32_t)(njobs < resident ? njobs : resident)), dim3(ZZ_INF_THREADS), 0, st, Q);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(want, F.job, njobs * sizeof(zi_find_job), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return ZZ_OK;
+}
+
+extern "C" int zz_points_index_device(zz_ctx* c, const void* d_src_v, uint64_t src_len, int format, uint64_t chunk_bytes, uint64_t spacing,
+                                      uint64_t* points, uint64_t max_entries, uint64_t* entries, uint64_t* out_len, void* hip_stream)
+{
+    if (!c || !d_src_v || !entries || !out_len) { set_err("null argument"); return ZZ_E_ARG; }
+    *entries = 0; *out_len = 0;
+    if (chunk_bytes < 16) { set_err("chunk_bytes must be at least 16"); return ZZ_E_ARG; }
+    if (spacing == 0) { set_err("spacing must be at least 1"); return ZZ_E_ARG; }
+    if (!dec_format_ok(format)) return ZZ_E_ARG;
+    if (call_pending(c)) return ZZ_E_ARG;
+    const uint8_t* d_src = (const uint8_t*)d_src_v;
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t st = (hipStream_t)hip_stream;
+    auto& F = c->dec.pf;
+    F.candidates = 0; F.dropped = 0; F.rounds = 0;
+    int64_t hl = 0;
+    if (int rc = dec_container(d_src, src_len, format, st, &hl)) return rc;
+    const uint8_t* d = d_src + hl;                                          // D: the DEFLATE bytes and the trailer
+    const uint64_t n = src_len - (uint64_t)hl;
+    const uint64_t chunks = zi_find_chunks(n, chunk_bytes);
+    if (n > (~0ull >> 3) || chunks > 0x7fffffffull) { set_err("at most 2^31 - 1 chunks"); return ZZ_E_ARG; }
+    if (int rc = F.job.grow(chunks + 2)) return rc;
+    if (int rc = F.next.grow(1)) return rc;
+    const uint64_t resident = 256ull * ZZ_PF_WG_PER_CU;
+    // the candidates
+    std::vector<zi_find_job> rec(chunks + 2);
+    std::vector<uint64_t> cand{ 0 };
+    if (chunks > 1) {
+        HIPCHK(hipMemsetAsync(F.next, 0, sizeof(unsigned int), st));
+        zz_pf_params Q = {};
+        Q.d = d; Q.n = n; Q.chunk = chunk_bytes; Q.chunks = chunks; Q.job = F.job; Q.next = F.next;
+        hipLaunchKernelGGL(k_points_find, dim3((uint32_t)(chunks - 1 < resident ? chunks - 1 : resident)), dim3(ZZ_INF_THREADS), 0, st, Q);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(rec.data(), F.job, chunks * sizeof(zi_find_job), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        for (uint64_t k = 1; k < chunks; ++k) if (rec[k].a != ZI_FIND_NONE) cand.push_back(rec[k].a);
+    }
+    // the jobs, the chain and its repair rounds
+    const uint64_t nc = cand.size();
+    std::vector<zi_find_job> rc_(nc), rr_(nc + 1);
+    std::vector<uint64_t> acc(2 * (2 * nc + 2));
+    memset(rc_.data(), 0, nc * sizeof(zi_find_job)); memset(rr_.data(), 0, (nc + 1) * sizeof(zi_find_job));
+    zi_find_walk W{ zi_view<const uint64_t>{ cand.data(), nc }, nc, zi_view<zi_find_job>{ rc_.data(), nc }, zi_view<zi_find_job>{ rr_.data(), nc + 1 },
+                    zi_view<uint64_t>{ acc.data(), acc.size() }, 0, 0, 0, 0, 0, 0, chunk_bytes };
+    uint64_t nwant = nc;
+    for (uint64_t k = 0; k < nc; ++k) rec[k] = zi_find_first_job(W.cand, nc, k, W.slack, n);
+    int verdict;
+    for (;;) {
+        ++F.rounds;
+        if (int rc = pf_run_jobs(c, d, n, rec.data(), nwant, st)) return rc;
+        for (uint64_t j = 0; j < nwant; ++j) zi_find_store(W, rec[j]);
+        verdict = zi_find_link(W, zi_view<zi_find_job>{ rec.data(), rec.size() }, &nwant);
+        if (verdict != ZI_FW_MORE) break;
+        if (F.rounds > 3 * nc + 2) { set_err("the chain of block starts did not close"); return ZZ_E_DATA; }   // (every round confirms a job)
+    }
+    F.candidates = nc; F.dropped = nc - W.kept;
+    if (verdict == ZI_FW_DATA) { set_err("not a valid stream of the requested format"); return ZZ_E_DATA; }
+    uint8_t t[8] = { 0 };
+    const uint64_t tn = n < 8 ? n : 8;
+    if (tn) HIPCHK(hipMemcpyAsync(t + 8 - tn, d + n - tn, tn, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (!zi_find_trailer_ok(format, n, W.end_bit, W.bytes, t)) { set_err("not a valid stream of the requested format: trailer"); return ZZ_E_DATA; }
+    *entries = zi_find_rows(W, spacing, nullptr, 0);
+    *out_len = W.bytes;
+    if (!points || max_entries < *entries) { set_err("point index buffer too small"); return ZZ_E_NOSPACE; }
+    zi_find_rows(W, spacing, points, max_entries);
+    return ZZ_OK;
+}
+
+extern "C" int zz_ctx_last_points_index_stats(const zz_ctx* c, uint64_t* candidates, uint64_t* dropped, uint32_t* rounds)
+{
+    if (!c) { set_err("null ctx"); return ZZ_E_ARG; }
+    if (candidates) *candidates = c->dec.pf.candidates;
+    if (dropped) *dropped = c->dec.pf.dropped;
+    if (rounds) *rounds = c->dec.pf.rounds;
+    return ZZ_OK;
 }
 
 // ---- bytes [first, first + nbytes) of an indexed stream (zz_inflate.h's range kernels; the rules in zz_inflate_core.h) -----

@@ -41,7 +41,8 @@
 namespace zz {
 
 // results of the core (the C ABI maps them: DATA / FAR -> ZZ_E_DATA, SPACE -> ZZ_E_NOSPACE)
-enum { ZI_OK = 0, ZI_E_DATA = 1, ZI_E_SPACE = 2, ZI_E_FAR = 3, ZI_E_SHAPE = 4 };
+enum { ZI_OK = 0, ZI_E_DATA = 1, ZI_E_SPACE = 2, ZI_E_FAR = 3, ZI_E_SHAPE = 4,
+       ZI_E_GAVEUP = 5 };      // ZI_RUN_REACH only: the run passed its `limit` bit in mid-block (zi_pt_reach)
 
 #define ZI_ROOT 10
 #define ZI_TAB 1536
@@ -179,7 +180,8 @@ ZZ_HD inline int zi_decode(const zi_view<uint16_t>& tab, uint64_t& bb, uint32_t&
 enum { ZI_RUN_STREAM = 0,     // until the final block (serial path)
        ZI_RUN_INDEXED = 1,    // a packet with a known end: non-final blocks until bit `end * 8`, or the final block
        ZI_RUN_DISCOVER = 2,   // a packet from a candidate start: until `want` bytes at a byte-aligned block end, or the final block
-       ZI_RUN_POINT = 3 };    // a segment of a point index (zi_pt_segment below): from a bit to a bit, exactly `want` bytes
+       ZI_RUN_POINT = 3,      // a segment of a point index (zi_pt_segment below): from a bit to a bit, exactly `want` bytes
+       ZI_RUN_REACH = 4 };    // measuring a stretch (zi_pt_reach below): from a bit to the first block boundary at or behind `stop`
 struct zi_result {
     int err;
     int final;               // the run ended with the final block
@@ -210,6 +212,20 @@ struct zi_pt_segment {
     uint32_t skip; uint64_t stop; bool last; uint64_t end_bit;
     ZZ_HD void block(uint64_t, uint64_t) {}
 };
+// ZI_RUN_REACH (a job of the point finder, zi_find_* below): blocks from bit start * 8 + skip until the FIRST block boundary with
+// consumed() >= stop, or through the final block; nothing is said about bytes. A run from a false start decodes garbage, so it
+// carries `limit`: once consumed() has passed it in mid-block the run ends with ZI_E_GAVEUP (limit = ~0: never). Only a policy
+// that says so (zi_pt_reaches) compiles any of this in.
+struct zi_pt_reach {
+    static constexpr bool on = true;
+    uint32_t skip; uint64_t stop; bool last; uint64_t end_bit;
+    uint64_t limit;
+    ZZ_HD void block(uint64_t, uint64_t) {}
+};
+template <class Pt> struct zi_pt_reaches { static constexpr bool v = false; };
+template <> struct zi_pt_reaches<zi_pt_reach> { static constexpr bool v = true; };
+template <class Pt> ZZ_HD inline uint64_t zi_pt_limit(const Pt&) { return ~0ull; }
+ZZ_HD inline uint64_t zi_pt_limit(const zi_pt_reach& pt) { return pt.limit; }
 template <class In, class Out, class Pt>
 ZZ_HD zi_result zi_run(In& in, zi_view<const uint8_t> view, uint64_t start, Out& o, zi_tables& S, int mode, uint64_t want,
                        uint32_t lane, uint32_t nl, Pt& pt)
@@ -225,6 +241,7 @@ ZZ_HD zi_result zi_run(In& in, zi_view<const uint8_t> view, uint64_t start, Out&
             if (mode == ZI_RUN_INDEXED && b.consumed() == view.n * 8) break;
             if (mode == ZI_RUN_DISCOVER && o.pos == want && (b.consumed() & 7) == 0) break;
             if (Pt::on && mode == ZI_RUN_POINT && b.consumed() == pt.stop) break;
+            if (zi_pt_reaches<Pt>::v && mode == ZI_RUN_REACH && b.consumed() >= pt.stop) break;
         }
         if (b.consumed() >= view.n * 8) { R.err = ZI_E_DATA; break; }          // the run needs another block that is not there
         if (Pt::on) pt.block(b.consumed(), o.pos);
@@ -285,6 +302,7 @@ ZZ_HD zi_result zi_run(In& in, zi_view<const uint8_t> view, uint64_t start, Out&
             }
             // the symbols of the block; one refill covers a whole length / distance pair (<= 48 bits)
             for (;;) {
+                if (zi_pt_reaches<Pt>::v && b.consumed() > zi_pt_limit(pt)) { R.err = ZI_E_GAVEUP; break; }
                 if (b.bn < 48) b.refill();
                 const int sym = zi_decode(lit, b.bb, b.bn);
                 if (sym < 256) {
@@ -315,12 +333,14 @@ ZZ_HD zi_result zi_run(In& in, zi_view<const uint8_t> view, uint64_t start, Out&
         if (bfinal) { R.final = 1; break; }
         if (mode == ZI_RUN_INDEXED && b.consumed() > view.n * 8) { R.err = ZI_E_DATA; break; }
         if (Pt::on && mode == ZI_RUN_POINT && b.consumed() > pt.stop) { R.err = ZI_E_SHAPE; break; }
+        if (zi_pt_reaches<Pt>::v && b.consumed() > zi_pt_limit(pt) && b.consumed() < pt.stop) { R.err = ZI_E_GAVEUP; break; }
     }
     R.end = (b.consumed() + 7) >> 3;
     R.out = o.pos;
     if (Pt::on) pt.end_bit = b.consumed();
     if (R.err) return R;
     if (mode == ZI_RUN_STREAM) { if (!R.final) R.err = ZI_E_DATA; return R; }
+    if (zi_pt_reaches<Pt>::v && mode == ZI_RUN_REACH) return R;
     if (Pt::on && mode == ZI_RUN_POINT) {
         if ((R.final != 0) != pt.last || b.consumed() != pt.stop || o.pos != want) R.err = ZI_E_SHAPE;
         return R;
@@ -1328,6 +1348,218 @@ ZZ_HD int zi_points_build(const uint8_t* src, uint64_t src_len, int format, uint
     sink.put(pt.end_bit, R.out);
     *out_len = R.out;
     return ZI_ITEM_OK;
+}
+
+// ---- the point index found in parallel (zz_points_index_device, zz_inflate_points_find.h; tests/cxx/points_find_harness.cpp) ----
+// Block starts are FOUND in the compressed bytes instead of being reached one after the other. D = the bytes behind the container
+// header, trailer included; C = chunk_bytes. cand[0] = 0, and for every chunk c >= 1 (the bits [8cC, min(8(c+1)C, 8|D|))) the
+// lowest bit p that passes the TEST: BFINAL = 0, BTYPE = 2 and a dynamic header that zi_run would accept (zi_find_header), no bit
+// of it past D. Stored, fixed and final blocks are not searched for. A candidate is only a guess, so the stretches between
+// candidates are MEASURED (ZI_RUN_REACH onto zi_out_count: no byte is written) and chained from bit 0: only what is reached from
+// bit 0 over block boundaries is the true chain, and only candidates on it become rows.
+//
+// the first 74 bits at most of a dynamic header, by one lane: lo = the bits p .. p + 63, hi = the bits from p + 64 on (10 used).
+// BFINAL / BTYPE, HLIT, HDIST, and the code-length code complete (zi_build(19 symbols, neither empty nor incomplete) accepts
+// exactly the length sets whose Kraft sum is one). Rejects nothing zi_find_header accepts.
+ZZ_HD inline bool zi_find_prefilter(uint64_t lo, uint64_t hi)
+{
+    if ((lo & 7u) != 4u) return false;                                // BFINAL 0, BTYPE 2 (binary 10, low bit first)
+    if (((lo >> 3) & 31u) > 29u || ((lo >> 8) & 31u) > 29u) return false;
+    const uint32_t hclen = (uint32_t)((lo >> 13) & 15u) + 4;
+    uint32_t kraft = 0;                                               // in units of 2^-7
+    for (uint32_t i = 0; i < 19; ++i) {
+        const uint32_t at = 17 + 3 * i;                               // 17 .. 71: a field may straddle bit 64
+        const uint32_t l = (uint32_t)((at < 64 ? (lo >> at) | (at > 61 ? hi << (64 - at) : 0) : hi >> (at - 64)) & 7u);
+        if (i < hclen && l) kraft += 128u >> l;
+    }
+    return kraft == 128u;
+}
+// the prefilter at bit p over a byte source (In::peek8: zero past the view, so a header cut off by the end reads zeros)
+template <class In> ZZ_HD bool zi_find_prefilter_at(In& in, uint64_t p)
+{
+    const uint64_t b0 = in.peek8(p >> 3), b1 = in.peek8((p >> 3) + 8);
+    const uint32_t sh = (uint32_t)(p & 7);
+    return zi_find_prefilter(sh ? (b0 >> sh) | (b1 << (64 - sh)) : b0, b1 >> sh);
+}
+// The dynamic header behind BFINAL / BTYPE exactly as zi_run reads it, the two zi_build calls included: restated, not shared, so
+// that zi_run's instantiations stay what they were; the harness holds the two equal at every bit of its small cases.
+template <class In>
+ZZ_HD bool zi_dyn_header(zi_bits<In>& b, zi_tables& S, uint32_t lane, uint32_t nl)
+{
+    zi_view<uint16_t> lit{ S.lit, ZI_TAB }, dst{ S.dst, ZI_TAB };
+    zi_view<uint8_t> lens{ S.lens, 320 };
+    S.kind = 0;
+    b.refill();
+    const uint32_t hlit = b.get(5) + 257, hdist = b.get(5) + 1, hclen = b.get(4) + 4;
+    if (hlit > 286 || hdist > 30) return false;
+    const uint8_t order[19] = { 16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15 };
+    for (int i = 0; i < 19; ++i) lens[i] = 0;
+    b.refill();
+    for (uint32_t i = 0; i < hclen; ++i) { if (b.bn < 3) b.refill(); lens[order[i]] = (uint8_t)b.get(3); }
+    if (!zi_build(lit, S, 19, false, false, lane, nl)) return false;
+    uint32_t idx = 0;
+    while (idx < hlit + hdist) {
+        b.refill();
+        const int sym = zi_decode(lit, b.bb, b.bn);
+        if (sym < 0 || sym > 18) return false;
+        if (sym < 16) { lens[idx++] = (uint8_t)sym; continue; }
+        uint32_t rep, val = 0;
+        if (sym == 16) { if (idx == 0) return false; val = lens[idx - 1]; rep = 3 + b.get(2); }
+        else if (sym == 17) rep = 3 + b.get(3);
+        else rep = 11 + b.get(7);
+        if (idx + rep > hlit + hdist) return false;
+        while (rep--) lens[idx++] = (uint8_t)val;
+    }
+    if (b.overrun()) return false;
+    if (lens[256] == 0) return false;
+    if (!zi_build(lit, S, (int)hlit, false, true, lane, nl)) return false;
+    for (uint32_t i = 0; i < hdist; ++i) lens[i] = lens[hlit + i];
+    if (!zi_build(dst, S, (int)hdist, true, true, lane, nl)) return false;
+    S.kind = 2;
+    return true;
+}
+// the TEST at bit p of view (p < 8 * view.n), by the whole lane group over its tables
+template <class In>
+ZZ_HD bool zi_find_header(In& in, zi_view<const uint8_t> view, uint64_t p, zi_tables& S, uint32_t lane, uint32_t nl)
+{
+    zi_bits<In> b(in, p >> 3, view.n);
+    if (p & 7) (void)b.get((uint32_t)(p & 7));
+    b.refill();
+    if (b.get(1) != 0 || b.get(2) != 2) { S.kind = 0; return false; }
+    return zi_dyn_header(b, S, lane, nl);
+}
+// an Out policy without memory: it counts. A distance cannot be checked here (the decode call does that).
+struct zi_out_count {
+    uint64_t pos;
+    ZZ_HD int lit(uint32_t) { ++pos; return ZI_OK; }
+    ZZ_HD int copy(uint32_t, uint32_t len) { pos += len; return ZI_OK; }
+    ZZ_HD int stored(const zi_view<const uint8_t>&, uint64_t, uint32_t len) { pos += len; return ZI_OK; }
+};
+// A JOB measures one stretch; the record is the job on the way in and its result on the way out (32 bytes, in place).
+//   in:  a = start bit, b = stop bit (~0: through the final block), c = limit bit (~0: none)
+//   out: a = start bit, b = the bit where the run ended, c = the bytes it counted, flags = ZI_FJ_*
+enum { ZI_FJ_OK = 1, ZI_FJ_FINAL = 2, ZI_FJ_GAVEUP = 4, ZI_FJ_ERROR = 8,     // a result has exactly one of OK, GAVEUP, ERROR
+       ZI_FJ_SENT = 16 };                                                        // (the walk's own: asked for, not there yet)
+struct zi_find_job { uint64_t a, b, c; uint32_t flags, pad; };
+#define ZI_FIND_NONE (~0ull)
+// one job by one lane group: the record is read and then written by the caller
+template <class In>
+ZZ_HD zi_find_job zi_find_reach(In& in, zi_view<const uint8_t> view, const zi_find_job& j, zi_tables& S, uint32_t lane, uint32_t nl)
+{
+    zi_out_count o{ 0 };
+    zi_pt_reach pt{ (uint32_t)(j.a & 7), j.b, false, 0, j.c };
+    S.kind = 0;
+    const zi_result R = zi_run(in, view, j.a >> 3, o, S, ZI_RUN_REACH, 0, lane, nl, pt);
+    return zi_find_job{ j.a, pt.end_bit, R.out,
+                        R.err == ZI_OK ? (uint32_t)ZI_FJ_OK | (R.final ? (uint32_t)ZI_FJ_FINAL : 0u) : R.err == ZI_E_GAVEUP ? (uint32_t)ZI_FJ_GAVEUP : (uint32_t)ZI_FJ_ERROR, 0 };
+}
+// chunks of |D| = n bytes (an empty D has one), and the limit of a speculative job that is to stop at `stop`: `slack` bytes more
+ZZ_HD inline uint64_t zi_find_chunks(uint64_t n, uint64_t C) { const uint64_t k = n / C + (n % C ? 1 : 0); return k ? k : 1; }
+ZZ_HD inline uint64_t zi_find_limit(uint64_t stop, uint64_t slack) { return stop == ZI_FIND_NONE || stop + 8 * slack < stop ? ZI_FIND_NONE : stop + 8 * slack; }
+// The chain (zi_find_link) and the rows (zi_find_rows). The WALK owns, for ncand candidates (cand[0] = 0, ascending):
+//   rc[k]  the result of the job from cand[k] to cand[k + 1] (the last one: through the final block)
+//   rr[m]  the result of a REPAIR job that is to stop at cand[m] (m = ncand: through the final block) -- a.start says from where
+//   acc    the accepted jobs in chain order: 2 words each, (start bit | candidate flag in bit 63, bytes)
+// Link k -> k + 1 holds iff rc[k] ended at cand[k + 1]. Where a job of the true chain ends at a bit e that is no candidate, the
+// candidates in front of e are dropped and [e, first candidate at or behind e) is a gap: a repair job from e -- on the true chain by
+// construction, so without a limit -- measures it in the next round. A true-chain job that gave up is run again without a limit.
+// Behind the first gap the walk goes on PROVISIONALLY, as if the gap's repair landed on its candidate, and asks for the repairs it
+// meets there too (with a limit: they may start anywhere), so that the next round finds them done; it accepts nothing there.
+// zi_find_link returns what the round decided; jobs it wants are appended to `want` (room for ncand + 2).
+enum { ZI_FW_MORE = 0,        // jobs are wanted: run them (one launch), store the results with zi_find_store, link again
+       ZI_FW_DONE = 1,        // the chain reached the end of the final block
+       ZI_FW_DATA = 2 };      // a job of the true chain ended in an error: the stream's verdict
+struct zi_find_walk {
+    zi_view<const uint64_t> cand; uint64_t ncand;
+    zi_view<zi_find_job> rc, rr;           // ncand, ncand + 1
+    zi_view<uint64_t> acc; uint64_t nacc;  // 2 * (2 * ncand + 2) words
+    uint64_t pos, m;                       // the confirmed chain's end bit; the first candidate at or behind it
+    uint64_t bytes, kept;                  // decoded bytes in front of pos; accepted jobs that started at a candidate
+    uint64_t end_bit;                      // ZI_FW_DONE: the bit behind the final block
+    uint64_t slack;
+};
+// the jobs of the first round: one per candidate, job 0 without a limit (it is the true chain). The last candidate's job runs
+// through the final block: it gets a limit only where more than ZI_FIND_TAIL bytes of D (n of them) lie behind it.
+#define ZI_FIND_TAIL (1ull << 20)
+ZZ_HD inline zi_find_job zi_find_first_job(const zi_view<const uint64_t>& cand, uint64_t ncand, uint64_t k, uint64_t slack, uint64_t n)
+{
+    const uint64_t stop = k + 1 < ncand ? cand[k + 1] : ZI_FIND_NONE;
+    uint64_t limit = zi_find_limit(stop, slack);
+    if (stop == ZI_FIND_NONE && n * 8 - cand[k] > 8 * ZI_FIND_TAIL) limit = cand[k] + 8 * ZI_FIND_TAIL;
+    return zi_find_job{ cand[k], stop, k ? limit : ZI_FIND_NONE, 0, 0 };
+}
+// a result back into the walk's tables: a job that started at a candidate is rc's, any other rr's (by its start it finds its slot)
+ZZ_HD inline void zi_find_store(zi_find_walk& W, const zi_find_job& r)
+{
+    uint64_t lo = 0, hi = W.ncand;                                   // first candidate at or behind r.a
+    while (lo < hi) { const uint64_t mid = (lo + hi) / 2; if (W.cand[mid] < r.a) lo = mid + 1; else hi = mid; }
+    if (lo < W.ncand && W.cand[lo] == r.a) W.rc[lo] = r; else W.rr[lo] = r;
+}
+ZZ_HD inline int zi_find_link(zi_find_walk& W, zi_view<zi_find_job> want, uint64_t* nwant)
+{
+    *nwant = 0;
+    uint64_t q = ZI_FIND_NONE;                                       // the provisional walk starts at candidate q
+    for (;;) {                                                        // the confirmed chain
+        while (W.m < W.ncand && W.cand[W.m] < W.pos) ++W.m;
+        const bool at_cand = W.m < W.ncand && W.cand[W.m] == W.pos;
+        zi_find_job& R = at_cand ? W.rc[W.m] : W.rr[W.m];
+        const uint64_t stop = at_cand ? (W.m + 1 < W.ncand ? W.cand[W.m + 1] : ZI_FIND_NONE) : (W.m < W.ncand ? W.cand[W.m] : ZI_FIND_NONE);
+        const bool have = (R.flags & (ZI_FJ_OK | ZI_FJ_GAVEUP | ZI_FJ_ERROR)) && R.a == W.pos;
+        if (!have || (R.flags & ZI_FJ_GAVEUP)) {
+            want[(*nwant)++] = zi_find_job{ W.pos, stop, ZI_FIND_NONE, 0, 0 };
+            R = zi_find_job{ W.pos, 0, 0, ZI_FJ_SENT, 0 };
+            q = at_cand ? W.m + 1 : W.m;
+            break;
+        }
+        if (R.flags & ZI_FJ_ERROR) return ZI_FW_DATA;
+        W.acc[2 * W.nacc] = W.pos | (at_cand ? 1ull << 63 : 0); W.acc[2 * W.nacc + 1] = R.c; ++W.nacc;
+        if (at_cand) ++W.kept;
+        W.bytes += R.c;
+        if (R.flags & ZI_FJ_FINAL) { W.end_bit = R.b; return ZI_FW_DONE; }
+        if (R.b <= W.pos) return ZI_FW_DATA;                         // (a run consumes at least a block header)
+        W.pos = R.b;
+    }
+    for (uint64_t steps = 0; q < W.ncand && steps <= W.ncand; ++steps) {   // the provisional chain from candidate q
+        const zi_find_job& R = W.rc[q];
+        if (!(R.flags & ZI_FJ_OK) || (R.flags & ZI_FJ_FINAL) || R.a != W.cand[q] || R.b <= R.a) break;
+        uint64_t lo = q + 1, hi = W.ncand;
+        while (lo < hi) { const uint64_t mid = (lo + hi) / 2; if (W.cand[mid] < R.b) lo = mid + 1; else hi = mid; }
+        if (lo < W.ncand && W.cand[lo] == R.b) { q = lo; continue; }  // the link holds (or hops over dropped candidates)
+        zi_find_job& G = W.rr[lo];
+        if (!(G.flags && G.a == R.b)) {
+            const uint64_t stop = lo < W.ncand ? W.cand[lo] : ZI_FIND_NONE;
+            want[(*nwant)++] = zi_find_job{ R.b, stop, zi_find_limit(stop, W.slack), 0, 0 };
+            G = zi_find_job{ R.b, 0, 0, ZI_FJ_SENT, 0 };
+        }
+        q = lo;
+    }
+    return ZI_FW_MORE;
+}
+// The rows behind ZI_FW_DONE: (0, 0), the accepted candidates with the bytes in front of them (the exclusive scan of the accepted
+// jobs' bytes), (end_bit, bytes); thinned by the host builder's rule (zi_pt_record) -- an inner row is kept only if it is the first
+// at or behind a multiple of `spacing` bytes. Returns the rows; writes them while they fit `max_rows` (rows == nullptr: counts).
+ZZ_HD inline uint64_t zi_find_rows(const zi_find_walk& W, uint64_t spacing, uint64_t* rows, uint64_t max_rows)
+{
+    uint64_t n = 0, pos = 0, next = 0;
+    for (uint64_t i = 0; i < W.nacc; ++i) {
+        const uint64_t bit = W.acc[2 * i] & ~(1ull << 63);
+        if ((W.acc[2 * i] >> 63) && !(pos < next && !(spacing == 1 && bit != 0))) {
+            if (rows && n < max_rows) { rows[2 * n] = bit; rows[2 * n + 1] = pos; }
+            ++n;
+            next = pos - pos % spacing + spacing;
+        }
+        pos += W.acc[2 * i + 1];
+    }
+    if (rows && n < max_rows) { rows[2 * n] = W.end_bit; rows[2 * n + 1] = pos; }
+    return n + 1;
+}
+// the trailer's place and, for gzip, ISIZE: what the call can judge without a decoded byte. t = the last min(n, 8) bytes of D.
+ZZ_HD inline bool zi_find_trailer_ok(int format, uint64_t n, uint64_t end_bit, uint64_t out_len, const uint8_t* t)
+{
+    const uint64_t tl = format == 0 ? 4 : format == 1 ? 8 : 0, end = (end_bit + 7) >> 3;
+    if (end > n || n - end != tl) return false;
+    if (format != 1) return true;
+    return (t[4] | ((uint32_t)t[5] << 8) | ((uint32_t)t[6] << 16) | ((uint32_t)t[7] << 24)) == (uint32_t)out_len;
 }
 
 // ---- reads of any stream through a point index with windows (zz_decode_points_ranges_device, zz_inflate_points_ranges.h;
