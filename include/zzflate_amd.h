@@ -681,6 +681,42 @@ int zz_decode_points_ranges_device(zz_ctx* ctx, const void* d_src, uint64_t src_
 /* what the last zz_decode_points_ranges_device did: the segments it decoded (each once), and the waves */
 int zz_ctx_last_decode_points_ranges_stats(const zz_ctx* ctx, uint64_t* segments_decoded, uint32_t* waves);
 
+/* ---- the same sidecar built on the device ----------------------------------------------------------------------
+ * For a stream d_src[0, src_len) in DEVICE memory and the rows `points` (HOST memory, `entries` of them), d_windows and d_sums
+ * (DEVICE: (entries - 1) * 32768 bytes, entries - 1 words) receive exactly what zz_points_windows_host makes for those rows; the
+ * bytes that format leaves unspecified -- the front of a slot where the stream is shorter than 32 KiB there, all of slot 0 -- are
+ * written as zeros. The stream is decoded in batches of at most stage_bytes decoded bytes (0: 64 MiB, also the most) by
+ * zz_decode_points_device's kernels onto a stage of 32768 + stage_bytes bytes, and slots and sums are cut out of each batch; no
+ * destination of the stream's length is needed. With d_dst (cap bytes, DEVICE) the batches decode there instead and the decoded
+ * stream is left in d_dst[0, last out_byte).
+ * fine_points (HOST, may be NULL): rows to DECODE with, a superset of `points` -- every row of `points` occurs in it with the same
+ *   two numbers, first and last rows equal. The sidecar wants sparse rows (32,772 bytes per segment), the decode dense ones (a
+ *   wavefront per segment): take the index dense (zz_points_index_device, spacing 1), thin it for the sidecar (zz_points_thin), and
+ *   pass both.
+ * NOTHING IS TRUSTED, and nothing is repaired: ZZ_E_DATA wherever zz_points_windows_host gives it -- rows that are not an index
+ *   (row 0 == (0, 0), in_bit strictly ascending, out_byte ascending), a last row that is not the end of the final block directly in
+ *   front of the trailer, a segment (of the rows decoded with) that does not begin at a block header, end at the next row's bit with
+ *   exactly its room or keep its distances inside the stream, and, for zlib and gzip, sums whose fold over the 64-bit segment
+ *   lengths misses the trailer (gzip: ISIZE against L mod 2^32 too). A raw stream has no trailer to hold the sums to.
+ *   ZZ_E_UNSUPPORTED: a preset dictionary; a segment of the rows decoded with that is longer than the stage.
+ *   After a failure the contents of d_windows, d_sums and d_dst are unspecified; nothing is written outside them.
+ * ZZ_E_ARG, before anything is launched: a null context, source, points, d_windows or d_sums; entries < 2; entries - 1 above
+ *   2^31 - 1; a format outside 0..2; stage_bytes above 64 MiB; d_dst null with cap > 0; fine_points that is no superset of points;
+ *   an unfinished zz_encode_device_async. ZZ_E_NOSPACE, nothing written: d_dst given and cap below the last out_byte.
+ * Workspace: the stage, 4 bytes of pointer and 1 bit per byte of a batch, 32 bytes per segment of a batch. Synchronous; the host
+ * reads the batch's counters and its sums (4 bytes per segment) once per batch and folds them. Leaves the context's "last call",
+ * "last decode" path and stats and the range calls' stats alone. */
+int zz_points_windows_device(zz_ctx* ctx, const void* d_src, uint64_t src_len, int format,
+                             const uint64_t* points, uint64_t entries, const uint64_t* fine_points, uint64_t fine_entries,
+                             void* d_windows, uint32_t* d_sums, void* d_dst, uint64_t cap, uint64_t stage_bytes, void* hip_stream);
+/* what the last zz_points_windows_device did: decode batches launched, the bytes phase 1 left pending, the most rounds of a batch */
+int zz_ctx_last_points_windows_stats(const zz_ctx* ctx, uint64_t* batches, uint64_t* pending_bytes, uint32_t* rounds);
+/* An index thinned on the host by the builders' own rule: row 0 and the last row stay, an inner row stays iff it is the first at
+ * or behind the next multiple of `spacing` decoded bytes -- zz_points_thin(index at spacing 1, s) is the index at spacing s.
+ * *out_entries is set whenever the arguments pass (ZZ_E_NOSPACE: max_entries is too small, or out is NULL). ZZ_E_ARG: a null
+ * points or out_entries, entries < 2, spacing 0. */
+int zz_points_thin(const uint64_t* points, uint64_t entries, uint64_t spacing, uint64_t* out, uint64_t max_entries, uint64_t* out_entries);
+
 enum { ZZ_DECODE_INDEXED = 1, ZZ_DECODE_DISCOVERED = 2, ZZ_DECODE_SERIAL = 3, ZZ_DECODE_POINTS = 4 };
 /* which path the last zz_decode_device / zz_decode_points_device finished on (0: none) */
 int zz_ctx_last_decode_path(const zz_ctx* ctx);

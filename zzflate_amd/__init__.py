@@ -18,7 +18,7 @@ __all__ = [
     "Format", "Config", "ZzFlateError", "ZzFlateEncode", "ZzFlateEncodeToCallback", "adler32x", "combine",
     "crc32", "crc32_combine", "bound", "Context", "lib", "DEFAULT_PACKET", "generate_host", "header", "trailer",
     "MEMBERS_BLOCK", "members_bound", "members_header", "gzi_bytes", "packet_checksums_host",
-    "POINTS_CHUNK", "points_index_bound",
+    "POINTS_CHUNK", "points_index_bound", "points_thin",
 ]
 
 DEFAULT_PACKET = 32768
@@ -120,6 +120,9 @@ def _load():
         "zz_ctx_last_decode_members_ranges_stats": (i32, [vp, pu64, ctypes.POINTER(u32)]),
         "zz_points_windows_host": (i32, [vp, u64, i32, vp, u64, vp, vp]),
         "zz_decode_points_ranges_device": (i32, [vp, vp, u64, i32, vp, u64, vp, vp, u64, vp, vp, vp, vp, vp, vp, vp]),
+        "zz_points_windows_device": (i32, [vp, vp, u64, i32, vp, u64, vp, u64, vp, vp, vp, u64, u64, vp]),
+        "zz_ctx_last_points_windows_stats": (i32, [vp, pu64, pu64, ctypes.POINTER(u32)]),
+        "zz_points_thin": (i32, [vp, u64, u64, vp, u64, pu64]),
         "zz_ctx_last_decode_points_ranges_stats": (i32, [vp, pu64, ctypes.POINTER(u32)]),
         "zz_ctx_last_decode_path": (i32, [vp]),
         "zz_ctx_last_decode_stats": (i32, [vp, pu64, ctypes.POINTER(u32)]),
@@ -310,6 +313,22 @@ def points_windows_host(data, points, format=Format.Zlib):
     sums = torch.zeros(segments, dtype=torch.int32)
     _check(lib.zz_points_windows_host(data, len(data), int(format), points.data_ptr(), points.shape[0], windows.data_ptr(), sums.data_ptr()))
     return windows, sums
+
+
+def points_thin(points, spacing):
+    """The point index ``points`` (an ``(entries, 2)`` int64 CPU tensor) thinned to ``spacing`` decoded bytes by the builders' own
+    rule: row 0 and the last row stay, an inner row stays iff it is the first at or behind the next multiple of ``spacing``. A
+    dense index (``Context.points_index``, spacing 1) thinned to ``s`` is the index at spacing ``s``. Returns a CPU tensor."""
+    import torch
+    _points_tensor(points, "cpu")
+    if isinstance(spacing, bool) or not isinstance(spacing, int):
+        raise TypeError("spacing must be an int")
+    if spacing < 1:
+        raise ValueError("spacing must be at least 1")
+    out = torch.zeros((points.shape[0], 2), dtype=torch.int64)
+    entries = ctypes.c_uint64(0)
+    _check(lib.zz_points_thin(points.data_ptr(), points.shape[0], spacing, out.data_ptr(), out.shape[0], ctypes.byref(entries)))
+    return out[: entries.value].clone()
 
 
 def members_bound(n, block_size=MEMBERS_BLOCK, packet_size=DEFAULT_PACKET, eof=True):
@@ -732,6 +751,58 @@ class Context:
         Results and path reporting are ``decode_points``'s."""
         points, _ = self.points_index(src, src_len, format, chunk_bytes, 1, stream)
         return self.decode_points(src, src_len, dst, cap, points, format, stream)
+
+    def points_windows(self, src, src_len, points, format=Format.Zlib, fine_points=None, dst=None, cap=None, stage_bytes=0, stream=None):
+        """``points_windows_host`` on the device, for a stream in device memory: ``(windows, sums)`` on this context's device -- uint8
+        ``[segments, 32768]`` and int32 ``[segments]``, byte for byte what the host builder returns for the CPU tensor ``points``
+        and exactly what ``decode_points_ranges`` takes. ``fine_points``: a CPU tensor of rows to decode with, a superset of
+        ``points`` (the dense index that ``points`` was thinned from: the decode wants dense rows, the sidecar sparse ones).
+        ``dst`` (``cap`` bytes, default its size): also leave the decoded stream there. ``stage_bytes``: decoded bytes per batch
+        (0: 64 MiB), which bounds the workspace. The index is verified, never repaired: ZzFlateError (E_DATA, E_UNSUPPORTED,
+        E_ARG, E_NOSPACE) otherwise."""
+        import torch
+        _points_tensor(points, "cpu")
+        fp, fn = None, 0
+        if fine_points is not None:
+            _points_tensor(fine_points, "cpu")
+            fp, fn = fine_points.data_ptr(), fine_points.shape[0]
+        if isinstance(stage_bytes, bool) or not isinstance(stage_bytes, int):
+            raise TypeError("stage_bytes must be an int")
+        if stage_bytes < 0:
+            raise ValueError("stage_bytes must not be negative")
+        dp = None
+        if dst is not None:
+            if not isinstance(dst, torch.Tensor) or dst.dtype != torch.uint8 or not dst.is_contiguous():
+                raise TypeError("dst must be a contiguous uint8 tensor")
+            dp, cap = self._ptr(dst), (dst.numel() if cap is None else cap)
+        elif cap:
+            raise TypeError("cap needs dst")
+        segments = points.shape[0] - 1
+        dev = torch.device("cuda", self.device)
+        windows = torch.empty((segments, POINTS_WINDOW), dtype=torch.uint8, device=dev)
+        sums = torch.empty(segments, dtype=torch.int32, device=dev)
+        st = self._stream() if stream is None else stream
+        _check(lib.zz_points_windows_device(self._h, self._ptr(src), src_len, int(format), points.data_ptr(), points.shape[0], fp, fn,
+                                            windows.data_ptr(), sums.data_ptr(), dp, cap or 0, stage_bytes, st))
+        return windows, sums
+
+    def last_points_windows_stats(self):
+        """(decode batches, pending bytes, most rounds of a batch) of the last ``points_windows``."""
+        batches, pending, rounds = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint32(0)
+        _check(lib.zz_ctx_last_points_windows_stats(self._h, ctypes.byref(batches), ctypes.byref(pending), ctypes.byref(rounds)))
+        return batches.value, pending.value, rounds.value
+
+    def open_found(self, src, src_len, format=Format.Zlib, chunk_bytes=POINTS_CHUNK, spacing=POINTS_SPACING, dst=None, cap=None,
+                   stream=None):
+        """A foreign stream in device memory opened for ``decode_points_ranges`` with no host pass over its bytes:
+        ``points_index`` (dense) on the device, ``points_thin`` to ``spacing``, ``points_windows`` with the dense rows to decode
+        with. Returns ``(points, windows, sums, decoded_length)``, all three tensors on this context's device. With ``dst`` the
+        stream is also decoded whole in the same call."""
+        import torch
+        dense, n = self.points_index(src, src_len, format, chunk_bytes, 1, stream)
+        points = points_thin(dense, spacing)
+        windows, sums = self.points_windows(src, src_len, points, format, dense, dst, cap, 0, stream)
+        return points.to(torch.device("cuda", self.device)), windows, sums, n
 
     def decode_range(self, src, src_len, dst, cap, first, nbytes, format=Format.Zlib, packet_size=DEFAULT_PACKET, index=None,
                      stream=None):

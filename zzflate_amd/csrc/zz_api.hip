@@ -37,6 +37,7 @@
 #include "zz_inflate_members.h"
 #include "zz_inflate_members_ranges.h"
 #include "zz_inflate_points_ranges.h"
+#include "zz_inflate_points_windows.h"
 #include "zz_batch.h"
 #include "zz_members_write.h"
 
@@ -211,6 +212,13 @@ struct zz_ctx {
             zz_buf<zz_pr_state> st; zz_pin<zz_pr_state> h_st;
             uint64_t decoded = 0; uint32_t waves_run = 0;
         } pr;
+        // zz_points_windows_device (zz_inflate_points_windows.h): the stage (32 KiB carried, then a batch), the rows the cut works on,
+        // two slots nobody keeps and one sum (a sidecar segment longer than the stage is cut piece by piece), the dealing counter,
+        // and what the last call did
+        struct {
+            zz_buf<uint8_t> stage, spare; zz_buf<uint64_t> rows; zz_buf<uint32_t> piece; zz_buf<unsigned int> next;
+            uint64_t batches = 0, pending = 0; uint32_t rounds = 0;
+        } pw;
     } dec;
 };
 // one call per context at a time: every entry point that would use the buffers of an enqueued call refuses
@@ -1399,6 +1407,53 @@ extern "C" int zz_points_index_host(const uint8_t* src, uint64_t src_len, int fo
     return ZZ_OK;
 }
 
+// One batch of the point-index decode, shared by dec_points and the sidecar's builder (pw_build): segments [0, nseg) of `rows` (host,
+// nseg + 1 of them) through phase 1, the tile counts and the rounds onto dst, which is addressed by absolute output position. The
+// workspace (dec_points_workspace) holds the batch. DEC_SERIAL: a segment's run was refused. *pending, *rounds_used: what the batch adds.
+static int dec_points_workspace(zz_ctx* c, uint64_t max_bytes, uint64_t max_segs)
+{
+    auto& D = c->dec;
+    const uint64_t max_tiles = (max_bytes + ZI_POINTS_TILE - 1) / ZI_POINTS_TILE;
+    if (int rc = dec_batch_workspace(c, max_tiles, max_bytes, ZI_POINTS_TILE / 32, 0)) return rc;
+    if (int rc = D.pts.rows.grow(2 * (max_segs + 1))) return rc;
+    if (int rc = D.pts.stat.grow(max_segs)) return rc;
+    return D.pts.next.grow(1);
+}
+static int dec_points_batch(zz_ctx* c, const uint8_t* s, uint64_t sn, const uint64_t* rows, uint32_t nseg, bool last, uint8_t* dst,
+                            hipStream_t st, uint64_t* pending, uint32_t* rounds_used)
+{
+    auto& D = c->dec;
+    const uint32_t words = ZI_POINTS_TILE / 32;
+    const uint64_t resident = 256ull * ZZ_PT_WG_PER_CU;                     // persistent wavefronts: what the CUs hold at once
+    const uint64_t base = rows[1], nbytes = rows[2 * (uint64_t)nseg + 1] - base;
+    const uint32_t tiles = (uint32_t)((nbytes + ZI_POINTS_TILE - 1) / ZI_POINTS_TILE);
+    HIPCHK(hipMemsetAsync(D.tot, 0, ZZ_TOT_SLOTS * sizeof(unsigned long long), st));
+    HIPCHK(hipMemsetAsync(D.pts.next, 0, sizeof(unsigned int), st));
+    if (tiles) HIPCHK(hipMemsetAsync(D.pend, 0, (uint64_t)tiles * words * 4, st));
+    HIPCHK(hipMemcpyAsync(D.pts.rows, rows, (uint64_t)(nseg + 1) * 16, hipMemcpyHostToDevice, st));
+    zz_pt_params Q;
+    Q.s = s; Q.sn = sn; Q.rows = D.pts.rows; Q.nseg = nseg; Q.last = last; Q.dst = dst; Q.base = base; Q.nbytes = nbytes;
+    Q.st = D.st; Q.pend = D.pend; Q.words = (uint64_t)tiles * words; Q.stat = D.pts.stat; Q.next = D.pts.next; Q.tot = D.tot;
+    hipLaunchKernelGGL(k_inflate_segments, dim3((uint32_t)(nseg < resident ? nseg : resident)), dim3(ZZ_INF_THREADS), 0, st, Q);
+    if (tiles) hipLaunchKernelGGL(k_points_count, dim3(tiles), dim3(256), 0, st, D.pend, D.pcnt, D.prem, D.tot);
+    HIPCHK(hipGetLastError());
+    unsigned long long tot[ZZ_TOT_SLOTS];
+    if (int rc = dec_read_tot(c, tot, st)) return rc;
+    if (tot[ZZ_TOT_FAILED] != 0) return DEC_SERIAL;                         // a segment is not what the index says
+    if (tot[ZZ_TOT_PENDING] == 0) return DEC_DONE;
+    const uint32_t rounds = zz_inf_rounds(nseg);                            // a chain has at most one link per segment of a batch
+    zz_res_params R{ dst, base, ZI_POINTS_TILE, tiles, words, D.st, D.pend, D.pcnt, D.prem, D.tot };
+    for (uint32_t r = 1; r <= rounds; ++r) hipLaunchKernelGGL(k_inflate_resolve, dim3(tiles), dim3(ZZ_INF_RES_THREADS), 0, st, R, r);
+    HIPCHK(hipGetLastError());
+    if (int rc = dec_read_tot(c, tot, st)) return rc;
+    if (tot[ZZ_TOT_OPEN + rounds] != 0) return DEC_SERIAL;                  // (cannot happen: the rounds suffice for any chain)
+    uint32_t r = 1;
+    while (r < rounds && tot[ZZ_TOT_OPEN + r] != 0) ++r;
+    *pending += tot[ZZ_TOT_PENDING];
+    *rounds_used = std::max(*rounds_used, r);
+    return DEC_DONE;
+}
+
 // phase 1 over the segments, the tile counts and the rounds, batch by batch. DEC_SERIAL: the index or a segment's run was refused
 // (what this wrote so far lies inside [0, cap) and the serial path writes over it).
 static int dec_points(zz_ctx* c, const uint8_t* s, uint64_t sn, const uint64_t* points, uint64_t entries, uint8_t* dst, uint64_t cap,
@@ -1414,43 +1469,13 @@ static int dec_points(zz_ctx* c, const uint8_t* s, uint64_t sn, const uint64_t* 
         max_bytes = std::max(max_bytes, points[2 * k1 + 1] - points[2 * k0 + 1]);
         max_segs = std::max(max_segs, k1 - k0);
     }
-    const uint32_t words = ZI_POINTS_TILE / 32;
-    const uint64_t max_tiles = (max_bytes + ZI_POINTS_TILE - 1) / ZI_POINTS_TILE;
-    if (!dec_have(dec_batch_workspace(c, max_tiles, max_bytes, words, 0)) || !dec_have(D.pts.rows.grow(2 * (max_segs + 1))) ||
-        !dec_have(D.pts.stat.grow(max_segs)) || !dec_have(D.pts.next.grow(1)))
-        return DEC_SERIAL;
+    if (!dec_have(dec_points_workspace(c, max_bytes, max_segs))) return DEC_SERIAL;
     uint64_t pending = 0;
     uint32_t rounds_used = 0;
-    const uint64_t resident = 256ull * ZZ_PT_WG_PER_CU;                     // persistent wavefronts: what the CUs hold at once
     for (uint64_t k0 = 0, k1; k0 < nseg_total; k0 = k1) {
         k1 = zi_points_batches(points, entries, k0, ZZ_INF_BATCH_BYTES, ZZ_PT_BATCH_SEGMENTS);
-        const uint32_t nseg = (uint32_t)(k1 - k0);
-        const uint64_t base = points[2 * k0 + 1], nbytes = points[2 * k1 + 1] - base;
-        const uint32_t tiles = (uint32_t)((nbytes + ZI_POINTS_TILE - 1) / ZI_POINTS_TILE);
-        HIPCHK(hipMemsetAsync(D.tot, 0, ZZ_TOT_SLOTS * sizeof(unsigned long long), st));
-        HIPCHK(hipMemsetAsync(D.pts.next, 0, sizeof(unsigned int), st));
-        if (tiles) HIPCHK(hipMemsetAsync(D.pend, 0, (uint64_t)tiles * words * 4, st));
-        HIPCHK(hipMemcpyAsync(D.pts.rows, points + 2 * k0, (uint64_t)(nseg + 1) * 16, hipMemcpyHostToDevice, st));
-        zz_pt_params Q;
-        Q.s = s; Q.sn = sn; Q.rows = D.pts.rows; Q.nseg = nseg; Q.last = k1 == nseg_total; Q.dst = dst; Q.base = base; Q.nbytes = nbytes;
-        Q.st = D.st; Q.pend = D.pend; Q.words = (uint64_t)tiles * words; Q.stat = D.pts.stat; Q.next = D.pts.next; Q.tot = D.tot;
-        hipLaunchKernelGGL(k_inflate_segments, dim3((uint32_t)(nseg < resident ? nseg : resident)), dim3(ZZ_INF_THREADS), 0, st, Q);
-        if (tiles) hipLaunchKernelGGL(k_points_count, dim3(tiles), dim3(256), 0, st, D.pend, D.pcnt, D.prem, D.tot);
-        HIPCHK(hipGetLastError());
-        unsigned long long tot[ZZ_TOT_SLOTS];
-        if (int rc = dec_read_tot(c, tot, st)) return rc;
-        if (tot[ZZ_TOT_FAILED] != 0) return DEC_SERIAL;                     // a segment is not what the index says
-        if (tot[ZZ_TOT_PENDING] == 0) continue;
-        const uint32_t rounds = zz_inf_rounds(nseg);                        // a chain has at most one link per segment of a batch
-        zz_res_params R{ dst, base, ZI_POINTS_TILE, tiles, words, D.st, D.pend, D.pcnt, D.prem, D.tot };
-        for (uint32_t r = 1; r <= rounds; ++r) hipLaunchKernelGGL(k_inflate_resolve, dim3(tiles), dim3(ZZ_INF_RES_THREADS), 0, st, R, r);
-        HIPCHK(hipGetLastError());
-        if (int rc = dec_read_tot(c, tot, st)) return rc;
-        if (tot[ZZ_TOT_OPEN + rounds] != 0) return DEC_SERIAL;              // (cannot happen: the rounds suffice for any chain)
-        uint32_t r = 1;
-        while (r < rounds && tot[ZZ_TOT_OPEN + r] != 0) ++r;
-        pending += tot[ZZ_TOT_PENDING];
-        rounds_used = std::max(rounds_used, r);
+        const int got = dec_points_batch(c, s, sn, points + 2 * k0, (uint32_t)(k1 - k0), k1 == nseg_total, dst, st, &pending, &rounds_used);
+        if (got != DEC_DONE) return got;
     }
     D.last_pending = pending; D.last_rounds = rounds_used;
     *out = points[2 * nseg_total + 1];
@@ -2883,6 +2908,161 @@ extern "C" int zz_points_windows_host(const uint8_t* src, uint64_t src_len, int 
     const int rc = zi_points_windows_build(src, src_len, format, points, entries, windows, sums, ring.data(), S[0], sum[0]);
     if (rc == ZI_ITEM_UNSUPPORTED) { set_err("the stream needs a preset dictionary (FDICT): not supported"); return ZZ_E_UNSUPPORTED; }
     if (rc) { set_err("not a valid stream of the requested format, or not an index of it (a row is no block boundary with its bytes in front of it)"); return ZZ_E_DATA; }
+    return ZZ_OK;
+}
+
+// The same sidecar built on the device (zz_inflate_points_windows.h). A UNIT is what lies on the stage at once: the decode
+// rows [g0, g1] -- decoded by dec_points_batch, in several launches where they are more than ZZ_PT_BATCH_SEGMENTS -- and the rows the
+// cut works on: the sidecar's rows of a batch planned over `points`, or, for a sidecar segment longer than the stage, the two ends of
+// a piece of it.
+struct pw_unit {
+    uint64_t g0, g1;                            // decode rows
+    const uint64_t* cut_rows; uint32_t ncut;    // ncut + 1 rows (host): slots and sums of the segments between them
+    uint8_t* win_dst; uint32_t* sum_dst;        // where slot 0 .. ncut - 1 and the sums go
+    uint8_t* tail_dst;                          // where the slot of row ncut goes: the next unit's carry (null: the stream ends here)
+};
+static int pw_run_unit(zz_ctx* c, const uint8_t* s, uint64_t sn, const uint64_t* dec, uint64_t dec_entries, const pw_unit& U, uint8_t* d_dst,
+                       uint64_t stage_bytes, int kind, hipStream_t st)
+{
+    auto& W = c->dec.pw;
+    const uint64_t base = dec[2 * U.g0 + 1], end = dec[2 * U.g1 + 1];
+    const int64_t org = zi_pw_org(base, d_dst != nullptr);
+    uint8_t* const buf = d_dst ? d_dst : (uint8_t*)W.stage;
+    uint8_t* const pos0 = (uint8_t*)((uintptr_t)buf - (uintptr_t)org);          // where position 0 would lie: the decode addresses by position
+    for (uint64_t h0 = U.g0, h1; h0 < U.g1; h0 = h1) {
+        h1 = zi_points_batches(dec, U.g1 + 1, h0, stage_bytes, ZZ_PT_BATCH_SEGMENTS);
+        const int got = dec_points_batch(c, s, sn, dec + 2 * h0, (uint32_t)(h1 - h0), h1 + 1 == dec_entries, pos0, st, &W.pending, &W.rounds);
+        if (got < 0) return got;
+        if (got != DEC_DONE) { set_err("not an index of this stream: a segment does not decode from its row to the next with its bytes"); return ZZ_E_DATA; }
+        ++W.batches;
+    }
+    HIPCHK(hipMemcpyAsync(W.rows, U.cut_rows, (uint64_t)(U.ncut + 1) * 16, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemsetAsync(W.next, 0, sizeof(unsigned int), st));
+    zz_pw_params Q;
+    Q.buf = buf; Q.buf_n = d_dst ? end : ZI_PR_WINDOW + (end - base); Q.org = org; Q.rows = W.rows; Q.nseg = U.ncut;
+    Q.windows = U.win_dst; Q.sums = U.sum_dst; Q.tail = U.tail_dst; Q.kind = kind; Q.next = W.next;
+    const uint64_t items = (uint64_t)U.ncut + (U.tail_dst ? 1 : 0), resident = 256ull * ZZ_PT_WG_PER_CU;
+    hipLaunchKernelGGL(k_points_windows_cut, dim3((uint32_t)(items < resident ? items : resident)), dim3(ZZ_INF_THREADS), 0, st, Q);
+    HIPCHK(hipGetLastError());
+    if (U.tail_dst && !d_dst) HIPCHK(hipMemcpyAsync(W.stage, U.tail_dst, ZI_PR_WINDOW, hipMemcpyDeviceToDevice, st));   // the next carry
+    return ZZ_OK;
+}
+
+extern "C" int zz_points_windows_device(zz_ctx* c, const void* d_src_v, uint64_t src_len, int format, const uint64_t* points, uint64_t entries,
+                                        const uint64_t* fine_points, uint64_t fine_entries, void* d_windows_v, uint32_t* d_sums,
+                                        void* d_dst_v, uint64_t cap, uint64_t stage_bytes, void* hip_stream)
+{
+    if (!c || !d_src_v || !points || !d_windows_v || !d_sums) { set_err("null argument"); return ZZ_E_ARG; }
+    if (entries < 2) { set_err("a point index has at least two rows (host memory)"); return ZZ_E_ARG; }
+    if (entries - 1 > 0x7fffffffull) { set_err("at most 2^31 - 1 segments per index"); return ZZ_E_ARG; }
+    if (!dec_format_ok(format)) return ZZ_E_ARG;
+    if (stage_bytes > ZZ_INF_BATCH_BYTES) { set_err("stage_bytes is at most " + std::to_string(ZZ_INF_BATCH_BYTES)); return ZZ_E_ARG; }
+    if (!d_dst_v && cap) { set_err("null buffer"); return ZZ_E_ARG; }
+    if (fine_points && !zi_points_superset(points, entries, fine_points, fine_entries)) {
+        set_err("fine_points must hold every row of points, and the same first and last row");
+        return ZZ_E_ARG;
+    }
+    if (call_pending(c)) return ZZ_E_ARG;
+    const uint64_t segments = entries - 1, L = points[2 * segments + 1];
+    if (d_dst_v && cap < L) { set_err("destination too small for the decoded stream (" + std::to_string(L) + " bytes)"); return ZZ_E_NOSPACE; }
+    const uint8_t* d_src = (const uint8_t*)d_src_v;
+    uint8_t* const d_windows = (uint8_t*)d_windows_v;
+    uint8_t* const d_dst = (uint8_t*)d_dst_v;
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t st = (hipStream_t)hip_stream;
+    auto& W = c->dec.pw;
+    W.batches = 0; W.pending = 0; W.rounds = 0;
+    int64_t hl = 0;
+    if (int rc = dec_container(d_src, src_len, format, st, &hl)) return rc;
+    const uint64_t tl = (uint64_t)trailer_len(format), sn = src_len - hl - tl;
+    const uint64_t stage = stage_bytes ? stage_bytes : ZZ_INF_BATCH_BYTES;
+    const uint64_t* const dec = fine_points ? fine_points : points;                // the rows decoded with
+    const uint64_t dec_entries = fine_points ? fine_entries : entries;
+    if (!zi_points_check(points, entries, sn, ~0ull, ~0ull) || !zi_points_check(dec, dec_entries, sn, ~0ull, ~0ull) ||
+        (points[2 * segments] + 7) / 8 != sn) {
+        set_err("not an index of this stream: row 0 = (0, 0), bits strictly ascending, bytes ascending, the last row directly in front of the trailer");
+        return ZZ_E_DATA;
+    }
+    if (!zi_points_check(dec, dec_entries, sn, ~0ull, stage)) { set_err("a segment is longer than the stage (stage_bytes)"); return ZZ_E_UNSUPPORTED; }
+    // the workspace: nothing on the stage is longer than min(stage, L)
+    const uint64_t most = std::max<uint64_t>(1, std::min(stage, L));
+    if (int rc = c->dec.tot.grow(ZZ_TOT_SLOTS)) return rc;
+    if (int rc = dec_points_workspace(c, most, std::min<uint64_t>(ZZ_PT_BATCH_SEGMENTS, dec_entries - 1))) return rc;
+    if (!d_dst) if (int rc = W.stage.grow(ZI_PR_WINDOW + most)) return rc;
+    if (int rc = W.spare.grow(2 * ZI_PR_WINDOW)) return rc;
+    if (int rc = W.rows.grow(2 * (std::min<uint64_t>(ZZ_PT_BATCH_SEGMENTS, segments) + 1))) return rc;
+    if (int rc = W.piece.grow(1)) return rc;
+    if (int rc = W.next.grow(1)) return rc;
+    const int kind = zi_sidecar_kind(format);
+    std::vector<uint32_t> got;                                                     // a batch's sums, for the fold
+    zi_pr_part all{ 0, 0 };
+    uint64_t piece_rows[4];
+    uint32_t joined = 0;
+    uint64_t f0 = 0;                                                               // the decode row that is row k0
+    for (uint64_t k0 = 0, k1; k0 < segments; k0 = k1) {
+        k1 = zi_points_batches(points, entries, k0, stage, ZZ_PT_BATCH_SEGMENTS);
+        uint64_t f1 = f0 + (k1 - k0);
+        if (fine_points) for (f1 = f0 + 1; f1 + 1 < fine_entries && fine_points[2 * f1] != points[2 * k1]; ++f1) {}   // (the superset walk found the row; bits ascend strictly)
+        uint8_t* const tail = k1 < segments ? d_windows + k1 * ZI_PR_WINDOW : nullptr;
+        if (points[2 * k1 + 1] - points[2 * k0 + 1] <= stage) {
+            const pw_unit U{ f0, f1, points + 2 * k0, (uint32_t)(k1 - k0), d_windows + k0 * ZI_PR_WINDOW, d_sums + k0, tail };
+            if (int rc = pw_run_unit(c, d_src + hl, sn, dec, dec_entries, U, d_dst, stage, kind, st)) return rc;
+            got.resize(k1 - k0);
+            HIPCHK(hipMemcpyAsync(got.data(), d_sums + k0, (k1 - k0) * 4, hipMemcpyDeviceToHost, st));
+            HIPCHK(hipStreamSynchronize(st));
+            for (uint64_t k = k0; k < k1; ++k) {
+                zi_pr_part p;
+                if (!zi_pr_entry_part(kind, got[k - k0], points[2 * k + 3] - points[2 * k + 1], &p)) { set_err("a segment's sum is none its length can have"); return ZZ_E_DATA; }
+                all = zi_pr_join(kind, all, p);
+            }
+        } else {
+            // one sidecar segment longer than the stage, decoded with finer rows: piece by piece, the pieces' sums joined here
+            zi_pr_part seg{ 0, 0 };
+            for (uint64_t g0 = f0, g1; g0 < f1; g0 = g1) {
+                g1 = zi_points_batches(dec, f1 + 1, g0, stage, ZZ_PT_BATCH_SEGMENTS);
+                piece_rows[0] = dec[2 * g0]; piece_rows[1] = dec[2 * g0 + 1]; piece_rows[2] = dec[2 * g1]; piece_rows[3] = dec[2 * g1 + 1];
+                const pw_unit U{ g0, g1, piece_rows, 1, g0 == f0 ? d_windows + k0 * ZI_PR_WINDOW : (uint8_t*)W.spare, W.piece,
+                                 g1 == f1 ? tail : (uint8_t*)W.spare + ZI_PR_WINDOW };
+                if (int rc = pw_run_unit(c, d_src + hl, sn, dec, dec_entries, U, d_dst, stage, kind, st)) return rc;
+                uint32_t v = 0;
+                HIPCHK(hipMemcpyAsync(&v, W.piece, 4, hipMemcpyDeviceToHost, st));
+                HIPCHK(hipStreamSynchronize(st));
+                zi_pr_part p;
+                if (!zi_pr_entry_part(kind, v, piece_rows[3] - piece_rows[1], &p)) { set_err("a piece's sum is none its length can have"); return ZZ_E_DATA; }
+                seg = zi_pr_join(kind, seg, p);
+            }
+            joined = zi_pr_public(kind, seg);
+            HIPCHK(hipMemcpyAsync(d_sums + k0, &joined, 4, hipMemcpyHostToDevice, st));
+            HIPCHK(hipStreamSynchronize(st));
+            all = zi_pr_join(kind, all, seg);
+        }
+        f0 = f1;
+    }
+    uint8_t t[8] = { 0 };
+    if (tl) HIPCHK(hipMemcpyAsync(t, d_src + src_len - tl, tl, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (all.len != L || !zi_pr_trailer_ok(format, t, all)) { set_err("the segments' sums do not fold to the stream's trailer (checksum or ISIZE mismatch)"); return ZZ_E_DATA; }
+    return ZZ_OK;
+}
+
+extern "C" int zz_ctx_last_points_windows_stats(const zz_ctx* c, uint64_t* batches, uint64_t* pending_bytes, uint32_t* rounds)
+{
+    if (!c) { set_err("null ctx"); return ZZ_E_ARG; }
+    if (batches) *batches = c->dec.pw.batches;
+    if (pending_bytes) *pending_bytes = c->dec.pw.pending;
+    if (rounds) *rounds = c->dec.pw.rounds;
+    return ZZ_OK;
+}
+
+extern "C" int zz_points_thin(const uint64_t* points, uint64_t entries, uint64_t spacing, uint64_t* out, uint64_t max_entries, uint64_t* out_entries)
+{
+    if (!points || !out_entries) { set_err("null argument"); return ZZ_E_ARG; }
+    *out_entries = 0;
+    if (entries < 2) { set_err("a point index has at least two rows"); return ZZ_E_ARG; }
+    if (spacing == 0) { set_err("spacing must be at least 1"); return ZZ_E_ARG; }
+    *out_entries = zi_points_thin(points, entries, spacing, nullptr, 0);
+    if (!out || max_entries < *out_entries) { set_err("point index buffer too small"); return ZZ_E_NOSPACE; }
+    zi_points_thin(points, entries, spacing, out, max_entries);
     return ZZ_OK;
 }
 

@@ -1312,6 +1312,10 @@ struct zi_in_mem {
 };
 // The builder's block hook: a point at the first block boundary at or behind every multiple of `spacing` decoded bytes (spacing 1:
 // at every block, the empty ones included). Sink: put(in_bit, out_byte), one row.
+// the one thinning rule (zi_pt_record, zi_find_rows, zi_points_thin): a boundary at `bit` with `pos` bytes in front of it becomes a
+// row iff it is the first at or behind `next`; spacing 1 keeps every boundary, the empty blocks' included
+ZZ_HD inline bool zi_points_keep(uint64_t bit, uint64_t pos, uint64_t spacing, uint64_t next) { return !(pos < next && !(spacing == 1 && bit != 0)); }
+ZZ_HD inline uint64_t zi_points_next(uint64_t pos, uint64_t spacing) { return pos - pos % spacing + spacing; }
 template <class Sink> struct zi_pt_record {
     static constexpr bool on = true;
     uint32_t skip; uint64_t stop; bool last; uint64_t end_bit;
@@ -1319,9 +1323,9 @@ template <class Sink> struct zi_pt_record {
     uint64_t spacing, next;        // the next point: the first boundary with at least `next` bytes in front of it
     ZZ_HD void block(uint64_t bit, uint64_t pos)
     {
-        if (pos < next && !(spacing == 1 && bit != 0)) return;
+        if (!zi_points_keep(bit, pos, spacing, next)) return;
         sink->put(bit, pos);
-        next = pos - pos % spacing + spacing;
+        next = zi_points_next(pos, spacing);
     }
 };
 // The whole pass: container header, blocks onto the ring, trailer and checksum -- zi_item's verdict (ZI_ITEM_OK, ZI_ITEM_DATA,
@@ -1543,10 +1547,10 @@ ZZ_HD inline uint64_t zi_find_rows(const zi_find_walk& W, uint64_t spacing, uint
     uint64_t n = 0, pos = 0, next = 0;
     for (uint64_t i = 0; i < W.nacc; ++i) {
         const uint64_t bit = W.acc[2 * i] & ~(1ull << 63);
-        if ((W.acc[2 * i] >> 63) && !(pos < next && !(spacing == 1 && bit != 0))) {
+        if ((W.acc[2 * i] >> 63) && zi_points_keep(bit, pos, spacing, next)) {
             if (rows && n < max_rows) { rows[2 * n] = bit; rows[2 * n + 1] = pos; }
             ++n;
-            next = pos - pos % spacing + spacing;
+            next = zi_points_next(pos, spacing);
         }
         pos += W.acc[2 * i + 1];
     }
@@ -1583,6 +1587,8 @@ ZZ_HD inline zi_pr_part zi_pr_join(int kind, const zi_pr_part& x, const zi_pr_pa
 {
     return zi_pr_part{ kind == ZI_CKS_ADLER ? adler_combine(x.v, y.v, y.len) : crc32_combine(x.v, y.v, y.len), x.len + y.len };
 }
+// a partial as the public value a sidecar holds
+ZZ_HD inline uint32_t zi_pr_public(int kind, const zi_pr_part& p) { return kind == ZI_CKS_ADLER ? adler_combine(1u, p.v, p.len) : p.v; }
 // a sidecar entry of a segment of `len` bytes as a partial; false: no segment of that length has this entry (zi_cks_partial)
 ZZ_HD inline bool zi_pr_entry_part(int kind, uint32_t entry, uint64_t len, zi_pr_part* p)
 {
@@ -1734,6 +1740,64 @@ ZZ_HD inline int zi_points_windows_build(const uint8_t* src, uint64_t src_len, i
     }
     if (all.len != R.out || !zi_pr_trailer_ok(format, view.p + R.end, all)) return ZI_ITEM_DATA;
     return ZI_ITEM_OK;
+}
+
+// ---- the sidecar built on the device (zz_points_windows_device, zz_inflate_points_windows.h; tests/cxx/points_windows_harness.cpp) ----
+// The same sidecar from batches of the point-index decode: a batch of whole sidecar segments is decoded (ZI_RUN_POINT, the rounds)
+// onto a STAGE, and slots and sums are CUT out of it. The stage is `buf`, whose first byte is the absolute output position `org`:
+// without a destination it is ZI_PR_WINDOW carried bytes and then the batch (org = base - ZI_PR_WINDOW, negative inside the first
+// 32 KiB), with one it is the destination (org = 0). The decode kernels get the pointer position 0 would have, so their far-distance
+// check (dist > abs + pos) is the stream's own. A row that thins a finer index (zi_points_thin) is a row of it: the batch is decoded
+// with the finer rows between its ends (zi_points_superset), cut by the sidecar's.
+ZZ_HD inline int64_t zi_pw_org(uint64_t base, bool onto_dst) { return onto_dst ? 0 : (int64_t)base - (int64_t)ZI_PR_WINDOW; }
+// slot k: `zeros` zero bytes, then buf[at, at + ZI_PR_WINDOW - zeros) -- the bytes [out_byte - min(out_byte, 32768), out_byte)
+struct zi_pw_place { uint64_t zeros, at; };
+ZZ_HD inline zi_pw_place zi_pw_slot_place(uint64_t out_byte, int64_t org)
+{
+    const uint64_t have = out_byte < ZI_PR_WINDOW ? out_byte : ZI_PR_WINDOW;
+    return zi_pw_place{ ZI_PR_WINDOW - have, (uint64_t)((int64_t)(out_byte - have) - org) };
+}
+ZZ_HD inline void zi_pw_slot_copy(const zi_view<const uint8_t>& buf, const zi_view<uint8_t>& slot, const zi_pw_place& d, uint32_t lane, uint32_t nl)
+{
+    for (uint64_t j = lane; j < ZI_PR_WINDOW; j += nl) slot[j] = j < d.zeros ? (uint8_t)0 : buf[d.at + (j - d.zeros)];
+}
+// the public sum of the segment [o0, o1) where it lies on the stage; an empty one: 1 (Adler-32) or 0 (CRC-32), which the sums give
+template <class L>
+ZZ_HD uint32_t zi_pw_segment_sum(L& w, int kind, const zi_view<const uint8_t>& buf, int64_t org, uint64_t o0, uint64_t o1, uint32_t lane, uint32_t nl)
+{
+    const uint64_t at = (uint64_t)((int64_t)o0 - org), n = o1 - o0;
+    if (n) { (void)buf[at]; (void)buf[at + n - 1]; }
+    const zi_view<const uint8_t> seg{ buf.p + at, n };
+    return kind == ZI_CKS_ADLER ? zi_adler_lanes(w, seg, n, lane, nl) : zi_crc_lanes(w, seg, n, lane, nl);
+}
+// every row of `points` occurs in `fine` with the same two numbers, the first and the last rows are the same: one merge walk
+ZZ_HD inline bool zi_points_superset(const uint64_t* points, uint64_t entries, const uint64_t* fine, uint64_t fine_entries)
+{
+    if (entries < 2 || fine_entries < entries) return false;
+    if (points[0] != fine[0] || points[1] != fine[1]) return false;
+    if (points[2 * entries - 2] != fine[2 * fine_entries - 2] || points[2 * entries - 1] != fine[2 * fine_entries - 1]) return false;
+    uint64_t f = 0;
+    for (uint64_t k = 0; k < entries; ++k) {
+        while (f < fine_entries && !(fine[2 * f] == points[2 * k] && fine[2 * f + 1] == points[2 * k + 1])) ++f;
+        if (f == fine_entries) return false;
+        ++f;
+    }
+    return true;
+}
+// an index thinned to `spacing` by the builder's rule: row 0, the inner rows zi_points_keep keeps, the last row. Returns the rows;
+// writes them while they fit `max_rows` (out == nullptr: counts)
+ZZ_HD inline uint64_t zi_points_thin(const uint64_t* points, uint64_t entries, uint64_t spacing, uint64_t* out, uint64_t max_rows)
+{
+    uint64_t n = 0, next = 0;
+    for (uint64_t i = 0; i + 1 < entries; ++i) {
+        const uint64_t bit = points[2 * i], pos = points[2 * i + 1];
+        if (i != 0 && !zi_points_keep(bit, pos, spacing, next)) continue;
+        if (out && n < max_rows) { out[2 * n] = bit; out[2 * n + 1] = pos; }
+        ++n;
+        next = zi_points_next(pos, spacing);
+    }
+    if (out && n < max_rows) { out[2 * n] = points[2 * entries - 2]; out[2 * n + 1] = points[2 * entries - 1]; }
+    return n + 1;
 }
 
 }  // namespace zz
