@@ -572,6 +572,7 @@ int zz_ctx_last_decode_members_stats(const zz_ctx* ctx, uint64_t* members, uint6
  *     (as zz_packet_index_device: call with max_entries 0 for the size).
  *   ZZ_E_UNSUPPORTED: the file is not blocked -- no member announces its length, or the chain from offset 0 cannot be walked
  *     (members without `BC`, `cat a.gz b.gz`). Indexing such a file means decoding it, which zz_decode_members_device does.
+ *     zz_members_find_device below makes the same index for such a file by measuring its members in parallel.
  *   ZZ_E_DATA: src_len == 0.
  *   ZZ_E_ARG, before anything is launched: a null context, a null d_src with src_len > 0, a null d_index with max_entries > 0,
  *     null entries, an unfinished zz_encode_device_async on the context.
@@ -580,6 +581,58 @@ int zz_ctx_last_decode_members_stats(const zz_ctx* ctx, uint64_t* members, uint6
 int zz_members_index_device(zz_ctx* ctx, const void* d_src, uint64_t src_len,
                             uint64_t* d_index, uint64_t max_entries,
                             uint64_t* entries, void* hip_stream);
+
+/* The same index for ANY file of gzip members -- `cat a.gz b.gz`, append-mode logs, WARC files, whatever gzip.open(.., "ab")
+ * wrote: members that announce no length, so their ends are found by measuring. The result is defined by the file alone
+ * (DESIGN.md 22):
+ *   candidates  offset 0, and every offset i >= 20 where a gzip header stands that zz_decode_members_device would accept there
+ *               and that leaves ten bytes behind it; the first byte of every member of a valid file is one
+ *   measure     a candidate is decoded as a member WITHOUT WRITING A BYTE: header, blocks through the final one, eight bytes of
+ *               trailer whose ISIZE equals the low 32 bits of the byte count. That gives its length in the file and, exactly,
+ *               its decoded length. CRC-32 and match distances are not judged: there are no bytes yet.
+ *   walk        from offset 0 over the measured lengths. It must reach src_len exactly, over candidates whose measures
+ *               succeeded; candidates it steps over (headers stored inside a member) are dropped.
+ * The index has zz_members_index_device's format and size protocol: members + 1 pairs (file offset, decoded offset), the last
+ * (src_len, L); *entries is set even when max_entries is too small, and the call then returns ZZ_E_NOSPACE and writes nothing.
+ * Unlike that index its decoded offsets are measured, not claimed.
+ *   limit_bytes  a measure that does not start at offset 0 may start anywhere, so it gives up once it has consumed limit_bytes of
+ *     the file; the walk then runs the measures it needs again without a limit (two rounds at most). The result does not depend
+ *     on limit_bytes; only the time does. 0 means ZZ_MEMBERS_FIND_LIMIT_DEFAULT.
+ *   ZZ_OK is not a verdict on checksums: a read through the index (zz_decode_members_ranges_device) or a decode
+ *     (zz_decode_members_found_device) gives that.
+ *   ZZ_E_DATA: the walk breaks -- src_len == 0, a member that cannot be measured (header, blocks, truncation, ISIZE), or a byte
+ *     that is no header behind a trailer.
+ *   ZZ_E_UNSUPPORTED: more than 2^31 - 1 candidates (zz_decode_members_device still decodes such a file).
+ *   ZZ_E_ARG, before anything is launched: a null context, a null d_src with src_len > 0, a null d_index with max_entries > 0,
+ *     null entries, an unfinished zz_encode_device_async on the context.
+ * Cost: one pass over the file at memory bandwidth, then every candidate's blocks decoded once by one wavefront (a member is the
+ * unit: a file of two huge members gains a factor of two and no more). A header field that runs to the next zero byte (FNAME,
+ * FCOMMENT) is followed from every candidate that has one.
+ * Workspace: 12 bytes per 4 KiB of source and 45 bytes per candidate, sized from the count the device reports. Synchronous; the
+ * host reads 32 bytes per candidate and round. Leaves the context's "last call", "last decode" and
+ * zz_ctx_last_decode_members_stats state alone. */
+#define ZZ_MEMBERS_FIND_LIMIT_DEFAULT (1ull << 20)   /* derived, not tuned: the tail limit of the point finder (1 MiB of compressed bytes) -- members of logs, WARC records and 64 KiB blocks end far in front of it, so round 2 is the exception */
+int zz_members_find_device(zz_ctx* ctx, const void* d_src, uint64_t src_len, uint64_t limit_bytes,
+                           uint64_t* d_index, uint64_t max_entries,
+                           uint64_t* entries, void* hip_stream);
+/* zz_decode_members_device for files whose members announce no length: for EVERY input the return value, *out_len and the bytes
+ * are what zi_members defines, that is, what zz_decode_members_device returns; only the speed differs. The members are found as
+ * zz_members_find_device finds them (default limit), then:
+ *   a broken walk          the serial path decides on the whole file
+ *   a clean walk           the members in front of m* -- the first whose bytes pass `cap` -- are decoded as a batch, one wavefront
+ *                          each, into exactly their measured lengths. If all succeed and there is no m*: ZZ_OK, *out_len = L.
+ *                          Otherwise the serial path runs from the first member that did not succeed, or from m*, over what is
+ *                          left of source, destination and room; the members in front of it are proven, and its answer is the
+ *                          call's. A damaged or oversized file is so refused after one member's serial work, not the file's.
+ * Verdicts, ZZ_E_ARG rules, *out_len = ~0 on failure and "nothing is written outside d_dst[0, cap)" are zz_decode_members_device's.
+ * Workspace: zz_members_find_device's and 44 bytes per member. Synchronous. Leaves the context's "last call", "last decode" and
+ * zz_ctx_last_decode_members_stats state alone. */
+int zz_decode_members_found_device(zz_ctx* ctx, const void* d_src, uint64_t src_len, void* d_dst, uint64_t cap,
+                                   uint64_t* out_len, void* hip_stream);
+/* what the last zz_members_find_device or zz_decode_members_found_device did: the members the walk accepted (all of them behind
+ * a clean walk), the candidates, the candidates the walk stepped over, and the rounds of measures (1 or 2; all 0: no call yet, or
+ * refused before anything ran) */
+int zz_ctx_last_members_find_stats(const zz_ctx* ctx, uint64_t* members, uint64_t* candidates, uint64_t* dropped, uint32_t* rounds);
 
 /* Many reads of one blocked gzip (BGZF) file through its index in one call: read r receives the decoded bytes
  * [d_firsts[r], d_firsts[r] + d_nbytes[r]) of the file d_src[0, src_len). d_index / entries are an index as above (from

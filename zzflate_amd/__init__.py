@@ -116,6 +116,9 @@ def _load():
         "zz_decode_members_device": (i32, [vp, vp, u64, vp, u64, pu64, vp]),
         "zz_ctx_last_decode_members_stats": (i32, [vp, pu64, pu64, ctypes.POINTER(i32)]),
         "zz_members_index_device": (i32, [vp, vp, u64, vp, u64, pu64, vp]),
+        "zz_members_find_device": (i32, [vp, vp, u64, u64, vp, u64, pu64, vp]),
+        "zz_decode_members_found_device": (i32, [vp, vp, u64, vp, u64, pu64, vp]),
+        "zz_ctx_last_members_find_stats": (i32, [vp, pu64, pu64, pu64, ctypes.POINTER(u32)]),
         "zz_decode_members_ranges_device": (i32, [vp, vp, u64, vp, u64, u64, vp, vp, vp, vp, vp, vp, vp]),
         "zz_ctx_last_decode_members_ranges_stats": (i32, [vp, pu64, ctypes.POINTER(u32)]),
         "zz_points_windows_host": (i32, [vp, u64, i32, vp, u64, vp, vp]),
@@ -957,6 +960,52 @@ class Context:
         idx = torch.empty((entries.value, 2), dtype=torch.int64, device=f"cuda:{self.device}")
         _check(lib.zz_members_index_device(self._h, self._ptr(src), src_len, idx.data_ptr(), entries.value, ctypes.byref(entries), st))
         return idx
+
+    def members_find(self, src, limit_bytes=0, src_len=None, stream=None):
+        """The index of ANY file of gzip members ``src`` (a uint8 tensor on this context's device; ``src_len`` defaults to its
+        length) -- ``cat a.gz b.gz``, append-mode logs, WARC: members that announce no length. Every place where a gzip header
+        stands is measured as a member without writing a byte, in parallel, and the chain from offset 0 picks the members.
+        Returns ``members_index``'s tensor, ``[members + 1, 2]`` int64 on this context's device, with measured decoded offsets;
+        ``decode_members_ranges`` reads through it. ``limit_bytes`` (0: 1 MiB) bounds what a false start may cost before it is
+        given up; the result does not depend on it. Checksums are not judged here: a read or a decode does that. Raises
+        ZzFlateError (E_DATA: the file is no chain of members, or empty)."""
+        import torch
+        n = src.numel() if src_len is None else src_len
+        entries = ctypes.c_uint64(0)
+        st = self._stream() if stream is None else stream
+        rc = lib.zz_members_find_device(self._h, self._ptr(src), n, limit_bytes, None, 0, ctypes.byref(entries), st)
+        if rc != E_NOSPACE:
+            _check(rc)
+        idx = torch.empty((entries.value, 2), dtype=torch.int64, device=f"cuda:{self.device}")
+        _check(lib.zz_members_find_device(self._h, self._ptr(src), n, limit_bytes, idx.data_ptr(), entries.value, ctypes.byref(entries), st))
+        return idx
+
+    def decode_members_found(self, src, cap=None, src_len=None, dst=None, stream=None):
+        """``decode_members`` for files whose members announce no length: the members are found as ``members_find`` finds them
+        and decoded in parallel, one wavefront each. The verdict and the bytes are ``decode_members``' for every input; only the
+        speed differs. Returns the decoded bytes, a uint8 tensor on this context's device: a view of ``dst`` (``cap`` defaults to
+        its length) when that is given, else of a new tensor of ``cap`` bytes -- ``cap=None`` measures the file first
+        (``members_find``) and takes its decoded length. Raises ZzFlateError (E_DATA, E_NOSPACE) as ``decode_members`` does."""
+        import torch
+        n = src.numel() if src_len is None else src_len
+        if dst is not None:
+            if not isinstance(dst, torch.Tensor) or dst.dtype != torch.uint8 or not dst.is_contiguous():
+                raise TypeError("dst must be a contiguous uint8 tensor")
+            cap = dst.numel() if cap is None else cap
+        else:
+            if cap is None:
+                cap = int(self.members_find(src, 0, n, stream)[-1, 1])
+            dst = torch.empty(cap, dtype=torch.uint8, device=f"cuda:{self.device}")
+        out = ctypes.c_uint64(0)
+        st = self._stream() if stream is None else stream
+        _check(lib.zz_decode_members_found_device(self._h, self._ptr(src), n, dst.data_ptr(), cap, ctypes.byref(out), st))
+        return dst[:out.value]
+
+    def last_members_find_stats(self):
+        """(members, candidates, dropped candidates, rounds) of the last ``members_find`` or ``decode_members_found``."""
+        m, cand, dropped, rounds = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint32(0)
+        _check(lib.zz_ctx_last_members_find_stats(self._h, ctypes.byref(m), ctypes.byref(cand), ctypes.byref(dropped), ctypes.byref(rounds)))
+        return m.value, cand.value, dropped.value, rounds.value
 
     def _reads(self, call, firsts, nbytes, dsts, caps, stream):
         """the read arrays of decode_members_ranges and decode_points_ranges on the device, the call, and (lens, status) back"""

@@ -35,6 +35,7 @@
 #include "zz_inflate_points.h"
 #include "zz_inflate_points_find.h"
 #include "zz_inflate_members.h"
+#include "zz_inflate_members_find.h"
 #include "zz_inflate_members_ranges.h"
 #include "zz_inflate_points_ranges.h"
 #include "zz_inflate_points_windows.h"
@@ -194,6 +195,15 @@ struct zz_ctx {
             zz_buf<zz_inf_members_out> sres; zz_pin<zz_inf_members_out> h_sres;
             uint64_t members = 0, candidates = 0; int path = 0;
         } mem;
+        // zz_members_find_device, zz_decode_members_found_device (zz_inflate_members_find.h): per candidate its record, its flag
+        // and (round 2) its number, the dealing counter, the dealt members' statuses, what the host reads behind the slots, and what
+        // the last call did; the mark pass's buffers, the descriptors and the serial path's result are mem's
+        struct {
+            zz_buf<zi_find_job> rec; zz_buf<uint8_t> keep; zz_buf<uint32_t> which; zz_buf<unsigned int> next;
+            zz_buf<int32_t> status;
+            zz_buf<zz_mf_state> st; zz_pin<zz_mf_state> h_st;
+            uint64_t members = 0, candidates = 0, dropped = 0; uint32_t rounds = 0;
+        } mf;
         // the reads through an index (dec_reads; zz_inflate_members_ranges.h): the stage, per read (record, chunk scan), per unit
         // (differences, counts), per touched unit (list, S, F, G), per unit of a wave its status, per wave two words, what the
         // host reads; a wave's rooms and lengths (and k_inflate_items' descriptors) are mem's
@@ -2596,11 +2606,8 @@ extern "C" int zz_decode_batch_device(zz_ctx* c, uint64_t nitems, const void* co
 }
 
 // ---- a file of gzip members back to back (zz_inflate_members.h) -----------------------------------------------------------
-// the serial path: zi_members by one wavefront; it decides every verdict the blocked path does not. `members0` proven members
-// and `out0` bytes of theirs stand in front of src (0 and 0: the whole file); `path` is what the call reports if this succeeds
-// or answers "no space"
-static int dec_members_serial(zz_ctx* c, const uint8_t* src, uint64_t n, uint8_t* dst, uint64_t cap, hipStream_t st, uint64_t* out_len,
-                              uint64_t members0, uint64_t out0, int path)
+// k_inflate_members over src[0, n) onto dst[0, cap), waited for
+static int members_serial_run(zz_ctx* c, const uint8_t* src, uint64_t n, uint8_t* dst, uint64_t cap, hipStream_t st)      // (the result: mem.h_sres)
 {
     auto& M = c->dec.mem;
     if (int rc = M.sres.grow(1)) return rc;
@@ -2609,6 +2616,16 @@ static int dec_members_serial(zz_ctx* c, const uint8_t* src, uint64_t n, uint8_t
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(M.h_sres, M.sres, sizeof(zz_inf_members_out), hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
+    return ZZ_OK;
+}
+// the serial path: zi_members by one wavefront; it decides every verdict the blocked path does not. `members0` proven members
+// and `out0` bytes of theirs stand in front of src (0 and 0: the whole file); `path` is what the call reports if this succeeds
+// or answers "no space"
+static int dec_members_serial(zz_ctx* c, const uint8_t* src, uint64_t n, uint8_t* dst, uint64_t cap, hipStream_t st, uint64_t* out_len,
+                              uint64_t members0, uint64_t out0, int path)
+{
+    auto& M = c->dec.mem;
+    if (int rc = members_serial_run(c, src, n, dst, cap, st)) return rc;
     M.members = members0 + M.h_sres->members;
     M.path = path;
     if (M.h_sres->status == ZI_ITEM_OK) { *out_len = out0 + M.h_sres->out; return ZZ_OK; }
@@ -2757,6 +2774,201 @@ extern "C" int zz_members_index_device(zz_ctx* c, const void* d_src_v, uint64_t 
                        members, d_index);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(st));
+    return ZZ_OK;
+}
+
+// ---- the members of any member file, found (zz_inflate_members_find.h; the rules in zz_inflate_core.h) ---------------------------
+// one round of measures: one launch, the records back (all of them: a round's jobs write into the candidates' own records)
+static int mf_run_round(zz_ctx* c, const uint8_t* src, uint64_t n, uint64_t ncand, const uint32_t* h_which, uint64_t njobs, uint64_t limit,
+                        std::vector<zi_find_job>& rec, hipStream_t st)
+{
+    auto& F = c->dec.mf;
+    if (h_which) HIPCHK(hipMemcpyAsync(F.which, h_which, njobs * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemsetAsync(F.next, 0, sizeof(unsigned int), st));
+    zz_mf_params Q = {};
+    Q.src = src; Q.n = n; Q.offs = c->dec.mem.offs; Q.rec = F.rec; Q.which = h_which ? (const uint32_t*)F.which : nullptr;
+    Q.njobs = (uint32_t)njobs; Q.limit = limit; Q.next = F.next;
+    const uint64_t resident = 256ull * ZZ_MF_WG_PER_CU;
+    hipLaunchKernelGGL(k_members_reach, dim3((uint32_t)(njobs < resident ? njobs : resident)), dim3(ZZ_INF_THREADS), 0, st, Q);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(rec.data(), F.rec, ncand * sizeof(zi_find_job), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    ++F.rounds;
+    return ZZ_OK;
+}
+// The front of both calls: mark (count per stretch, scan, one readback that sizes everything by the candidates), fill, the
+// measures of round 1, the walk, round 2 where the walk met a job that gave up, the walk again. *walk: ZI_MF_CLEAN or
+// ZI_MF_BROKEN, or -1: more than one launch's grid holds (stretches or candidates above 2^31 - 1). Behind a clean walk rec (on
+// the host and in mf.rec) and keep (on the host) describe the members, and the call's stats are set.
+static int mf_front(zz_ctx* c, const uint8_t* src, uint64_t src_len, uint64_t limit_bytes, hipStream_t st, std::vector<zi_find_job>& rec,
+                    std::vector<uint8_t>& keep, int* walk)
+{
+    auto& M = c->dec.mem;
+    auto& F = c->dec.mf;
+    *walk = -1;
+    const uint64_t nblk = (src_len + ZZ_MEM_STRETCH - 1) / ZZ_MEM_STRETCH;
+    if (nblk > 0x7FFFFFFFull) return ZZ_OK;                              // (8 TiB of source)
+    if (int rc = M.blk_cnt.grow(nblk)) return rc;
+    if (int rc = M.blk_base.grow(nblk)) return rc;
+    if (int rc = M.st.grow(1)) return rc;
+    if (int rc = M.h_st.grow(1)) return rc;
+    HIPCHK(hipMemsetAsync(M.st, 0, sizeof(zz_mem_state), st));
+    hipLaunchKernelGGL(k_members_find_mark<false>, dim3((uint32_t)nblk), dim3(ZZ_MEM_THREADS), 0, st, src, src_len, (uint32_t*)M.blk_cnt,
+                       (const uint64_t*)nullptr, (uint64_t*)nullptr);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(k_members_scan, dim3(1), dim3(ZZ_MEM_SCAN_THREADS), 0, st, (const uint32_t*)M.blk_cnt, nblk, (uint64_t*)M.blk_base,
+                       (zz_mem_state*)M.st);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(M.h_st, M.st, sizeof(zz_mem_state), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    const uint64_t ncand = M.h_st->candidates;                            // (at least one: offset 0)
+    F.candidates = ncand;
+    if (ncand == 0 || ncand > 0x7FFFFFFFull) return ZZ_OK;
+    if (int rc = M.offs.grow(ncand)) return rc;
+    if (int rc = F.rec.grow(ncand)) return rc;
+    if (int rc = F.keep.grow(ncand)) return rc;
+    if (int rc = F.which.grow(ncand)) return rc;
+    if (int rc = F.next.grow(1)) return rc;
+    hipLaunchKernelGGL(k_members_find_mark<true>, dim3((uint32_t)nblk), dim3(ZZ_MEM_THREADS), 0, st, src, src_len, (uint32_t*)M.blk_cnt,
+                       (const uint64_t*)M.blk_base, (uint64_t*)M.offs);
+    HIPCHK(hipGetLastError());
+    rec.resize(ncand); keep.assign(ncand, 0);
+    if (int rc = mf_run_round(c, src, src_len, ncand, nullptr, ncand, limit_bytes, rec, st)) return rc;
+    zi_mf_walk W{ 0, 0, 0, 0 };
+    const zi_view<const zi_find_job> recs{ rec.data(), ncand };
+    int v = zi_mf_link(W, recs, ncand, src_len, zi_view<uint8_t>{ keep.data(), ncand });
+    if (v == ZI_MF_MORE) {
+        std::vector<uint32_t> which(zi_mf_again(W, recs, ncand, nullptr));
+        zi_mf_again(W, recs, ncand, which.data());
+        if (int rc = mf_run_round(c, src, src_len, ncand, which.data(), which.size(), ZI_FIND_NONE, rec, st)) return rc;
+        v = zi_mf_link(W, recs, ncand, src_len, zi_view<uint8_t>{ keep.data(), ncand });
+        if (v == ZI_MF_MORE) v = ZI_MF_BROKEN;                            // (a job without a limit does not give up)
+    }
+    F.members = W.members; F.dropped = W.dropped;
+    *walk = v;
+    return ZZ_OK;
+}
+// the slots behind a clean walk: the flags up, one launch, mf.h_st back. The descriptors go to mem's arrays when `dst_side` is set,
+// the index rows to d_index when it is not null
+static int mf_slots(zz_ctx* c, const uint8_t* src, uint64_t src_len, uint8_t* dst, uint64_t cap, bool dst_side, uint64_t* d_index,
+                    const std::vector<uint8_t>& keep, hipStream_t st)
+{
+    auto& M = c->dec.mem;
+    auto& F = c->dec.mf;
+    if (int rc = F.st.grow(1)) return rc;
+    if (int rc = F.h_st.grow(1)) return rc;
+    HIPCHK(hipMemcpyAsync(F.keep, keep.data(), keep.size(), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemsetAsync(F.st, 0, sizeof(zz_mf_state), st));
+    HIPCHK(hipMemsetAsync(&F.st->mstar, 0xFF, sizeof(unsigned long long), st));
+    zz_mf_slots q = {};
+    q.src = src; q.n = src_len; q.dst = dst; q.cap = cap; q.rec = F.rec; q.keep = F.keep; q.nc = keep.size();
+    if (dst_side) { q.srcs = M.srcs; q.src_lens = M.src_lens; q.dsts = M.dsts; q.caps = M.caps; }
+    q.idx = d_index; q.st = F.st;
+    hipLaunchKernelGGL(k_members_find_slots, dim3(1), dim3(ZZ_MEM_SCAN_THREADS), 0, st, q);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(F.h_st, F.st, sizeof(zz_mf_state), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return ZZ_OK;
+}
+
+extern "C" int zz_members_find_device(zz_ctx* c, const void* d_src_v, uint64_t src_len, uint64_t limit_bytes, uint64_t* d_index,
+                                      uint64_t max_entries, uint64_t* entries, void* hip_stream)
+{
+    if (entries) *entries = 0;
+    if (!c) { set_err("null ctx"); return ZZ_E_ARG; }
+    if (!entries) { set_err("null entries"); return ZZ_E_ARG; }
+    if (!d_src_v && src_len) { set_err("null source"); return ZZ_E_ARG; }
+    if (!d_index && max_entries) { set_err("null index"); return ZZ_E_ARG; }
+    if (call_pending(c)) return ZZ_E_ARG;
+    auto& F = c->dec.mf;
+    F.members = 0; F.candidates = 0; F.dropped = 0; F.rounds = 0;
+    if (src_len == 0) { set_err("an empty file holds no gzip member"); return ZZ_E_DATA; }
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t st = (hipStream_t)hip_stream;
+    const uint8_t* src = (const uint8_t*)d_src_v;
+    std::vector<zi_find_job> rec; std::vector<uint8_t> keep;
+    int walk = -1;
+    if (int rc = mf_front(c, src, src_len, limit_bytes ? limit_bytes : ZZ_MEMBERS_FIND_LIMIT_DEFAULT, st, rec, keep, &walk)) return rc;
+    if (walk < 0) { set_err("more than 2^31 - 1 places where a gzip header stands: zz_decode_members_device decodes such a file"); return ZZ_E_UNSUPPORTED; }
+    if (walk != ZI_MF_CLEAN) {
+        set_err("not a file of gzip members: the chain from offset 0 breaks behind member " + std::to_string(F.members));
+        return ZZ_E_DATA;
+    }
+    *entries = F.members + 1;
+    if (max_entries < F.members + 1) { set_err("the index has " + std::to_string(F.members + 1) + " entries"); return ZZ_E_NOSPACE; }
+    return mf_slots(c, src, src_len, nullptr, 0, false, d_index, keep, st);
+}
+
+extern "C" int zz_decode_members_found_device(zz_ctx* c, const void* d_src_v, uint64_t src_len, void* d_dst_v, uint64_t cap, uint64_t* out_len,
+                                              void* hip_stream)
+{
+    if (out_len) *out_len = ~0ull;
+    if (!c) { set_err("null ctx"); return ZZ_E_ARG; }
+    if (!out_len) { set_err("null out_len"); return ZZ_E_ARG; }
+    if (!d_src_v && src_len) { set_err("null source"); return ZZ_E_ARG; }
+    if (!d_dst_v && cap) { set_err("null destination"); return ZZ_E_ARG; }
+    if (call_pending(c)) return ZZ_E_ARG;
+    auto& M = c->dec.mem;
+    auto& F = c->dec.mf;
+    F.members = 0; F.candidates = 0; F.dropped = 0; F.rounds = 0;
+    if (src_len == 0) { set_err("an empty file holds no gzip member"); return ZZ_E_DATA; }
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t st = (hipStream_t)hip_stream;
+    const uint8_t* src = (const uint8_t*)d_src_v;
+    uint8_t* dst = (uint8_t*)d_dst_v;
+    // zi_members over what is left behind `members0` proven members (`at` source bytes, `off` decoded bytes): its answer is the call's
+    const auto serial = [&](uint64_t members0, uint64_t at, uint64_t off) -> int {
+        if (int rc = members_serial_run(c, src + at, src_len - at, dst + off, cap - off, st)) return rc;
+        const zz_inf_members_out& R = *M.h_sres;
+        const uint64_t member = members0 + R.members;
+        if (R.status == ZI_ITEM_OK) { *out_len = off + R.out; return ZZ_OK; }
+        if (R.status == ZI_ITEM_NOSPACE) { set_err("member " + std::to_string(member) + " does not fit what is left of the destination"); return ZZ_E_NOSPACE; }
+        set_err("what stands where member " + std::to_string(member) + " would begin is not a valid gzip member");
+        return ZZ_E_DATA;
+    };
+
+    std::vector<zi_find_job> rec; std::vector<uint8_t> keep;
+    int walk = -1;
+    if (int rc = mf_front(c, src, src_len, ZZ_MEMBERS_FIND_LIMIT_DEFAULT, st, rec, keep, &walk)) return rc;
+    if (walk != ZI_MF_CLEAN) return serial(0, 0, 0);                     // a broken walk, or too many candidates: the whole file
+    if (int rc = ensure_member_items(c, F.members)) return rc;
+    if (int rc = F.status.grow(F.members)) return rc;
+    if (int rc = mf_slots(c, src, src_len, dst, cap, true, nullptr, keep, st)) return rc;
+    const uint64_t members = F.h_st->members, mstar = F.h_st->mstar;
+    const bool have_mstar = mstar != ~0ull;
+    const uint64_t dealt = have_mstar ? mstar : members;
+
+    // decode: k_inflate_items over the members in front of m*, as zz_decode_batch_device launches it
+    unsigned long long failed = 0;
+    if (dealt) {
+        if (int rc = dec_items(c, member_items_params(c, (uint32_t)dealt, F.status), st)) return rc;
+        failed = c->dec.items_host[0] + c->dec.items_host[1];
+    }
+    if (!failed && !have_mstar) { *out_len = F.h_st->total; return ZZ_OK; }
+    // the first member that did not answer ZZ_OK, or m*: the members in front of it are proven, zi_members decides from there on
+    uint64_t first = dealt, at = F.h_st->mstar_src, off = F.h_st->mstar_dst;
+    if (failed) {
+        std::vector<int32_t> status(dealt);
+        HIPCHK(hipMemcpyAsync(status.data(), F.status, dealt * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        uint64_t j = 0, sum = 0;
+        for (uint64_t k = 0; k < keep.size(); ++k) {
+            if (!keep[k]) continue;
+            if (j >= dealt) break;
+            if (status[j] != ZI_ITEM_OK) { first = j; at = rec[k].a; off = sum; break; }
+            sum += rec[k].c; ++j;
+        }
+    }
+    return serial(first, at, off);
+}
+
+extern "C" int zz_ctx_last_members_find_stats(const zz_ctx* c, uint64_t* members, uint64_t* candidates, uint64_t* dropped, uint32_t* rounds)
+{
+    if (!c) { set_err("null ctx"); return ZZ_E_ARG; }
+    if (members) *members = c->dec.mf.members;
+    if (candidates) *candidates = c->dec.mf.candidates;
+    if (dropped) *dropped = c->dec.mf.dropped;
+    if (rounds) *rounds = c->dec.mf.rounds;
     return ZZ_OK;
 }
 

@@ -1800,4 +1800,93 @@ ZZ_HD inline uint64_t zi_points_thin(const uint64_t* points, uint64_t entries, u
     return n + 1;
 }
 
+// ---- the members of any member file found in parallel (zz_members_find_device, zz_decode_members_found_device,
+// zz_inflate_members_find.h; tests/cxx/members_find_harness.cpp) ------------------------------------------------------------------
+// A member without `BC` says nothing about its length, so its successor is FOUND instead of reached: every place where a gzip
+// header stands is a candidate, every candidate is MEASURED as a member (decoded without writing a byte), and the chain from
+// offset 0 over the measured lengths picks the members. The result is defined by the file alone:
+//   CANDIDATES  offset 0, and every offset i >= 20 (no member is shorter: ten bytes of header, two of blocks, eight of trailer)
+//               with hl = zi_header(gzip, src + i, src_len - i) >= 0 and i + hl + 10 <= src_len; ascending. That is what zi_member
+//               accepts as a header, so the start of every member of a valid file is a candidate: the chain below never needs a
+//               start that was not found (no gaps and no repair jobs, unlike the point finder above).
+//   MEASURE     candidate c: the header, then the blocks through the final one by ZI_RUN_REACH onto zi_out_count (stop ~0), then
+//               eight bytes of trailer inside the file whose ISIZE equals the count's low 32 bits. OK gives `used` (header, blocks
+//               and trailer) and `out` (the count, 64 bits). CRC-32 and distances cannot be judged: no byte exists yet.
+//   WALK        from stop 0: an OK measure at a stop moves it by `used`; stop == src_len ends the walk CLEAN; a stop that is no
+//               candidate, a measure that is not OK, or src_len == 0 makes it BROKEN. Candidates the walk steps over are dropped.
+// A measure from a false start decodes garbage, so in round 1 every job but job 0 (offset 0 is on the chain) carries a limit: it
+// gives up once it has consumed `limit` bytes from its start. A limited job answers what the unlimited one would, or GAVEUP; the
+// walk stops at a job that gave up, round 2 runs every job that gave up at or behind that stop again without a limit, and the walk
+// then meets no GAVEUP any more: two rounds at most, and what the walk reads -- OK or not, `used`, `out` -- never depends on the
+// limit, the rounds or the order the jobs ran in.
+ZZ_HD inline bool zi_mf_candidate(const uint8_t* src, uint64_t src_len, uint64_t i)
+{
+    if (i == 0) return src_len != 0;
+    if (i < 20 || i >= src_len) return false;
+    const int64_t hl = zi_header(1, src + i, src_len - i);
+    return hl >= 0 && i + (uint64_t)hl + 10 <= src_len;
+}
+// A job's record (zi_find_job, in place): in a = the candidate, c = the limit in bytes from it (ZI_FIND_NONE: none);
+// out a = the candidate, b = used, c = out, flags = exactly one of ZI_FJ_OK, ZI_FJ_GAVEUP, ZI_FJ_ERROR.
+ZZ_HD inline uint64_t zi_mf_limit(uint64_t k, uint64_t limit_bytes) { return k ? limit_bytes : ZI_FIND_NONE; }
+template <class L>
+ZZ_HD zi_find_job zi_mf_measure(L& w, const uint8_t* src, uint64_t src_len, const zi_find_job& j, zi_tables& S, uint32_t lane, uint32_t nl)
+{
+    zi_find_job r{ j.a, 0, 0, ZI_FJ_ERROR, 0 };
+    if (j.a >= src_len) return r;
+    const int64_t hl = zi_header(1, src + j.a, src_len - j.a);
+    if (hl < 0) return r;
+    const zi_view<const uint8_t> view{ src + j.a + hl, src_len - j.a - (uint64_t)hl };   // the blocks, the trailer and what follows
+    typename L::in_t in = w.input(view.p, view.n);
+    zi_out_count o{ 0 };
+    const uint64_t limit = j.c == ZI_FIND_NONE || j.c > (~0ull >> 3) ? ZI_FIND_NONE : 8 * (j.c > (uint64_t)hl ? j.c - (uint64_t)hl : 0);
+    zi_pt_reach pt{ 0, ZI_FIND_NONE, false, 0, limit };
+    S.kind = 0;
+    const zi_result R = zi_run(in, view, 0, o, S, ZI_RUN_REACH, 0, lane, nl, pt);
+    if (R.err == ZI_E_GAVEUP) { r.flags = ZI_FJ_GAVEUP; return r; }
+    if (R.err || !R.final) return r;
+    if (R.end > view.n || view.n - R.end < 8) return r;                       // truncated trailer
+    const zi_view<const uint8_t> t{ view.p + R.end, 8 };
+    const uint32_t l = t[4] | ((uint32_t)t[5] << 8) | ((uint32_t)t[6] << 16) | ((uint32_t)t[7] << 24);
+    if (l != (uint32_t)R.out) return r;
+    r.b = (uint64_t)hl + R.end + 8; r.c = R.out; r.flags = ZI_FJ_OK;
+    return r;
+}
+// The walk over the candidates' records rec[0, nc) (rec[k].a ascending). keep[0, nc) is zero on entry; the walk sets keep[k] for
+// the members. It can be called again with the same W after a round: it goes on from its stop.
+enum { ZI_MF_MORE = 0,        // the job at the stop gave up: run zi_mf_again's jobs without a limit, then link again
+       ZI_MF_CLEAN = 1,       // the chain reached src_len: `members` members, the other candidates dropped
+       ZI_MF_BROKEN = 2 };
+struct zi_mf_walk {
+    uint64_t pos, k;          // the stop; the first candidate that is not in front of it
+    uint64_t members, dropped;
+};
+ZZ_HD inline int zi_mf_link(zi_mf_walk& W, const zi_view<const zi_find_job>& rec, uint64_t nc, uint64_t src_len, zi_view<uint8_t> keep)
+{
+    if (src_len == 0) return ZI_MF_BROKEN;
+    for (;;) {
+        while (W.k < nc && rec[W.k].a < W.pos) { ++W.k; ++W.dropped; }
+        if (W.k >= nc || rec[W.k].a != W.pos) return ZI_MF_BROKEN;
+        const zi_find_job& R = rec[W.k];
+        if (R.flags & ZI_FJ_GAVEUP) return ZI_MF_MORE;
+        if (!(R.flags & ZI_FJ_OK) || R.b == 0 || R.b > src_len - W.pos) return ZI_MF_BROKEN;
+        keep[W.k] = 1; ++W.members; ++W.k;
+        W.pos += R.b;
+        if (W.pos == src_len) { W.dropped += nc - W.k; return ZI_MF_CLEAN; }
+    }
+}
+// the jobs of round 2: every candidate at or behind the stop whose job gave up. Returns their number; which == nullptr: counts.
+ZZ_HD inline uint64_t zi_mf_again(const zi_mf_walk& W, const zi_view<const zi_find_job>& rec, uint64_t nc, uint32_t* which)
+{
+    uint64_t n = 0;
+    for (uint64_t k = W.k; k < nc; ++k) if (rec[k].flags & ZI_FJ_GAVEUP) { if (which) which[n] = (uint32_t)k; ++n; }
+    return n;
+}
+// SLOTS of a clean walk: member j (the j-th kept candidate) begins `off` = the sum of `out` in front of it into the destination and
+// gets exactly `out` bytes of room: its count is measured, not claimed. m* is the first member with off + out > cap; the members in
+// front of it are dealt to zi_item, and zi_members from m* on gives the verdict. off + out never shrinks, so m* is the one member
+// that begins inside cap and ends behind it.
+ZZ_HD inline bool zi_mf_dealt(uint64_t out, uint64_t off, uint64_t cap) { return off <= cap && out <= cap - off; }
+ZZ_HD inline bool zi_mf_is_mstar(uint64_t out, uint64_t off, uint64_t cap) { return off <= cap && out > cap - off; }
+
 }  // namespace zz
