@@ -634,6 +634,49 @@ int zz_decode_members_found_device(zz_ctx* ctx, const void* d_src, uint64_t src_
  * refused before anything ran) */
 int zz_ctx_last_members_find_stats(const zz_ctx* ctx, uint64_t* members, uint64_t* candidates, uint64_t* dropped, uint32_t* rounds);
 
+/* Points INSIDE members: one index over the members of any file of gzip members and the blocks inside them, the
+ * cuts a decode of a file of few large members -- `cat lane1.fq.gz lane2.fq.gz`, rotated logs joined with cat -- needs to use many
+ * wavefronts per member (that decode is not part of the library yet: DESIGN.md 23). The
+ * result is defined by the file F, chunk_bytes C and spacing alone; bits count from F's first byte:
+ *   header candidates  zz_members_find_device's: offset 0, and every offset i >= 20 where a gzip header stands with ten bytes
+ *                      left behind it
+ *   block candidates   zz_points_index_device's with D = F: for every chunk c >= 1 the lowest bit where a non-final dynamic block
+ *                      header stands that a decoder would accept, no bit of it behind F
+ *   jobs               one per candidate, measured WITHOUT WRITING A BYTE: a header job parses its header and counts from the
+ *                      member's first block bit, a block job from its bit, to the first block boundary at or behind the lowest
+ *                      block candidate above its first bit, or through a final block -- whose member's ISIZE it then reads
+ *   walk               from offset 0: a header candidate whose job succeeded opens a member; a block boundary that is a block
+ *                      candidate continues it with that candidate's job (an inner row), any other with a repair job; a job that
+ *                      ends with a final block closes the member, whose ISIZE must equal the low 32 bits of its count, and the
+ *                      next member begins behind its trailer -- at src_len the walk is done. Candidates the walk steps over are
+ *                      dropped; a block candidate that is a member's first block bit is neither a row nor dropped.
+ * The index is `entries` rows (in_bit, out_byte) in HOST memory. Member j contributes a START row (the bit of its first block |
+ * ZZ_MP_START, the decoded bytes in front of it), its inner rows (bit, decoded bytes in front of the bit), and an END row (the bit
+ * behind its final block | ZZ_MP_END, the decoded bytes in front of member j + 1); the last row's out_byte is L = *out_len.
+ * spacing > 1 thins inner rows only, by zz_points_index_host's rule on file-absolute decoded positions, starting again at every
+ * START row. *entries and *out_len are set even when max_entries is too small: the call then returns ZZ_E_NOSPACE and writes
+ * nothing (2 * (src_len / 20 + 1) + src_len / chunk_bytes rows always suffice).
+ *   ZZ_OK is not a verdict on CRC-32 or match distances: no byte is produced (zz_decode_members_device gives the verdict).
+ *   ZZ_E_DATA: the walk breaks -- src_len == 0, a job of the walk in error, an ISIZE mismatch, a byte behind a trailer that is no
+ *     header, truncation.
+ *   ZZ_E_UNSUPPORTED: more than 2^31 - 1 candidates of either kind.
+ *   ZZ_E_ARG, before anything is launched: a null context, entries or out_len, a null d_src with src_len > 0, null points with
+ *     max_entries > 0, chunk_bytes < 16, spacing < 1, src_len >= 2^61, an unfinished zz_encode_device_async on the context.
+ * Synchronous; the host reads 40 bytes per job and round and walks them. Leaves the context's "last call", "last decode" and the
+ * other calls' stats alone. */
+#define ZZ_MP_START (1ull << 63)
+#define ZZ_MP_END (1ull << 62)
+int zz_members_points_device(zz_ctx* ctx, const void* d_src, uint64_t src_len, uint64_t chunk_bytes, uint64_t spacing,
+                             uint64_t* points, uint64_t max_entries, uint64_t* entries, uint64_t* out_len, void* hip_stream);
+/* what the last zz_members_points_device did: the members the walk accepted, the candidates of either kind, the candidates the
+ * walk stepped over, and the rounds of jobs (all 0: no call yet, or refused before anything ran) */
+int zz_ctx_last_members_points_stats(const zz_ctx* ctx, uint64_t* members, uint64_t* header_candidates, uint64_t* block_candidates,
+                                     uint64_t* dropped, uint32_t* rounds);
+/* Host only: the START / END rows of a member point index as zz_members_find_device's pairs (file offset, decoded offset), members
+ * + 1 of them, so that zz_decode_members_ranges_device reads such files too (`index` in host memory: copy it to the device).
+ * Size protocol as above. ZZ_E_DATA: the rows are not START, inner rows, END per member. */
+int zz_members_points_to_index(const uint64_t* points, uint64_t entries, uint64_t* index, uint64_t max_entries, uint64_t* index_entries);
+
 /* Many reads of one blocked gzip (BGZF) file through its index in one call: read r receives the decoded bytes
  * [d_firsts[r], d_firsts[r] + d_nbytes[r]) of the file d_src[0, src_len). d_index / entries are an index as above (from
  * zz_members_index_device, from zz_encode_members_device's offsets, or from a .gzi file); the six arrays of nranges entries live

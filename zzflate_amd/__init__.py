@@ -19,6 +19,7 @@ __all__ = [
     "crc32", "crc32_combine", "bound", "Context", "lib", "DEFAULT_PACKET", "generate_host", "header", "trailer",
     "MEMBERS_BLOCK", "members_bound", "members_header", "gzi_bytes", "packet_checksums_host",
     "POINTS_CHUNK", "points_index_bound", "points_thin",
+    "MP_START", "MP_END", "members_index_from_points",
 ]
 
 DEFAULT_PACKET = 32768
@@ -119,6 +120,9 @@ def _load():
         "zz_members_find_device": (i32, [vp, vp, u64, u64, vp, u64, pu64, vp]),
         "zz_decode_members_found_device": (i32, [vp, vp, u64, vp, u64, pu64, vp]),
         "zz_ctx_last_members_find_stats": (i32, [vp, pu64, pu64, pu64, ctypes.POINTER(u32)]),
+        "zz_members_points_device": (i32, [vp, vp, u64, u64, u64, vp, u64, pu64, pu64, vp]),
+        "zz_ctx_last_members_points_stats": (i32, [vp, pu64, pu64, pu64, pu64, ctypes.POINTER(u32)]),
+        "zz_members_points_to_index": (i32, [vp, u64, vp, u64, pu64]),
         "zz_decode_members_ranges_device": (i32, [vp, vp, u64, vp, u64, u64, vp, vp, vp, vp, vp, vp, vp]),
         "zz_ctx_last_decode_members_ranges_stats": (i32, [vp, pu64, ctypes.POINTER(u32)]),
         "zz_points_windows_host": (i32, [vp, u64, i32, vp, u64, vp, vp]),
@@ -331,6 +335,23 @@ def points_thin(points, spacing):
     out = torch.zeros((points.shape[0], 2), dtype=torch.int64)
     entries = ctypes.c_uint64(0)
     _check(lib.zz_points_thin(points.data_ptr(), points.shape[0], spacing, out.data_ptr(), out.shape[0], ctypes.byref(entries)))
+    return out[: entries.value].clone()
+
+
+MP_START = 1 << 63                                      # ZZ_MP_START, ZZ_MP_END: the flags in a member point index's in_bit
+MP_END = 1 << 62                                        # (an int64 tensor holds a START row's in_bit as a negative number)
+
+
+def members_index_from_points(points):
+    """The index ``Context.decode_members_ranges`` takes -- ``members_find``'s pairs (file offset, decoded offset), members + 1 of
+    them -- from the START / END rows of the member point index ``points`` (``Context.members_points``' CPU tensor). Returns an
+    ``(members + 1, 2)`` int64 CPU tensor; move it to the device for the reads. Raises ZzFlateError (E_DATA) where the rows are
+    not START, inner rows, END per member."""
+    import torch
+    _points_tensor(points, "cpu")
+    out = torch.zeros((points.shape[0], 2), dtype=torch.int64)
+    entries = ctypes.c_uint64(0)
+    _check(lib.zz_members_points_to_index(points.data_ptr(), points.shape[0], out.data_ptr(), out.shape[0], ctypes.byref(entries)))
     return out[: entries.value].clone()
 
 
@@ -1006,6 +1027,34 @@ class Context:
         m, cand, dropped, rounds = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint32(0)
         _check(lib.zz_ctx_last_members_find_stats(self._h, ctypes.byref(m), ctypes.byref(cand), ctypes.byref(dropped), ctypes.byref(rounds)))
         return m.value, cand.value, dropped.value, rounds.value
+
+    def members_points(self, src, chunk_bytes=POINTS_CHUNK, spacing=1, src_len=None, stream=None):
+        """The member point index of ANY file of gzip members ``src`` (a uint8 tensor on this context's device; ``src_len``
+        defaults to its length): ``members_find``'s members AND ``points_index``'s block starts inside them, found together: the
+        cuts at which a file of few large members can be decoded with many wavefronts per member. Returns ``(points, decoded_length)`` with
+        ``points`` an ``(entries, 2)`` int64 CPU tensor of rows (in_bit, out_byte), bits counted from the file's first byte:
+        per member a START row (``MP_START`` set in in_bit), its inner rows, an END row (``MP_END``).
+        ``members_index_from_points`` gives ``members_find``'s index from it. ``spacing`` > 1
+        thins inner rows only. Checksums and distances are NOT judged here (no byte is produced). Raises ZzFlateError (E_DATA:
+        the file is no chain of members, or empty)."""
+        import torch
+        n = src.numel() if src_len is None else src_len
+        entries, total = ctypes.c_uint64(0), ctypes.c_uint64(0)
+        st = self._stream() if stream is None else stream
+        rc = lib.zz_members_points_device(self._h, self._ptr(src), n, chunk_bytes, spacing, None, 0, ctypes.byref(entries), ctypes.byref(total), st)
+        if rc != E_NOSPACE:
+            _check(rc)
+        points = torch.zeros((entries.value, 2), dtype=torch.int64)
+        _check(lib.zz_members_points_device(self._h, self._ptr(src), n, chunk_bytes, spacing, points.data_ptr(), points.shape[0],
+                                            ctypes.byref(entries), ctypes.byref(total), st))
+        return points[: entries.value], total.value
+
+    def last_members_points_stats(self):
+        """(members, header candidates, block candidates, dropped candidates, rounds) of the last ``members_points``."""
+        m, hc, bc, dropped, rounds = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint32(0)
+        _check(lib.zz_ctx_last_members_points_stats(self._h, ctypes.byref(m), ctypes.byref(hc), ctypes.byref(bc), ctypes.byref(dropped),
+                                                    ctypes.byref(rounds)))
+        return m.value, hc.value, bc.value, dropped.value, rounds.value
 
     def _reads(self, call, firsts, nbytes, dsts, caps, stream):
         """the read arrays of decode_members_ranges and decode_points_ranges on the device, the call, and (lens, status) back"""

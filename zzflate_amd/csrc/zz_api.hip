@@ -36,6 +36,7 @@
 #include "zz_inflate_points_find.h"
 #include "zz_inflate_members.h"
 #include "zz_inflate_members_find.h"
+#include "zz_inflate_members_points.h"
 #include "zz_inflate_members_ranges.h"
 #include "zz_inflate_points_ranges.h"
 #include "zz_inflate_points_windows.h"
@@ -204,6 +205,12 @@ struct zz_ctx {
             zz_buf<zz_mf_state> st; zz_pin<zz_mf_state> h_st;
             uint64_t members = 0, candidates = 0, dropped = 0; uint32_t rounds = 0;
         } mf;
+        // zz_members_points_device (zz_inflate_members_points.h): the block candidates, a round's jobs (results in place), the dealing
+        // counter, and what the last call did. The mark passes' buffers are mem's and pf's
+        struct {
+            zz_buf<uint64_t> bc; zz_buf<zi_mp_job> job; zz_buf<unsigned int> next;
+            uint64_t members_found = 0, header_candidates = 0, block_candidates = 0, dropped = 0; uint32_t rounds = 0;
+        } mp;
         // the reads through an index (dec_reads; zz_inflate_members_ranges.h): the stage, per read (record, chunk scan), per unit
         // (differences, counts), per touched unit (list, S, F, G), per unit of a wave its status, per wave two words, what the
         // host reads; a wave's rooms and lengths (and k_inflate_items' descriptors) are mem's
@@ -2969,6 +2976,148 @@ extern "C" int zz_ctx_last_members_find_stats(const zz_ctx* c, uint64_t* members
     if (candidates) *candidates = c->dec.mf.candidates;
     if (dropped) *dropped = c->dec.mf.dropped;
     if (rounds) *rounds = c->dec.mf.rounds;
+    return ZZ_OK;
+}
+
+// ---- points inside members: one index over members and blocks (zz_inflate_members_points.h; the rules in
+// zz_inflate_core.h) ---------------------------------------------------------------------------------------------------------------
+// one round's jobs: up, one launch, the results back in place (want[0, njobs))
+static int mp_run_jobs(zz_ctx* c, const uint8_t* src, uint64_t n, uint64_t nb, uint64_t chunk, zi_mp_job* want, uint64_t njobs, hipStream_t st)
+{
+    auto& P = c->dec.mp;
+    HIPCHK(hipMemcpyAsync(P.job, want, njobs * sizeof(zi_mp_job), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemsetAsync(P.next, 0, sizeof(unsigned int), st));
+    zz_mp_params Q = {};
+    Q.src = src; Q.n = n; Q.bc = P.bc; Q.nb = nb; Q.chunk = chunk; Q.job = P.job; Q.njobs = (uint32_t)njobs; Q.next = P.next;
+    const uint64_t resident = 256ull * ZZ_MP_WG_PER_CU;
+    hipLaunchKernelGGL(k_members_points_reach, dim3((uint32_t)(njobs < resident ? njobs : resident)), dim3(ZZ_INF_THREADS), 0, st, Q);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(want, P.job, njobs * sizeof(zi_mp_job), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return ZZ_OK;
+}
+
+extern "C" int zz_members_points_device(zz_ctx* c, const void* d_src_v, uint64_t src_len, uint64_t chunk_bytes, uint64_t spacing,
+                                        uint64_t* points, uint64_t max_entries, uint64_t* entries, uint64_t* out_len, void* hip_stream)
+{
+    if (entries) *entries = 0;
+    if (out_len) *out_len = 0;
+    if (!c || !entries || !out_len) { set_err("null argument"); return ZZ_E_ARG; }
+    if (!d_src_v && src_len) { set_err("null source"); return ZZ_E_ARG; }
+    if (!points && max_entries) { set_err("null index"); return ZZ_E_ARG; }
+    if (chunk_bytes < 16) { set_err("chunk_bytes must be at least 16"); return ZZ_E_ARG; }
+    if (spacing == 0) { set_err("spacing must be at least 1"); return ZZ_E_ARG; }
+    if (src_len > (~0ull >> 3)) { set_err("src_len must be below 2^61"); return ZZ_E_ARG; }
+    if (call_pending(c)) return ZZ_E_ARG;
+    auto& M = c->dec.mem;
+    auto& F = c->dec.pf;
+    auto& P = c->dec.mp;
+    P.members_found = 0; P.header_candidates = 0; P.block_candidates = 0; P.dropped = 0; P.rounds = 0;
+    if (src_len == 0) { set_err("an empty file holds no gzip member"); return ZZ_E_DATA; }
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t st = (hipStream_t)hip_stream;
+    const uint8_t* src = (const uint8_t*)d_src_v;
+    const char* too_many = "more than 2^31 - 1 candidates: zz_decode_members_device decodes such a file";
+    // the header candidates: zz_members_find_device's mark passes
+    const uint64_t nblk = (src_len + ZZ_MEM_STRETCH - 1) / ZZ_MEM_STRETCH;
+    const uint64_t chunks = zi_find_chunks(src_len, chunk_bytes);
+    if (nblk > 0x7FFFFFFFull || chunks > 0x7FFFFFFFull) { set_err(too_many); return ZZ_E_UNSUPPORTED; }
+    if (int rc = M.blk_cnt.grow(nblk)) return rc;
+    if (int rc = M.blk_base.grow(nblk)) return rc;
+    if (int rc = M.st.grow(1)) return rc;
+    if (int rc = M.h_st.grow(1)) return rc;
+    if (int rc = P.next.grow(1)) return rc;
+    HIPCHK(hipMemsetAsync(M.st, 0, sizeof(zz_mem_state), st));
+    hipLaunchKernelGGL(k_members_find_mark<false>, dim3((uint32_t)nblk), dim3(ZZ_MEM_THREADS), 0, st, src, src_len, (uint32_t*)M.blk_cnt,
+                       (const uint64_t*)nullptr, (uint64_t*)nullptr);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(k_members_scan, dim3(1), dim3(ZZ_MEM_SCAN_THREADS), 0, st, (const uint32_t*)M.blk_cnt, nblk, (uint64_t*)M.blk_base,
+                       (zz_mem_state*)M.st);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(M.h_st, M.st, sizeof(zz_mem_state), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    const uint64_t nh = M.h_st->candidates;                                // (at least one: offset 0)
+    P.header_candidates = nh;
+    if (nh == 0 || nh > 0x7FFFFFFFull) { set_err(too_many); return ZZ_E_UNSUPPORTED; }
+    if (int rc = M.offs.grow(nh)) return rc;
+    hipLaunchKernelGGL(k_members_find_mark<true>, dim3((uint32_t)nblk), dim3(ZZ_MEM_THREADS), 0, st, src, src_len, (uint32_t*)M.blk_cnt,
+                       (const uint64_t*)M.blk_base, (uint64_t*)M.offs);
+    HIPCHK(hipGetLastError());
+    std::vector<uint64_t> hc(nh), bc;
+    HIPCHK(hipMemcpyAsync(hc.data(), M.offs, nh * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    // the block candidates: zz_points_index_device's finder with D = the file
+    const uint64_t resident = 256ull * ZZ_PF_WG_PER_CU;
+    if (chunks > 1) {
+        if (int rc = F.job.grow(chunks + 2)) return rc;
+        if (int rc = F.next.grow(1)) return rc;
+        std::vector<zi_find_job> rec(chunks);
+        HIPCHK(hipMemsetAsync(F.next, 0, sizeof(unsigned int), st));
+        zz_pf_params Q = {};
+        Q.d = src; Q.n = src_len; Q.chunk = chunk_bytes; Q.chunks = chunks; Q.job = F.job; Q.next = F.next;
+        hipLaunchKernelGGL(k_points_find, dim3((uint32_t)(chunks - 1 < resident ? chunks - 1 : resident)), dim3(ZZ_INF_THREADS), 0, st, Q);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(rec.data(), F.job, chunks * sizeof(zi_find_job), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        for (uint64_t k = 1; k < chunks; ++k) if (rec[k].a != ZI_FIND_NONE) bc.push_back(rec[k].a);
+    }
+    HIPCHK(hipStreamSynchronize(st));
+    const uint64_t nb = bc.size();
+    P.block_candidates = nb;
+    if (int rc = P.bc.grow(nb + 1)) return rc;
+    if (int rc = P.job.grow(nh + nb + 2)) return rc;
+    if (nb) HIPCHK(hipMemcpyAsync(P.bc, bc.data(), nb * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+    // the jobs, the walk and its repair rounds
+    std::vector<zi_mp_job> rh(nh + 1), rb(nb + 1), rr(nb + 1), want(nh + nb + 2);
+    std::vector<uint64_t> acc(2 * (2 * nh + nb) + 2);
+    memset(rh.data(), 0, rh.size() * sizeof(zi_mp_job)); memset(rb.data(), 0, rb.size() * sizeof(zi_mp_job));
+    memset(rr.data(), 0, rr.size() * sizeof(zi_mp_job));
+    zi_mp_walk W{ zi_view<const uint64_t>{ hc.data(), nh }, nh, zi_view<const uint64_t>{ bc.data(), nb }, nb, zi_view<zi_mp_job>{ rh.data(), nh },
+                  zi_view<zi_mp_job>{ rb.data(), nb }, zi_view<zi_mp_job>{ rr.data(), nb + 1 }, zi_view<uint64_t>{ acc.data(), 2 * (2 * nh + nb) }, 0,
+                  src_len, 0, 0, 0, 0, 0, 0, 0, 0, 0 };
+    uint64_t nwant = nh + nb;
+    for (uint64_t i = 0; i < nwant; ++i) want[i] = zi_mp_first_job(W, i);
+    int verdict;
+    for (;;) {
+        ++P.rounds;
+        if (int rc = mp_run_jobs(c, src, src_len, nb, chunk_bytes, want.data(), nwant, st)) return rc;
+        for (uint64_t j = 0; j < nwant; ++j) zi_mp_store(W, want[j]);
+        verdict = zi_mp_link(W, zi_view<zi_mp_job>{ want.data(), want.size() }, &nwant);
+        if (verdict != ZI_FW_MORE) break;
+        if (P.rounds > 3 * (nh + nb) + 2) { set_err("the walk over members and blocks did not close"); return ZZ_E_DATA; }   // (every round confirms a job)
+    }
+    P.members_found = W.members; P.dropped = zi_mp_dropped(W);
+    if (verdict == ZI_FW_DATA) {
+        set_err("not a file of gzip members: the walk from offset 0 breaks behind member " + std::to_string(W.members));
+        return ZZ_E_DATA;
+    }
+    *entries = zi_mp_rows(W, spacing, nullptr, 0);
+    *out_len = W.bytes;
+    if (max_entries < *entries) { set_err("the index has " + std::to_string(*entries) + " entries"); return ZZ_E_NOSPACE; }
+    zi_mp_rows(W, spacing, points, max_entries);
+    return ZZ_OK;
+}
+
+extern "C" int zz_ctx_last_members_points_stats(const zz_ctx* c, uint64_t* members, uint64_t* header_candidates, uint64_t* block_candidates,
+                                                uint64_t* dropped, uint32_t* rounds)
+{
+    if (!c) { set_err("null ctx"); return ZZ_E_ARG; }
+    if (members) *members = c->dec.mp.members_found;
+    if (header_candidates) *header_candidates = c->dec.mp.header_candidates;
+    if (block_candidates) *block_candidates = c->dec.mp.block_candidates;
+    if (dropped) *dropped = c->dec.mp.dropped;
+    if (rounds) *rounds = c->dec.mp.rounds;
+    return ZZ_OK;
+}
+
+extern "C" int zz_members_points_to_index(const uint64_t* points, uint64_t entries, uint64_t* index, uint64_t max_entries, uint64_t* index_entries)
+{
+    if (index_entries) *index_entries = 0;
+    if (!points || !index_entries || (!index && max_entries)) { set_err("null argument"); return ZZ_E_ARG; }
+    const uint64_t n = zi_mp_to_index(points, entries, nullptr, 0);
+    if (n == 0) { set_err("the rows are no member point index: START, inner rows and END per member"); return ZZ_E_DATA; }
+    *index_entries = n;
+    if (max_entries < n) { set_err("the index has " + std::to_string(n) + " entries"); return ZZ_E_NOSPACE; }
+    zi_mp_to_index(points, entries, index, max_entries);
     return ZZ_OK;
 }
 

@@ -1889,4 +1889,234 @@ ZZ_HD inline uint64_t zi_mf_again(const zi_mf_walk& W, const zi_view<const zi_fi
 ZZ_HD inline bool zi_mf_dealt(uint64_t out, uint64_t off, uint64_t cap) { return off <= cap && out <= cap - off; }
 ZZ_HD inline bool zi_mf_is_mstar(uint64_t out, uint64_t off, uint64_t cap) { return off <= cap && out > cap - off; }
 
+// ---- points inside members: one index over members and blocks (zz_members_points_device,
+// zz_inflate_members_points.h; tests/cxx/members_points_harness.cpp) ---------------------------------------------------------------
+// The two finders above joined. F = the file, C = chunk_bytes, bits count from F's first byte. The result is defined by F, C and
+// `spacing` alone:
+//   HEADER CANDIDATES H  zi_mf_candidate's set: offset 0, and every i >= 20 where zi_header(gzip) accepts with ten bytes left behind it
+//   BLOCK CANDIDATES B   for every chunk c >= 1 of F the lowest bit that passes zi_find_header, no bit of the header behind F
+//                        (the point finder with D = F); chunk 0 has none: bit 0 of F is a gzip header, not a block
+//   JOBS                 one per candidate. A header job at i parses the header and measures from bit 8(i + hl); a block job
+//                        measures from its bit: ZI_RUN_REACH onto zi_out_count to the first block boundary at or behind its STOP --
+//                        the lowest block candidate above the job's first block bit -- or through a final block. A job that ends
+//                        with a final block reads the member's ISIZE from the eight bytes behind the block's last byte (an error
+//                        if they do not fit in F). A limited job gives up `C` bytes behind its stop, or ZI_FIND_TAIL behind its
+//                        first bit where it has no stop; the job at offset 0 and every job the confirmed walk asks for again have
+//                        no limit, so no result depends on limits, rounds or scheduling.
+//   WALK                 header state at offset i: i must be in H and its job OK; it opens member j with the START row
+//                        (8(i + hl) | ZZ_MP_START, off_j). Block state at bit b: if b is in B its job continues the member and
+//                        (b, bytes in front of b) is an inner row; otherwise the stretch to the next block candidate is a gap that a
+//                        repair job measures (zi_find_link's scheme: behind the first gap the walk goes on provisionally, across
+//                        member ends too, and asks for the repairs it meets in the same launch). A job that ends FINAL closes the
+//                        member: ISIZE must equal the low 32 bits of the member's count, the END row is (end_bit | ZZ_MP_END,
+//                        off_{j+1}), and the next offset is ((end_bit + 7) >> 3) + 8 -- src_len: done, otherwise a header state.
+//                        Candidates the walk steps over are dropped; a block candidate that IS an accepted member's first block bit
+//                        is absorbed by the START row (neither a row nor dropped).
+//   ROWS                 START, inner rows, END per member; `spacing` > 1 thins inner rows only (zi_points_keep on file-absolute
+//                        decoded positions, `next` starting again at every START row).
+#define ZZ_MP_START (1ull << 63)
+#define ZZ_MP_END (1ull << 62)
+#define ZZ_MP_BIT(v) ((v) & ~(ZZ_MP_START | ZZ_MP_END))
+// A job's record (40 bytes, in place). in: a = the header's offset (ZI_MPJ_HEADER) or the start bit, flags = ZI_MPJ_*;
+// out: a as it was, first = the first block bit (8(a + hl), or a), b = the bit where the run ended, c = the bytes it counted,
+// isize (FINAL only), flags = the job's kind | exactly one of ZI_FJ_OK, ZI_FJ_GAVEUP, ZI_FJ_ERROR | ZI_FJ_FINAL.
+enum { ZI_MPJ_HEADER = 32, ZI_MPJ_NOLIMIT = 64 };
+struct zi_mp_job { uint64_t a, b, c, first; uint32_t flags, isize; };
+// the lowest block candidate above `bit` (ZI_FIND_NONE: none), and its number
+ZZ_HD inline uint64_t zi_mp_above(const zi_view<const uint64_t>& bc, uint64_t nb, uint64_t bit)
+{
+    uint64_t lo = 0, hi = nb;
+    while (lo < hi) { const uint64_t mid = (lo + hi) / 2; if (bc[mid] <= bit) lo = mid + 1; else hi = mid; }
+    return lo;
+}
+ZZ_HD inline uint64_t zi_mp_lower(const zi_view<const uint64_t>& v, uint64_t n, uint64_t x)      // the first element at or behind x
+{
+    uint64_t lo = 0, hi = n;
+    while (lo < hi) { const uint64_t mid = (lo + hi) / 2; if (v[mid] < x) lo = mid + 1; else hi = mid; }
+    return lo;
+}
+// a limited job's limit bit. own_limit (0: none) is the tests': that many bytes behind the job's first bit instead, so that with a
+// small one the jobs of the true walk give up too and are run again
+ZZ_HD inline uint64_t zi_mp_limit(uint64_t first, uint64_t stop, uint64_t C, uint64_t own_limit)
+{
+    if (own_limit) return first + 8 * own_limit;
+    return stop != ZI_FIND_NONE ? zi_find_limit(stop, C) : first + 8 * ZI_FIND_TAIL;
+}
+template <class L>
+ZZ_HD zi_mp_job zi_mp_measure(L& w, const uint8_t* src, uint64_t n, const zi_view<const uint64_t>& bc, uint64_t nb, uint64_t C,
+                              uint64_t own_limit, const zi_mp_job& j, zi_tables& S, uint32_t lane, uint32_t nl)
+{
+    const uint32_t kind = j.flags & ZI_MPJ_HEADER;
+    zi_mp_job r{ j.a, 0, 0, j.a, kind | (uint32_t)ZI_FJ_ERROR, 0 };
+    if (kind) {
+        if (j.a >= n) return r;
+        const int64_t hl = zi_header(1, src + j.a, n - j.a);
+        if (hl < 0) return r;
+        r.first = 8 * (j.a + (uint64_t)hl);
+    }
+    if (r.first >= 8 * n) return r;
+    const uint64_t s = zi_mp_above(bc, nb, r.first);
+    const uint64_t stop = s < nb ? bc[s] : ZI_FIND_NONE;
+    const uint64_t limit = (j.flags & ZI_MPJ_NOLIMIT) ? ZI_FIND_NONE : zi_mp_limit(r.first, stop, C, own_limit);
+    const zi_view<const uint8_t> view{ src, n };
+    typename L::in_t in = w.input(src, n);
+    zi_out_count o{ 0 };
+    zi_pt_reach pt{ (uint32_t)(r.first & 7), stop, false, 0, limit };
+    S.kind = 0;
+    const zi_result R = zi_run(in, view, r.first >> 3, o, S, ZI_RUN_REACH, 0, lane, nl, pt);
+    r.b = pt.end_bit; r.c = R.out;
+    if (R.err == ZI_E_GAVEUP) { r.flags = kind | (uint32_t)ZI_FJ_GAVEUP; return r; }
+    if (R.err) return r;
+    if (!R.final) { r.flags = kind | (uint32_t)ZI_FJ_OK; return r; }
+    if (R.end > n || n - R.end < 8) return r;                                 // truncated trailer
+    r.isize = view[R.end + 4] | ((uint32_t)view[R.end + 5] << 8) | ((uint32_t)view[R.end + 6] << 16) | ((uint32_t)view[R.end + 7] << 24);
+    r.flags = kind | (uint32_t)ZI_FJ_OK | (uint32_t)ZI_FJ_FINAL;
+    return r;
+}
+// The WALK owns, for nh header candidates hc (ascending offsets) and nb block candidates bc (ascending bits):
+//   rh[k]  the header job of hc[k];  rb[m]  the block job of bc[m];  rr[m]  a repair job whose stop is bc[m] (m = nb: none)
+//   acc    the rows in order, not thinned: 2 words each (room for 2 * nh + nb rows)
+// zi_mp_link returns ZI_FW_MORE / DONE / DATA as zi_find_link does; jobs it wants are appended to `want` (room for nh + nb + 2).
+struct zi_mp_walk {
+    zi_view<const uint64_t> hc; uint64_t nh; zi_view<const uint64_t> bc; uint64_t nb;
+    zi_view<zi_mp_job> rh, rb, rr;
+    zi_view<uint64_t> acc; uint64_t nacc;
+    uint64_t src_len;
+    int block;                              // the state: 0 a header at offset `pos`, 1 a block at bit `pos`
+    uint64_t pos, k, m;                     // k, m: the first header / block candidate that is not in front of the walk
+    uint64_t bytes, origin;                 // decoded bytes in front of pos; in front of the open member
+    uint64_t members, inner, absorbed;
+};
+ZZ_HD inline zi_mp_job zi_mp_first_job(const zi_mp_walk& W, uint64_t i)        // round 1: job i of nh + nb
+{
+    if (i < W.nh) return zi_mp_job{ W.hc[i], 0, 0, 0, (uint32_t)ZI_MPJ_HEADER | (W.hc[i] == 0 ? (uint32_t)ZI_MPJ_NOLIMIT : 0u), 0 };
+    return zi_mp_job{ W.bc[i - W.nh], 0, 0, 0, 0, 0 };
+}
+ZZ_HD inline void zi_mp_store(zi_mp_walk& W, const zi_mp_job& r)
+{
+    if (r.flags & ZI_MPJ_HEADER) { const uint64_t k = zi_mp_lower(W.hc, W.nh, r.a); if (k < W.nh && W.hc[k] == r.a) W.rh[k] = r; return; }
+    const uint64_t m = zi_mp_lower(W.bc, W.nb, r.a);
+    if (m < W.nb && W.bc[m] == r.a) W.rb[m] = r; else W.rr[m] = r;
+}
+ZZ_HD inline bool zi_mp_have(const zi_mp_job& R, uint64_t a) { return (R.flags & (ZI_FJ_OK | ZI_FJ_GAVEUP | ZI_FJ_ERROR)) && R.a == a; }
+ZZ_HD inline uint64_t zi_mp_next_offset(uint64_t end_bit) { return ((end_bit + 7) >> 3) + 8; }
+ZZ_HD inline int zi_mp_link(zi_mp_walk& W, zi_view<zi_mp_job> want, uint64_t* nwant)
+{
+    *nwant = 0;
+    if (W.src_len == 0) return ZI_FW_DATA;
+    bool pblock = false; uint64_t ppos = 0;                          // where the provisional walk starts (pblock: at candidate ppos)
+    for (;;) {                                                        // the confirmed walk
+        zi_mp_job* R;
+        bool at_cand = false;
+        if (!W.block) {
+            while (W.k < W.nh && W.hc[W.k] < W.pos) ++W.k;
+            if (W.k >= W.nh || W.hc[W.k] != W.pos) return ZI_FW_DATA;          // what stands behind a trailer is no header
+            R = &W.rh[W.k];
+        } else {
+            while (W.m < W.nb && W.bc[W.m] < W.pos) ++W.m;
+            at_cand = W.m < W.nb && W.bc[W.m] == W.pos;
+            R = at_cand ? &W.rb[W.m] : &W.rr[W.m];
+        }
+        if (!zi_mp_have(*R, W.pos) || (R->flags & ZI_FJ_GAVEUP)) {
+            const bool gave = zi_mp_have(*R, W.pos);
+            const uint64_t first = gave ? R->first : W.pos;
+            want[(*nwant)++] = zi_mp_job{ W.pos, 0, 0, 0, (W.block ? 0u : (uint32_t)ZI_MPJ_HEADER) | (uint32_t)ZI_MPJ_NOLIMIT, 0 };
+            *R = zi_mp_job{ W.pos, 0, 0, first, (W.block ? 0u : (uint32_t)ZI_MPJ_HEADER) | (uint32_t)ZI_FJ_SENT, 0 };
+            if (!W.block && !gave) return ZI_FW_MORE;                 // (round 1 runs every header job: not reached)
+            pblock = true; ppos = zi_mp_above(W.bc, W.nb, first);     // as if the job landed on the candidate above its first bit
+            break;
+        }
+        if (R->flags & ZI_FJ_ERROR) return ZI_FW_DATA;
+        if (!W.block) {                                               // the job opens a member
+            W.origin = W.bytes;
+            W.acc[2 * W.nacc] = R->first | ZZ_MP_START; W.acc[2 * W.nacc + 1] = W.bytes; ++W.nacc;
+            ++W.members;
+            while (W.m < W.nb && W.bc[W.m] < R->first) ++W.m;
+            if (W.m < W.nb && W.bc[W.m] == R->first) { ++W.absorbed; ++W.m; }
+            W.block = 1;
+        } else if (at_cand) {
+            W.acc[2 * W.nacc] = W.pos; W.acc[2 * W.nacc + 1] = W.bytes; ++W.nacc;
+            ++W.inner;
+        }
+        W.bytes += R->c;
+        if (R->flags & ZI_FJ_FINAL) {                                 // the job closes the member
+            if (R->isize != (uint32_t)(W.bytes - W.origin)) return ZI_FW_DATA;
+            W.acc[2 * W.nacc] = R->b | ZZ_MP_END; W.acc[2 * W.nacc + 1] = W.bytes; ++W.nacc;
+            const uint64_t next = zi_mp_next_offset(R->b);
+            if (next > W.src_len) return ZI_FW_DATA;
+            if (next == W.src_len) return ZI_FW_DONE;
+            W.block = 0; W.pos = next;
+            continue;
+        }
+        if (R->b <= R->first) return ZI_FW_DATA;                      // (a run consumes at least a block header)
+        W.pos = R->b;
+    }
+    for (uint64_t steps = 0; steps <= W.nh + W.nb; ++steps) {         // the provisional walk: it accepts nothing
+        const zi_mp_job* R;
+        if (pblock) {
+            if (ppos >= W.nb) break;
+            R = &W.rb[ppos];
+            if (!(R->flags & ZI_FJ_OK) || R->a != W.bc[ppos]) break;
+        } else {
+            const uint64_t k = zi_mp_lower(W.hc, W.nh, ppos);
+            if (k >= W.nh || W.hc[k] != ppos) break;
+            R = &W.rh[k];
+            if (!(R->flags & ZI_FJ_OK) || R->a != ppos) break;
+        }
+        if (R->flags & ZI_FJ_FINAL) {
+            pblock = false; ppos = zi_mp_next_offset(R->b);
+            if (ppos >= W.src_len) break;
+            continue;
+        }
+        if (R->b <= R->first) break;
+        const uint64_t lo = zi_mp_lower(W.bc, W.nb, R->b);
+        if (!(lo < W.nb && W.bc[lo] == R->b)) {                       // a gap: its repair, limited (it may start anywhere)
+            zi_mp_job& G = W.rr[lo];
+            if (!(G.flags && G.a == R->b)) {
+                want[(*nwant)++] = zi_mp_job{ R->b, 0, 0, 0, 0, 0 };
+                G = zi_mp_job{ R->b, 0, 0, R->b, ZI_FJ_SENT, 0 };
+            }
+        }
+        pblock = true; ppos = lo;
+    }
+    return ZI_FW_MORE;
+}
+ZZ_HD inline uint64_t zi_mp_dropped(const zi_mp_walk& W) { return W.nh + W.nb - W.members - W.inner - W.absorbed; }
+// The rows behind ZI_FW_DONE, thinned. Returns the rows; writes them while they fit `max_rows` (rows == nullptr: counts).
+ZZ_HD inline uint64_t zi_mp_rows(const zi_mp_walk& W, uint64_t spacing, uint64_t* rows, uint64_t max_rows)
+{
+    uint64_t n = 0, next = 0;
+    for (uint64_t i = 0; i < W.nacc; ++i) {
+        const uint64_t bit = W.acc[2 * i], pos = W.acc[2 * i + 1];
+        if (!(bit & (ZZ_MP_START | ZZ_MP_END)) && !zi_points_keep(bit, pos, spacing, next)) continue;
+        if (!(bit & ZZ_MP_END)) next = zi_points_next(pos, spacing);
+        if (rows && n < max_rows) { rows[2 * n] = bit; rows[2 * n + 1] = pos; }
+        ++n;
+    }
+    return n;
+}
+// The START / END rows as zz_members_find_device's pairs (file offset, decoded offset): c_0 = 0, c_{j+1} = behind END_j's trailer.
+// Returns the pairs (members + 1), or 0 where the rows are no member point index; writes them while they fit.
+ZZ_HD inline uint64_t zi_mp_to_index(const uint64_t* points, uint64_t entries, uint64_t* index, uint64_t max_entries)
+{
+    uint64_t n = 0, c = 0;
+    bool open = false;
+    for (uint64_t i = 0; i < entries; ++i) {
+        const uint64_t bit = points[2 * i], pos = points[2 * i + 1];
+        if ((bit & ZZ_MP_START) && (bit & ZZ_MP_END)) return 0;
+        if (bit & ZZ_MP_START) {
+            if (open) return 0;
+            open = true;
+            if (index && n < max_entries) { index[2 * n] = c; index[2 * n + 1] = pos; }
+            ++n;
+        } else if (bit & ZZ_MP_END) {
+            if (!open) return 0;
+            open = false;
+            c = zi_mp_next_offset(ZZ_MP_BIT(bit));
+            if (i + 1 == entries) { if (index && n < max_entries) { index[2 * n] = c; index[2 * n + 1] = pos; } ++n; }
+        } else if (!open) return 0;
+    }
+    return open || entries == 0 ? 0 : n;
+}
+
 }  // namespace zz
