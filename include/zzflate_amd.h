@@ -636,7 +636,7 @@ int zz_ctx_last_members_find_stats(const zz_ctx* ctx, uint64_t* members, uint64_
 
 /* Points INSIDE members: one index over the members of any file of gzip members and the blocks inside them, the
  * cuts a decode of a file of few large members -- `cat lane1.fq.gz lane2.fq.gz`, rotated logs joined with cat -- needs to use many
- * wavefronts per member (that decode is not part of the library yet: DESIGN.md 23). The
+ * wavefronts per member (that decode is zz_decode_members_points_device, below). The
  * result is defined by the file F, chunk_bytes C and spacing alone; bits count from F's first byte:
  *   header candidates  zz_members_find_device's: offset 0, and every offset i >= 20 where a gzip header stands with ten bytes
  *                      left behind it
@@ -676,6 +676,36 @@ int zz_ctx_last_members_points_stats(const zz_ctx* ctx, uint64_t* members, uint6
  * + 1 of them, so that zz_decode_members_ranges_device reads such files too (`index` in host memory: copy it to the device).
  * Size protocol as above. ZZ_E_DATA: the rows are not START, inner rows, END per member. */
 int zz_members_points_to_index(const uint64_t* points, uint64_t entries, uint64_t* index, uint64_t max_entries, uint64_t* index_entries);
+/* zz_decode_members_device for files of LARGE members, through a member point index: many wavefronts per member. For EVERY input
+ * -- every file, every row array (true, thinned, lying, another file's), every cap and batch_bytes -- the return value, *out_len,
+ * the bytes d_dst[0, *out_len) and "nothing is written outside d_dst[0, cap)" are what zi_members defines, that is, what
+ * zz_decode_members_device gives. The index decides speed, never the result.
+ *   points, entries  zz_members_points_device's rows in HOST memory (as zz_decode_points_device takes its rows). NULL with 0: the
+ *                    call makes the index itself (ZZ_POINTS_CHUNK_DEFAULT, spacing 1); if that fails for any reason but ZZ_E_HIP
+ *                    the serial path decides on the whole file.
+ *   batch_bytes      the most decoded bytes in a batch (zz_points_windows_device's stage_bytes knob); 0 means 64 MiB.
+ * The rows are an index if they are START, inner rows, END per member; their masked bits ascend strictly; every START bit is a
+ * multiple of 8; out_byte ascends from 0 and every END's equals the next START's; and with c_0 = 0, c_{j+1} = ((end_j + 7) >> 3) + 8:
+ * c_j + 10 <= start_j / 8 and the last c is src_len. Anything else sends the whole file to the serial path. Member j is DEALT if it
+ * lies in front of m*, the first member whose END out_byte passes cap or that holds a segment longer than batch_bytes. A dealt member
+ * is PROVEN iff (1) the gzip header at c_j ends exactly at start_j / 8; (2) every segment of it decodes from its bit to exactly the
+ * next row's bit into exactly its room, the final block in its last segment and nowhere else, no distance reaching in front of the
+ * member's first byte; (3) the CRC-32 of its bytes is the trailer's; (4) ISIZE is the low 32 bits of its length. With f the first
+ * dealt member that is not proven, or m*: without f the result is ZZ_OK and *out_len = L; otherwise the serial path runs from member
+ * f over what is left of source, destination and room, and its answer is the call's (DESIGN.md 23 has the argument).
+ *   ZZ_E_ARG, before anything is launched: zz_decode_members_found_device's rules; null points with entries > 0; entries == 1;
+ *     batch_bytes above 64 MiB.
+ * *out_len = ~0 on failure. Workspace: a batch's (4 bytes and a bit per decoded byte of it), 53 bytes per segment and 65 per member.
+ * Synchronous; the host reads a fixed number of words per batch and per call. Leaves the context's "last call", "last decode" and
+ * the other calls' stats alone (zz_ctx_last_members_points_stats too when the call makes its own index). */
+int zz_decode_members_points_device(zz_ctx* ctx, const void* d_src, uint64_t src_len, void* d_dst, uint64_t cap,
+                                    uint64_t* out_len, const uint64_t* points, uint64_t entries,
+                                    uint64_t batch_bytes, void* hip_stream);
+/* what the last zz_decode_members_points_device did: the members the rows name (0: the rows were no index, or none could be made),
+ * the members proven in front of the serial tail (all of them: no tail), the segments dealt, the batches launched, the pending bytes
+ * and the most rounds of a batch, and 1 if the serial path ran (all 0: no call yet, or refused before anything ran) */
+int zz_ctx_last_decode_members_points_stats(const zz_ctx* ctx, uint64_t* members, uint64_t* proven, uint64_t* segments,
+                                            uint32_t* batches, uint64_t* pending_bytes, uint32_t* rounds, int* serial);
 
 /* Many reads of one blocked gzip (BGZF) file through its index in one call: read r receives the decoded bytes
  * [d_firsts[r], d_firsts[r] + d_nbytes[r]) of the file d_src[0, src_len). d_index / entries are an index as above (from

@@ -20,7 +20,7 @@ KERNELS = ["k_encode_l1E", "k_encode_l1pE", "k_encode_l1pwE", "k_encode_l1wE", "
            "k_inflate_itemsE", "k_inflate_segmentsE", "k_inflate_segments_winE", "k_inflate_membersE", "k_members_markILb0E", "k_members_markILb1E", "k_members_slotsE",
            "k_points_findE", "k_points_reachE", "k_points_windows_cutE",
            "k_members_find_markILb0E", "k_members_find_markILb1E", "k_members_reachE", "k_members_find_slotsE",
-           "k_members_points_reachE"]
+           "k_members_points_reachE", "k_members_segmentsE", "k_members_sumsE", "k_members_verdictE"]
 
 
 def main():

@@ -123,6 +123,8 @@ def _load():
         "zz_members_points_device": (i32, [vp, vp, u64, u64, u64, vp, u64, pu64, pu64, vp]),
         "zz_ctx_last_members_points_stats": (i32, [vp, pu64, pu64, pu64, pu64, ctypes.POINTER(u32)]),
         "zz_members_points_to_index": (i32, [vp, u64, vp, u64, pu64]),
+        "zz_decode_members_points_device": (i32, [vp, vp, u64, vp, u64, pu64, vp, u64, u64, vp]),
+        "zz_ctx_last_decode_members_points_stats": (i32, [vp, pu64, pu64, pu64, ctypes.POINTER(u32), pu64, ctypes.POINTER(u32), ctypes.POINTER(i32)]),
         "zz_decode_members_ranges_device": (i32, [vp, vp, u64, vp, u64, u64, vp, vp, vp, vp, vp, vp, vp]),
         "zz_ctx_last_decode_members_ranges_stats": (i32, [vp, pu64, ctypes.POINTER(u32)]),
         "zz_points_windows_host": (i32, [vp, u64, i32, vp, u64, vp, vp]),
@@ -1055,6 +1057,48 @@ class Context:
         _check(lib.zz_ctx_last_members_points_stats(self._h, ctypes.byref(m), ctypes.byref(hc), ctypes.byref(bc), ctypes.byref(dropped),
                                                     ctypes.byref(rounds)))
         return m.value, hc.value, bc.value, dropped.value, rounds.value
+
+    def decode_members_points(self, src, points=None, cap=None, src_len=None, dst=None, batch_bytes=0, stream=None):
+        """``decode_members`` for files of LARGE members -- ``cat lane1.fq.gz lane2.fq.gz``, rotated logs joined with cat -- through
+        a member point index: many wavefronts per member, where ``decode_members_found`` has one. ``points`` are ``members_points``'
+        rows, an ``(entries, 2)`` int64 CPU tensor (or anything ``torch.as_tensor`` makes one of); ``None``: the call makes the
+        index itself. The rows are never trusted: the verdict and the bytes are ``decode_members``' for every input and every row
+        array, true, thinned or lying; only the speed differs. ``batch_bytes`` is the most decoded bytes in a batch (0: 64 MiB).
+        Returns the decoded bytes, a uint8 tensor on this context's device: a view of ``dst`` (``cap`` defaults to its length) when
+        that is given, else of a new tensor of ``cap`` bytes -- ``cap=None`` takes the decoded length from ``members_points``
+        (which is then also the index used when ``points`` is None). Raises ZzFlateError (E_DATA, E_NOSPACE) as ``decode_members``
+        does, TypeError for rows that are no ``(entries, 2)`` int64 array."""
+        import torch
+        n = src.numel() if src_len is None else src_len
+        if dst is not None:
+            if not isinstance(dst, torch.Tensor) or dst.dtype != torch.uint8 or not dst.is_contiguous():
+                raise TypeError("dst must be a contiguous uint8 tensor")
+            cap = dst.numel() if cap is None else cap
+        if points is not None:
+            points = torch.as_tensor(points)
+            if points.dtype != torch.int64 or points.dim() != 2 or points.shape[1] != 2 or points.device.type != "cpu":
+                raise TypeError("points must be an (entries, 2) int64 CPU tensor")
+            points = points.contiguous()
+        if dst is None:
+            if cap is None:
+                made, cap = self.members_points(src, POINTS_CHUNK, 1, n, stream)
+                points = made if points is None else points
+            dst = torch.empty(cap, dtype=torch.uint8, device=f"cuda:{self.device}")
+        out = ctypes.c_uint64(0)
+        st = self._stream() if stream is None else stream
+        rows, entries = (None, 0) if points is None else (points.data_ptr(), points.shape[0])
+        _check(lib.zz_decode_members_points_device(self._h, self._ptr(src), n, dst.data_ptr(), cap, ctypes.byref(out), rows, entries,
+                                                   batch_bytes, st))
+        return dst[:out.value]
+
+    def last_decode_members_points_stats(self):
+        """(members the rows name, members proven in front of the serial tail, segments dealt, batches, pending bytes, rounds,
+        serial) of the last ``decode_members_points``; serial is 1 if the serial path ran (from the first member not proven)."""
+        m, proven, segs, pend = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint64(0)
+        batches, rounds, serial = ctypes.c_uint32(0), ctypes.c_uint32(0), ctypes.c_int(0)
+        _check(lib.zz_ctx_last_decode_members_points_stats(self._h, ctypes.byref(m), ctypes.byref(proven), ctypes.byref(segs),
+                                                           ctypes.byref(batches), ctypes.byref(pend), ctypes.byref(rounds), ctypes.byref(serial)))
+        return m.value, proven.value, segs.value, batches.value, pend.value, rounds.value, serial.value
 
     def _reads(self, call, firsts, nbytes, dsts, caps, stream):
         """the read arrays of decode_members_ranges and decode_points_ranges on the device, the call, and (lens, status) back"""

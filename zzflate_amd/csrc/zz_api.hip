@@ -10,6 +10,7 @@
 #include <mutex>
 #include <string>
 #include <thread>
+#include <tuple>
 #include <vector>
 #include <algorithm>
 #include <cstdio>
@@ -37,6 +38,7 @@
 #include "zz_inflate_members.h"
 #include "zz_inflate_members_find.h"
 #include "zz_inflate_members_points.h"
+#include "zz_inflate_members_decode.h"
 #include "zz_inflate_members_ranges.h"
 #include "zz_inflate_points_ranges.h"
 #include "zz_inflate_points_windows.h"
@@ -211,6 +213,14 @@ struct zz_ctx {
             zz_buf<uint64_t> bc; zz_buf<zi_mp_job> job; zz_buf<unsigned int> next;
             uint64_t members_found = 0, header_candidates = 0, block_candidates = 0, dropped = 0; uint32_t rounds = 0;
         } mp;
+        // zz_decode_members_points_device (zz_inflate_members_decode.h): the dealt descriptors and members of the call, per descriptor
+        // its flag and its sum, per member its status, the verdict's word, the dealing counter, and what the last call did. The batch's
+        // workspace is dec_points_workspace's, the serial path's result is mem's
+        struct {
+            zz_buf<zi_mpd_seg> seg; zz_buf<zi_mpd_member> mem; zz_buf<uint8_t> segok, status; zz_buf<uint32_t> sums;
+            zz_buf<unsigned long long> first_bad; zz_buf<unsigned int> next;
+            uint64_t members = 0, proven = 0, segments = 0, pending = 0; uint32_t batches = 0, rounds = 0; int serial = 0;
+        } mpd;
         // the reads through an index (dec_reads; zz_inflate_members_ranges.h): the stage, per read (record, chunk scan), per unit
         // (differences, counts), per touched unit (list, S, F, G), per unit of a wave its status, per wave two words, what the
         // host reads; a wave's rooms and lengths (and k_inflate_items' descriptors) are mem's
@@ -3118,6 +3128,172 @@ extern "C" int zz_members_points_to_index(const uint64_t* points, uint64_t entri
     *index_entries = n;
     if (max_entries < n) { set_err("the index has " + std::to_string(n) + " entries"); return ZZ_E_NOSPACE; }
     zi_mp_to_index(points, entries, index, max_entries);
+    return ZZ_OK;
+}
+
+// ---- decode through a member point index (zz_inflate_members_decode.h; the rules, zi_mpd_*, in zz_inflate_core.h) ---------------
+// One batch: descriptors [k0, k0 + nseg) of the call through phase 1, the tile counts, the rounds and the sums. *failed: segments
+// whose run was refused (the rounds and the sums still run: pointers never leave their member, so the members that hold no refused
+// segment end up whole). The host waits once, and once more behind the rounds if anything is pending.
+static int mpd_batch(zz_ctx* c, const uint8_t* src, uint64_t n, const zi_mpd_seg* seg, uint64_t k0, uint32_t nseg, uint8_t* dst,
+                     hipStream_t st, unsigned long long* failed)
+{
+    auto& D = c->dec;
+    auto& X = D.mpd;
+    const uint32_t words = ZI_POINTS_TILE / 32;
+    const uint64_t resident = 256ull * ZZ_MPD_WG_PER_CU;
+    const uint64_t base = seg[k0].o0, nbytes = seg[k0 + nseg - 1].o1 - base;
+    const uint32_t tiles = (uint32_t)((nbytes + ZI_POINTS_TILE - 1) / ZI_POINTS_TILE);
+    const uint32_t grid = (uint32_t)(nseg < resident ? nseg : resident);
+    HIPCHK(hipMemsetAsync(D.tot, 0, ZZ_TOT_SLOTS * sizeof(unsigned long long), st));
+    HIPCHK(hipMemsetAsync(X.next, 0, sizeof(unsigned int), st));
+    if (tiles) HIPCHK(hipMemsetAsync(D.pend, 0, (uint64_t)tiles * words * 4, st));
+    zz_mpd_params Q;
+    Q.src = src; Q.n = n; Q.seg = X.seg; Q.k0 = k0; Q.nseg = nseg; Q.dst = dst; Q.base = base; Q.nbytes = nbytes;
+    Q.st = D.st; Q.pend = D.pend; Q.words = (uint64_t)tiles * words; Q.segok = X.segok; Q.sums = X.sums; Q.next = X.next; Q.tot = D.tot;
+    hipLaunchKernelGGL(k_members_segments, dim3(grid), dim3(ZZ_INF_THREADS), 0, st, Q);
+    if (tiles) hipLaunchKernelGGL(k_points_count, dim3(tiles), dim3(256), 0, st, D.pend, D.pcnt, D.prem, D.tot);
+    HIPCHK(hipGetLastError());
+    unsigned long long tot[ZZ_TOT_SLOTS];
+    if (int rc = dec_read_tot(c, tot, st)) return rc;
+    *failed = tot[ZZ_TOT_FAILED];
+    ++X.batches;
+    if (tot[ZZ_TOT_PENDING] != 0) {
+        const uint32_t rounds = zz_inf_rounds(nseg);                        // a chain has at most one link per segment of a batch
+        zz_res_params R{ dst, base, ZI_POINTS_TILE, tiles, words, D.st, D.pend, D.pcnt, D.prem, D.tot };
+        for (uint32_t r = 1; r <= rounds; ++r) hipLaunchKernelGGL(k_inflate_resolve, dim3(tiles), dim3(ZZ_INF_RES_THREADS), 0, st, R, r);
+        HIPCHK(hipGetLastError());
+    }
+    HIPCHK(hipMemsetAsync(X.next, 0, sizeof(unsigned int), st));
+    hipLaunchKernelGGL(k_members_sums, dim3(grid), dim3(ZZ_INF_THREADS), 0, st, Q);
+    HIPCHK(hipGetLastError());
+    if (tot[ZZ_TOT_PENDING] != 0) {
+        const uint32_t rounds = zz_inf_rounds(nseg);
+        const unsigned long long pending = tot[ZZ_TOT_PENDING];
+        if (int rc = dec_read_tot(c, tot, st)) return rc;
+        if (tot[ZZ_TOT_OPEN + rounds] != 0) *failed += 1;                   // (cannot happen: the rounds suffice for any chain)
+        uint32_t r = 1;
+        while (r < rounds && tot[ZZ_TOT_OPEN + r] != 0) ++r;
+        X.pending += pending;
+        X.rounds = std::max(X.rounds, r);
+    }
+    return ZZ_OK;
+}
+
+extern "C" int zz_decode_members_points_device(zz_ctx* c, const void* d_src_v, uint64_t src_len, void* d_dst_v, uint64_t cap, uint64_t* out_len,
+                                               const uint64_t* points, uint64_t entries, uint64_t batch_bytes, void* hip_stream)
+{
+    if (out_len) *out_len = ~0ull;
+    if (!c) { set_err("null ctx"); return ZZ_E_ARG; }
+    {   // the stats say "refused before anything ran" from here on
+        auto& X0 = c->dec.mpd;
+        X0.members = 0; X0.proven = 0; X0.segments = 0; X0.pending = 0; X0.batches = 0; X0.rounds = 0; X0.serial = 0;
+    }
+    if (!out_len) { set_err("null out_len"); return ZZ_E_ARG; }
+    if (!d_src_v && src_len) { set_err("null source"); return ZZ_E_ARG; }
+    if (!d_dst_v && cap) { set_err("null destination"); return ZZ_E_ARG; }
+    if (!points && entries) { set_err("null points with entries > 0 (the rows live in host memory; NULL and 0: the call makes them)"); return ZZ_E_ARG; }
+    if (entries == 1) { set_err("a member point index has at least two rows"); return ZZ_E_ARG; }
+    if (batch_bytes > ZZ_INF_BATCH_BYTES) { set_err("batch_bytes must be at most 64 MiB (0: 64 MiB)"); return ZZ_E_ARG; }
+    if (call_pending(c)) return ZZ_E_ARG;
+    auto& D = c->dec;
+    auto& M = D.mem;
+    auto& X = D.mpd;
+    if (src_len == 0) { set_err("an empty file holds no gzip member"); return ZZ_E_DATA; }
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t st = (hipStream_t)hip_stream;
+    const uint8_t* src = (const uint8_t*)d_src_v;
+    uint8_t* dst = (uint8_t*)d_dst_v;
+    const uint64_t limit = batch_bytes ? batch_bytes : ZZ_INF_BATCH_BYTES;
+    // zi_members over what is left behind `members0` proven members (`at` source bytes, `off` decoded bytes): its answer is the call's
+    const auto serial = [&](uint64_t members0, uint64_t at, uint64_t off) -> int {
+        X.serial = 1; X.proven = members0;
+        if (int rc = members_serial_run(c, src + at, src_len - at, dst + off, cap - off, st)) return rc;
+        const zz_inf_members_out& R = *M.h_sres;
+        const uint64_t member = members0 + R.members;
+        if (R.status == ZI_ITEM_OK) { *out_len = off + R.out; return ZZ_OK; }
+        if (R.status == ZI_ITEM_NOSPACE) { set_err("member " + std::to_string(member) + " does not fit what is left of the destination"); return ZZ_E_NOSPACE; }
+        set_err("what stands where member " + std::to_string(member) + " would begin is not a valid gzip member");
+        return ZZ_E_DATA;
+    };
+
+    // the rows: the caller's, or the call's own (its index call's stats are put back: this call leaves the other calls' alone)
+    std::vector<uint64_t> own;
+    if (!points) {
+        const auto keep = std::make_tuple(D.mp.members_found, D.mp.header_candidates, D.mp.block_candidates, D.mp.dropped, D.mp.rounds);
+        uint64_t need = 0, total = 0;
+        int rc = zz_members_points_device(c, d_src_v, src_len, ZZ_POINTS_CHUNK_DEFAULT, 1, nullptr, 0, &need, &total, hip_stream);
+        if (rc == ZZ_E_NOSPACE) {
+            own.resize(2 * need);
+            rc = zz_members_points_device(c, d_src_v, src_len, ZZ_POINTS_CHUNK_DEFAULT, 1, own.data(), need, &need, &total, hip_stream);
+        }
+        std::tie(D.mp.members_found, D.mp.header_candidates, D.mp.block_candidates, D.mp.dropped, D.mp.rounds) = keep;
+        if (rc == ZZ_E_HIP) return rc;
+        if (rc != ZZ_OK) return serial(0, 0, 0);
+        points = own.data(); entries = need;
+    }
+    // the check, the members and the descriptors
+    uint64_t nmem = 0, nseg = 0;
+    if (!zi_mpd_plan(points, entries, src_len, nullptr, 0, nullptr, 0, &nmem, &nseg)) return serial(0, 0, 0);
+    std::vector<zi_mpd_member> mem(nmem);
+    std::vector<zi_mpd_seg> seg(nseg);
+    zi_mpd_plan(points, entries, src_len, mem.data(), nmem, seg.data(), nseg, &nmem, &nseg);
+    X.members = nmem;
+    const uint64_t mstar = zi_mpd_mstar(mem.data(), nmem, cap, limit);
+    const uint64_t dealt = mstar, dsegs = mstar < nmem ? mem[mstar].seg0 : nseg;
+    X.segments = dsegs;
+    if (dealt == 0) return serial(0, 0, 0);
+    if (dealt > 0x7FFFFFFFull) return serial(0, 0, 0);                      // (beyond one launch's dealing counter)
+    // the workspace: the largest batch, and per descriptor and member of the call
+    uint64_t max_bytes = 1, max_segs = 1;
+    for (uint64_t k0 = 0, k1; k0 < dsegs; k0 = k1) {
+        k1 = zi_mpd_batch(seg.data(), dsegs, k0, limit, ZZ_PT_BATCH_SEGMENTS);
+        max_bytes = std::max(max_bytes, seg[k1 - 1].o1 - seg[k0].o0);
+        max_segs = std::max(max_segs, k1 - k0);
+    }
+    const bool have = dec_have(dec_points_workspace(c, max_bytes, max_segs)) && dec_have(D.tot.grow(ZZ_TOT_SLOTS)) &&
+                      dec_have(X.seg.grow(dsegs)) && dec_have(X.mem.grow(dealt)) && dec_have(X.segok.grow(dsegs)) && dec_have(X.sums.grow(dsegs)) &&
+                      dec_have(X.status.grow(dealt)) && dec_have(X.first_bad.grow(1)) && dec_have(X.next.grow(1));
+    if (!have) return serial(0, 0, 0);
+    HIPCHK(hipMemcpyAsync(X.seg, seg.data(), dsegs * sizeof(zi_mpd_seg), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(X.mem, mem.data(), dealt * sizeof(zi_mpd_member), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemsetAsync(X.segok, 0, dsegs, st));
+    HIPCHK(hipMemsetAsync(X.first_bad, 0xFF, sizeof(unsigned long long), st));
+    // the batches; those behind the first that reports a refused segment are not launched (their segments' flags stay 0)
+    for (uint64_t k0 = 0, k1; k0 < dsegs; k0 = k1) {
+        k1 = zi_mpd_batch(seg.data(), dsegs, k0, limit, ZZ_PT_BATCH_SEGMENTS);
+        unsigned long long failed = 0;
+        if (int rc = mpd_batch(c, src, src_len, seg.data(), k0, (uint32_t)(k1 - k0), dst, st, &failed)) return rc;
+        if (failed) break;
+    }
+    // the verdict, and the one word the host reads of it
+    HIPCHK(hipMemsetAsync(X.next, 0, sizeof(unsigned int), st));
+    zz_mpd_verdict_params V;
+    V.src = src; V.n = src_len; V.mem = X.mem; V.nmem = (uint32_t)dealt; V.seg = X.seg; V.sums = X.sums; V.segok = X.segok;
+    V.status = X.status; V.first_bad = X.first_bad; V.next = X.next;
+    const uint64_t resident = 256ull * ZZ_MPD_WG_PER_CU;
+    hipLaunchKernelGGL(k_members_verdict, dim3((uint32_t)(dealt < resident ? dealt : resident)), dim3(ZZ_INF_THREADS), 0, st, V);
+    HIPCHK(hipGetLastError());
+    unsigned long long first_bad = 0;
+    HIPCHK(hipMemcpyAsync(&first_bad, X.first_bad, sizeof first_bad, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    const uint64_t f = first_bad < dealt ? (uint64_t)first_bad : mstar;     // the first dealt member not proven, or m*
+    if (f == nmem) { X.proven = nmem; *out_len = mem[nmem - 1].off + mem[nmem - 1].out; return ZZ_OK; }
+    return serial(f, mem[f].c, mem[f].off);
+}
+
+extern "C" int zz_ctx_last_decode_members_points_stats(const zz_ctx* c, uint64_t* members, uint64_t* proven, uint64_t* segments,
+                                                       uint32_t* batches, uint64_t* pending_bytes, uint32_t* rounds, int* serial)
+{
+    if (!c) { set_err("null ctx"); return ZZ_E_ARG; }
+    const auto& X = c->dec.mpd;
+    if (members) *members = X.members;
+    if (proven) *proven = X.proven;
+    if (segments) *segments = X.segments;
+    if (batches) *batches = X.batches;
+    if (pending_bytes) *pending_bytes = X.pending;
+    if (rounds) *rounds = X.rounds;
+    if (serial) *serial = X.serial;
     return ZZ_OK;
 }
 

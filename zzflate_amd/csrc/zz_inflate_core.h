@@ -2119,4 +2119,130 @@ ZZ_HD inline uint64_t zi_mp_to_index(const uint64_t* points, uint64_t entries, u
     return open || entries == 0 ? 0 : n;
 }
 
+// ---- decode through a member point index (zz_decode_members_points_device, zz_inflate_members_decode.h;
+// tests/cxx/members_points_decode_harness.cpp) ------------------------------------------------------------------------------------
+// The rows are never trusted: they decide speed, not the result, which is zi_members' for every input.
+//   THE ROWS ARE AN INDEX (zi_mpd_plan)  START, inner rows, END per member (zi_mp_to_index's rule); masked bits ascend strictly over
+//                        the whole array; every START bit is a multiple of 8; out_byte ascends from 0 and every END's equals the next
+//                        START's; with c_0 = 0 and c_{j+1} = zi_mp_next_offset(end_j): c_j + 10 <= start_j / 8, and the last c is
+//                        src_len. Anything else: the serial path decides on the whole file.
+//   SEGMENTS             a pair of neighbouring rows whose first is no END row: one descriptor (zi_mpd_seg) -- its two bits with the
+//                        flags masked off, its bytes [o0, o1), its member's decoded origin off_j, whether it is the member's last.
+//   DEALT                member j is dealt if it lies in front of m*, the first member whose bytes pass `cap` or that holds a segment
+//                        of more than `limit` bytes (zi_mpd_mstar). Batches are greedy runs of dealt descriptors (zi_mpd_batch).
+//   PROVEN               a dealt member is proven iff (1) zi_header(gzip) at c_j ends exactly at start_j / 8, (2) every segment of it
+//                        runs ZI_RUN_POINT from its bit to exactly the next row's bit with exactly its room, the final block in its
+//                        last segment and nowhere else, NO DISTANCE REACHING IN FRONT OF off_j (zi_out_segment::abs = o0 - off_j: abs
+//                        serves the ZI_E_FAR test and nothing else), (3) the CRC-32 of its segments' bytes, joined in order
+//                        (zi_pr_join), is the trailer's and (4) ISIZE is the low 32 bits of off_{j+1} - off_j (zi_mpd_verdict).
+// With f the first dealt member that is not proven, or m*: no f is ZI_ITEM_OK with the last row's out_byte; otherwise zi_members from
+// (c_f, off_f) over what is left of source, destination and room answers. Why that is zi_members' answer: DESIGN.md 23.
+struct zi_mpd_seg { uint64_t b0, b1, o0, o1, origin, member_last; };       // member_last = member << 1 | the member's last segment
+struct zi_mpd_member {
+    uint64_t c, first, end;          // its first byte in the file, its first block's byte, the bit behind its final block
+    uint64_t off, out;               // decoded bytes in front of it, its own
+    uint64_t seg0, nseg, longest;    // its descriptors, and its longest segment's bytes
+};
+// The rows as members and descriptors. Returns false where the rows are no index. Counts (*nmem, *nseg) are always set for an index;
+// mem / seg are written while they fit (null: counts only). One row per turn: entries turns.
+ZZ_HD inline bool zi_mpd_plan(const uint64_t* points, uint64_t entries, uint64_t src_len, zi_mpd_member* mem, uint64_t max_mem,
+                              zi_mpd_seg* seg, uint64_t max_seg, uint64_t* nmem, uint64_t* nseg)
+{
+    *nmem = 0; *nseg = 0;
+    if (entries < 2 || src_len > (~0ull >> 3)) return false;
+    if (zi_mp_to_index(points, entries, nullptr, 0) == 0) return false;    // START, inner rows, END per member
+    const zi_view<const uint64_t> p{ points, 2 * entries };
+    uint64_t c = 0, m = 0, s = 0;
+    zi_mpd_member cur{ 0, 0, 0, 0, 0, 0, 0, 0 };
+    for (uint64_t i = 0; i < entries; ++i) {
+        const uint64_t raw = p[2 * i], bit = ZZ_MP_BIT(raw), pos = p[2 * i + 1];
+        if (i == 0 ? pos != 0 : (bit <= ZZ_MP_BIT(p[2 * i - 2]) || pos < p[2 * i - 1])) return false;
+        if (raw & ZZ_MP_START) {
+            if ((bit & 7) != 0 || bit / 8 < c + 10) return false;
+            if (i && pos != p[2 * i - 1]) return false;                    // the gap between two members holds no byte
+            cur = zi_mpd_member{ c, bit / 8, 0, pos, 0, s, 0, 0 };
+            continue;
+        }
+        // an inner row or an END row closes the segment its predecessor opened
+        const uint64_t b0 = ZZ_MP_BIT(p[2 * i - 2]), o0 = p[2 * i - 1];
+        const bool last = (raw & ZZ_MP_END) != 0;
+        if (seg && s < max_seg) seg[s] = zi_mpd_seg{ b0, bit, o0, pos, cur.off, (m << 1) | (last ? 1u : 0u) };
+        ++s; ++cur.nseg;
+        if (pos - o0 > cur.longest) cur.longest = pos - o0;
+        if (!last) continue;
+        cur.end = bit; cur.out = pos - cur.off;
+        c = zi_mp_next_offset(bit);
+        if (c > src_len) return false;
+        if (mem && m < max_mem) mem[m] = cur;
+        ++m;
+    }
+    if (c != src_len) return false;
+    *nmem = m; *nseg = s;
+    return true;
+}
+// m*: the first member whose bytes pass cap or that holds a segment longer than a batch (nmem: none). off + out never shrinks.
+ZZ_HD inline uint64_t zi_mpd_mstar(const zi_mpd_member* mem, uint64_t nmem, uint64_t cap, uint64_t limit)
+{
+    for (uint64_t j = 0; j < nmem; ++j) if (mem[j].off + mem[j].out > cap || mem[j].longest > limit) return j;
+    return nmem;
+}
+// the batch that begins with descriptor k0 < n ends in front of descriptor (return value) > k0: zi_points_batches' rule on descriptors
+// (no dealt segment is longer than `limit`, and the members' bytes lie back to back, so a batch holds at most `limit` bytes)
+ZZ_HD inline uint64_t zi_mpd_batch(const zi_mpd_seg* seg, uint64_t n, uint64_t k0, uint64_t limit, uint64_t max_segs)
+{
+    uint64_t k1 = k0 + 1;
+    while (k1 < n && k1 - k0 < max_segs && seg[k1].o1 - seg[k0].o0 <= limit) ++k1;
+    return k1;
+}
+// One descriptor's phase 1 onto the destination (absolute positions), by one lane group: zi_out_segment with the member's origin.
+// `in` reads the file src[0, n); the batch's bitmap and pointers count from `base`. Returns the run's result (err == 0: condition 2).
+template <class Fence, class Bits, class In>
+ZZ_HD zi_result zi_mpd_segment(In& in, const uint8_t* src, uint64_t n, const zi_mpd_seg& d, uint8_t* dst, uint64_t base, uint32_t* pend,
+                               uint64_t words, uint32_t* st, uint64_t nbytes, zi_tables& S, uint32_t lane, uint32_t nl, uint32_t* npend)
+{
+    const zi_view<const uint8_t> view{ src, n };
+    zi_out_segment<Fence, Bits> o{ zi_view<uint8_t>{ dst + d.o0, d.o1 - d.o0 }, zi_view<uint32_t>{ pend, words }, zi_view<uint32_t>{ st, nbytes },
+                                   d.o0 - d.origin, d.o0 - base, 0, 0, false, lane, nl, {}, {} };
+    zi_pt_segment pt{ (uint32_t)(d.b0 & 7), d.b1, (d.member_last & 1) != 0, 0 };
+    S.kind = 0;
+    const zi_result R = zi_run(in, view, d.b0 >> 3, o, S, ZI_RUN_POINT, d.o1 - d.o0, lane, nl, pt);
+    *npend = o.npend;
+    return R;
+}
+// The verdict's fold. A lane's run: the sums of `per` consecutive segments of the member from its lane * per-th on, joined in
+// order; `ok` is cleared by a segment whose run was refused (or never launched). No lane joins more than per = ceil(nseg / nl) sums.
+ZZ_HD inline zi_pr_part zi_mpd_fold_run(const zi_mpd_member& M, const zi_mpd_seg* seg, const uint32_t* sums, const uint8_t* segok,
+                                        uint32_t lane, uint32_t nl, bool* ok)
+{
+    const uint64_t per = (M.nseg + nl - 1) / nl;
+    uint64_t k0 = M.seg0 + (uint64_t)lane * per, k1 = k0 + per;
+    if (k0 > M.seg0 + M.nseg) k0 = M.seg0 + M.nseg;
+    if (k1 > M.seg0 + M.nseg) k1 = M.seg0 + M.nseg;
+    zi_pr_part acc{ 0, 0 };
+    for (uint64_t k = k0; k < k1; ++k) {
+        if (!segok[k]) *ok = false;
+        acc = zi_pr_join(ZI_CKS_CRC, acc, zi_pr_part{ sums[k], seg[k].o1 - seg[k].o0 });
+    }
+    return acc;
+}
+// one step of the tree over the lanes' runs part[0, nl), nl a power of two: step o = 1, 2, 4, ... joins lane + o onto every lane that is
+// a multiple of 2 o; behind the step o = nl / 2 part[0] is the member's. A barrier stands between two steps.
+ZZ_HD inline void zi_mpd_fold_step(zi_pr_part* part, uint32_t lane, uint32_t nl, uint32_t o)
+{
+    if ((lane & (2 * o - 1)) == 0 && lane + o < nl) part[lane] = zi_pr_join(ZI_CKS_CRC, part[lane], part[lane + o]);
+}
+// conditions 1, 3, 4 (and 2 through segs_ok) of member M of the file src[0, n): true iff it is proven. `all`: its segments' sums joined.
+ZZ_HD inline bool zi_mpd_verdict(const uint8_t* src, uint64_t n, const zi_mpd_member& M, const zi_pr_part& all, bool segs_ok)
+{
+    if (!segs_ok || M.c > n || all.len != M.out) return false;
+    const int64_t hl = zi_header(1, src + M.c, n - M.c);
+    if (hl < 0 || (uint64_t)hl != M.first - M.c) return false;
+    const uint64_t t0 = (M.end + 7) >> 3;
+    if (t0 > n || n - t0 < 8) return false;
+    const zi_view<const uint8_t> t{ src + t0, 8 };
+    const uint32_t c = t[0] | ((uint32_t)t[1] << 8) | ((uint32_t)t[2] << 16) | ((uint32_t)t[3] << 24);
+    const uint32_t l = t[4] | ((uint32_t)t[5] << 8) | ((uint32_t)t[6] << 16) | ((uint32_t)t[7] << 24);
+    return c == all.v && l == (uint32_t)M.out;
+}
+
 }  // namespace zz
